@@ -1,20 +1,24 @@
 #!/usr/bin/env python3
 """Benchmark of the EAV per-modality training step on MI355X (BASELINE.json metric and configs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torchrun environment the script starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py ...` itself, as a CHILD process and
 before anything touches the GPU, and relays the child's JSON line and exit code.
 
-Output contract: rank 0 prints ONE compact JSON headline (< 4 KB, asserted < 8 KB) as the LAST stdout line - metric, value,
-ms_per_step, roofline, cpu_baseline and one short record per modality - and writes everything else (phases, notes,
-front-ends, trainer epochs, alternative encoders, the strong-scaling proxy) to `bench_detail.json` next to this file (and
-to gpurun_out/ when that directory exists).  Headline: EEGNet_tor train step on x[64,1,30,10000] fp32 per GPU (configs[1]) -
-batch gather from the HBM-resident synthetic subject, forward, CrossEntropy on the softmax output, backward, (gradient
-all-reduce when N > 1), fused Adam: the body of Trainer_uni.train() (CNN_torch/EEGNet_tor.py:99-110), nothing skipped.
-`modalities` holds one object per modality (EEGNet / AST / ViT) with its own throughput, dominant-kernel roofline and
-same-run CPU baseline; `multi_gpu` holds the strong-scaling and subject-sharded (42 subjects) legs when N > 1.
+Output contract: rank 0 prints ONE compact JSON headline (< 4 KB, asserted < 8 KB) as the LAST stdout line.  A plain run sets
+up, runs the W warm-up steps, times the K steps and prints metric, value, unit, ms_per_step (one timed step), dtype and the
+config.  --full adds everything else: the per-kernel roofline pass, repeat blocks, CPU baselines and one short record per
+modality in the headline, and the phases, notes, front-ends, trainer epochs, alternative encoders and the strong-scaling
+proxy in `bench_detail.json` next to this file (and a copy in the run's output directory when there is one).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy; with the same arguments the inputs are the
+same from run to run, so two builds can be compared output for output.
+Headline: EEGNet_tor train step on x[64,1,30,10000] fp32 per GPU (configs[1]) - batch gather from the HBM-resident
+synthetic subject, forward, CrossEntropy on the softmax output, backward, (gradient all-reduce when N > 1), fused Adam: the
+body of Trainer_uni.train() (CNN_torch/EEGNet_tor.py:99-110), nothing skipped.  Under --full, `modalities` holds one object
+per modality (EEGNet / AST / ViT) with its own throughput, dominant-kernel roofline and same-run CPU baseline, and
+`multi_gpu` the strong-scaling and subject-sharded (42 subjects) legs when N > 1.
 HIP-extension only: a missing libeav_hip.so raises on import (no CPU fallback); `oracle/` is imported for `cpu_baseline` only.
 """
 import argparse
@@ -287,6 +291,7 @@ def _subject_job_record(sched, world, n_subjects, steps, batch, times, have, dev
            "ideal_speedup_round_robin": round(eav_dist.subject_schedule(sched.world, n_subjects, hybrid=False).ideal_speedup(), 3),
            "speedup_vs_one_gpu_rate_of_this_run": round(value / one_gpu, 3) if one_gpu else None,
            "all_subjects_reported": bool((have > 0).all().item()),
+           "final_losses": [float(v) for v in have.tolist()],
            "scaling": "strong (total work fixed: every subject once)",
            "note": "independent per-subject trainings; no collective on the data path of the whole rounds, gradient "
                    "all-reduce only inside the tail groups, one all_gather of the results"}
@@ -797,6 +802,11 @@ def compact_headline(out):
                                 "scaling", "vs_baseline", "dtype", "data")}
     cfg = out["config"]
     line["config"] = {k: cfg[k] for k in ("workload", "global_batch", "per_gpu_batch", "parallelism")}
+    for k in ("ideal_speedup", "speedup_vs_ideal"):
+        if out.get(k) is not None:
+            line[k] = out[k]
+    if "roofline" not in out:             # a plain run (no --full): the headline fields only, no detail file
+        return line
     line["roofline"] = _short_roofline(dict(out["roofline"], algorithmic_bytes=out["roofline"].get("algorithmic_bytes")))
     line["roofline"]["flop_per_launch"] = out["roofline"].get("flop_per_launch")
     line["roofline"]["avg_kernel_ms"] = out["roofline"].get("avg_kernel_ms", {}).get(
@@ -846,9 +856,6 @@ def compact_headline(out):
             if e.get("speedup_vs_ideal") is not None:
                 short[f"{kind}_subjects_speedup_vs_ideal"] = e["speedup_vs_ideal"]
         line["multi_gpu"] = short
-    for k in ("ideal_speedup", "speedup_vs_ideal"):
-        if out.get(k) is not None:
-            line[k] = out[k]
     if out.get("subject_loop_check"):
         line["subject_loop_vs_plain_step_rate"] = out["subject_loop_check"]["ratio_to_plain_step_rate"]
     # (the single-GPU proxy of the Mode-G scaling curve is a prediction, not a measurement: detail file only)
@@ -867,6 +874,10 @@ def emit(out):
                 json.dump(out, f, indent=1)
         except OSError as e:                      # a read-only tree must not cost the headline
             print(f"bench.py: could not write {p}: {e}", file=sys.stderr)
+    print_headline(out)
+
+
+def print_headline(out):
     line = json.dumps(compact_headline(out), separators=(",", ":"))
     assert len(line) < 8192, f"headline grew to {len(line)} bytes - the driver's parser needs a compact line"
     sys.stdout.flush()
@@ -1006,7 +1017,21 @@ class EEGRun:
         key = (bool(self.model.training), self.sync is not None)
         if key not in self.graphs:       # one captured graph per BatchNorm mode / kernel set, like Trainer_uni
             self.graphs[key] = GraphStep(self.model, self.opt, self.crit, self.xs, self.ys, self.batch, self.sync)
-        return self.graphs[key].run(self.batches[i % len(self.batches)])[1]
+        self.last = self.graphs[key].run(self.batches[i % len(self.batches)])      # (scores, loss) of this step
+        return self.last[1]
+
+    def outputs(self, step=True):
+        """What a caller of the training step holds after the last one: that step's softmax scores and loss (step=True),
+        the updated parameters and BatchNorm buffers (host float32 / float64 arrays, for --dump-outputs)."""
+        out = {}
+        if step:
+            scores, loss = self.last
+            out = {"scores": scores.float().cpu().numpy(), "loss": loss.float().reshape(1).cpu().numpy()}
+        for k, p in self.model.named_parameters():
+            out["param." + k] = p.detach().float().cpu().numpy()
+        for k, b in self.model.named_buffers():
+            out["buffer." + k] = b.detach().cpu().numpy().astype("float64" if not b.is_floating_point() else "float32")
+        return out
 
     def eager_step(self, i):
         from eav_amd.eegnet import gather_batch
@@ -1127,6 +1152,62 @@ def bench_eeg_subjects(dev, rank, world, steps, warmup, solo=None, n_subjects=42
     return _subject_job_record(sched, world, n_subjects, steps, B_PER_GPU, [dt, t_solo, t_all - t_solo], have, dev, hybrid)
 
 
+def headline_record(args, world, per_gpu, mode, dt, subj, final_loss=None):
+    """The headline fields of the record, from the K timed steps (dt seconds) or the N > 1 subject job (subj)."""
+    from eav_amd import dist as eav_dist
+    bk = eav_dist.backend_name()
+    via = f"torch.distributed backend '{bk}'" + (" = RCCL" if bk == "nccl" else "")
+    if subj is not None:
+        value = subj["value"]
+        gb, scaling = subj["subjects"] * B_PER_GPU, "strong"
+        workload = (f"{subj['subjects']} independent per-subject trainings of EEGNet_tor(5, Chans=30, Samples=10000, "
+                    f"kernLength=300, F1=8, D=8, F2=64), {args.steps} optimiser steps each on x[64,1,30,10000] fp32 "
+                    f"(BASELINE.json configs[1] per subject, configs[4] across GPUs); a step = one optimiser step of "
+                    f"every subject model")
+        sch = subj["schedule"]
+        par = (f"subjects over {world} ranks: {sch['rounds']} whole rounds one subject per rank, no collective"
+               + (f"; the {len(sch['groups'])} remaining subjects on groups of {sch['group_size']} ranks (batch split, "
+                  f"gradient all-reduce inside the group, {via})" if sch["groups"] else "")
+               + f"; ideal speed-up {subj['ideal_speedup']}")
+    else:
+        value = round(args.steps * per_gpu * world / dt, 2)
+        # (one GPU: there is nothing to scale - "none"; the N > 1 labels say how per-GPU work changes with N)
+        gb, scaling = per_gpu * world, ("none" if world == 1 else mode)
+        workload = ("EEGNet_tor(5, Chans=30, Samples=10000, kernLength=300, F1=8, D=8, F2=64) "
+                    f"train step on x[{per_gpu},1,30,10000] fp32 per GPU (BASELINE.json configs[1])")
+        par = f"dp{world}" + (f" (ONE training, gradient all-reduce over {via})" if world > 1 else "")
+    out = {
+        "metric": "EEGNet training samples/sec (fwd+CE+bwd+Adam), whole job",
+        "value": value, "unit": "samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload, "global_batch": gb, "per_gpu_batch": per_gpu, "parallelism": par,
+                   "optimizer": "Adam lr=1e-5", "dropout": 0.5,
+                   "launch": "hipGraph replay of the whole step (Trainer_uni's own path: GraphStep)"},
+    }
+    if final_loss is not None:
+        out["config"]["final_loss"] = round(final_loss, 5)
+    if subj is not None:
+        out["speedup_vs_ideal"] = subj.get("speedup_vs_ideal")
+        out["ideal_speedup"] = subj["ideal_speedup"]
+    return out
+
+
+def dump_outputs(path, run, subj):
+    """--dump-outputs: what the timed path computed in its last step, as <path>/<name>.npy (float32 / float64, well under
+    64 MB).  N = 1: the step's scores and loss, the updated parameters and BatchNorm buffers.  N > 1 subject job: every
+    subject's final loss and the parameters / buffers of this rank's last model."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = run.outputs(step=subj is None)
+    if subj is not None:
+        arrays["subject_final_losses"] = np.asarray(subj["final_losses"], dtype=np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1136,12 +1217,20 @@ def main():
                     help="N > 1, what the headline times: subjects = the 42 per-subject trainings sharded over the ranks, "
                          "total work fixed (default; comparable with the N = 1 value); strong = ONE training, global "
                          "batch 64 split over N, gradient all-reduce; weak = 64 samples per GPU per step")
-    ap.add_argument("--repeats", type=int, default=4, help="extra K-step blocks timed after the headline block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-encoders", action="store_true", help="skip the AST / ViT / alternative-encoder sections")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the per-kernel roofline pass, repeat blocks, the subject-loop check, "
+                         "the eval-mode step, CPU baselines, the AST / ViT / alternative encoders, front-ends, trainer epochs, "
+                         "the N > 1 side legs, and bench_detail.json; without it a run sets up, warms up, times the K steps "
+                         "and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (scores, loss, updated parameters and "
+                         "BatchNorm buffers; N > 1: every subject's final loss) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=4, help="--full: extra K-step blocks timed after the headline block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-encoders", action="store_true", help="--full: skip the AST / ViT / alternative-encoder sections")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the detail-only legs (comparison precisions, strong-scaling proxy, trainer epochs, front-ends, "
-                         "alternative encoders): headline + per-modality records only")
+                    help="--full: skip the detail-only legs (comparison precisions, strong-scaling proxy, trainer epochs, "
+                         "front-ends, alternative encoders): headline + per-modality records only")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args))
@@ -1177,29 +1266,42 @@ def main():
     if mode != "subjects":
         for i in range(3):                                   # set-up first: two eager steps, the third call captures the graph
             run.step(i)                                      # (its host work leaves the GPU idle for tens of milliseconds)
+    # (a plain run issues the same eager steps untraced: they are training steps the timed ones follow, so that its K steps
+    # compute what --full's compute, and they keep the GPU busy after the capture's idle gap)
     n_eager = min(args.steps, 20)
     run.eager_step(args.warmup)
     torch.cuda.synchronize()
-    eavlib.TRACE = {}
+    eavlib.TRACE = {} if args.full else None
     for i in range(n_eager):
         run.eager_step(args.warmup + i)
     torch.cuda.synchronize()
     trace, eavlib.TRACE = eavlib.TRACE, None
-    kern_ms = {k: sum(a.elapsed_time(b) for a, b in v) / len(v) for k, v in trace.items() if v}            # per call
-    kern_step_ms = {k: sum(a.elapsed_time(b) for a, b in v) / n_eager for k, v in trace.items() if v}       # per step
-    del trace
+    if args.full:
+        kern_ms = {k: sum(a.elapsed_time(b) for a, b in v) / len(v) for k, v in trace.items() if v}            # per call
+        kern_step_ms = {k: sum(a.elapsed_time(b) for a, b in v) / n_eager for k, v in trace.items() if v}       # per step
+        del trace
     subj = None
     if mode == "subjects":
         # THE timed region for N > 1: K optimiser steps of EVERY one of the 42 subject models (a job step = one step of
         # each), subjects sharded over the ranks - fixed total work, so `value` is comparable with the N = 1 value
         subj = bench_eeg_subjects(dev, rank, world, args.steps, args.warmup, solo=run)
         dt = subj["seconds"]
-        for i in range(3):
-            loss = run.step(i)
     else:
         for i in range(args.warmup):                         # the W warm-up steps: replays, like the K timed ones
             run.step(i)
         dt, loss = run.timed(args.steps, args.warmup)       # THE timed region: exactly K steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run, subj)
+    if not args.full:
+        if rank == 0:
+            print_headline(headline_record(args, world, per_gpu, mode, dt, subj))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    if mode == "subjects":
+        for i in range(3):
+            loss = run.step(i)
     final_loss = float(loss.item())
     blocks_ms = [dt / args.steps * 1e3] if subj is None else []
     for _ in range(args.repeats):                            # spread of the same K-step block (one model, this rank)
@@ -1367,47 +1469,16 @@ def main():
                                  "hbm_gbps_algorithmic": round(abytes[k] / (kern_ms[k] * 1e-3) / 1e9, 1)}
         roofline["fir_kernels"] = fir
         cpu_eeg = cpu_baseline_eegnet() if (world == 1 and not args.no_cpu_baseline) else None
-        bk = eav_dist.backend_name()
-        via = f"torch.distributed backend '{bk}'" + (" = RCCL" if bk == "nccl" else "")
-        if subj is not None:
-            value = subj["value"]
-            gb, scaling = subj["subjects"] * B_PER_GPU, "strong"
-            workload = (f"{subj['subjects']} independent per-subject trainings of EEGNet_tor(5, Chans=30, Samples=10000, "
-                        f"kernLength=300, F1=8, D=8, F2=64), {args.steps} optimiser steps each on x[64,1,30,10000] fp32 "
-                        f"(BASELINE.json configs[1] per subject, configs[4] across GPUs); a step = one optimiser step of "
-                        f"every subject model")
-            sch = subj["schedule"]
-            par = (f"subjects over {world} ranks: {sch['rounds']} whole rounds one subject per rank, no collective"
-                   + (f"; the {len(sch['groups'])} remaining subjects on groups of {sch['group_size']} ranks (batch split, "
-                      f"gradient all-reduce inside the group, {via})" if sch["groups"] else "")
-                   + f"; ideal speed-up {subj['ideal_speedup']}")
-        else:
-            value = round(args.steps * per_gpu * world / dt, 2)
-            # (one GPU: there is nothing to scale - "none"; the N > 1 labels say how per-GPU work changes with N)
-            gb, scaling = per_gpu * world, ("none" if world == 1 else ("strong" if strong else "weak"))
-            workload = ("EEGNet_tor(5, Chans=30, Samples=10000, kernLength=300, F1=8, D=8, F2=64) "
-                        f"train step on x[{per_gpu},1,30,10000] fp32 per GPU (BASELINE.json configs[1])")
-            par = f"dp{world}" + (f" (ONE training, gradient all-reduce over {via})" if world > 1 else "")
-        out = {
-            "metric": "EEGNet training samples/sec (fwd+CE+bwd+Adam), whole job",
-            "value": value, "unit": "samples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "global_batch": gb, "per_gpu_batch": per_gpu, "parallelism": par,
-                       "optimizer": "Adam lr=1e-5", "dropout": 0.5, "final_loss": round(final_loss, 5),
-                       "launch": "hipGraph replay of the whole step (Trainer_uni's own path: GraphStep)"},
+        out = headline_record(args, world, per_gpu, mode, dt, subj, final_loss)
+        out.update({
             "repeat_blocks": {"ms_per_step": [round(v, 4) for v in blocks_ms],
                               "median_ms_per_step": round(statistics.median(blocks_ms), 4),
                               "min_ms_per_step": round(min(blocks_ms), 4),
                               "note": f"{len(blocks_ms)} blocks of {args.steps} steps of ONE model on this rank" +
                                       ("; `value` is the first block" if subj is None else "")},
             "roofline": roofline,
-        }
-        if subj is not None:
-            out["speedup_vs_ideal"] = subj.get("speedup_vs_ideal")
-            out["ideal_speedup"] = subj["ideal_speedup"]
+        })
+        value = out["value"]
         if subj_check is not None:
             plain = B_PER_GPU / (statistics.median(blocks_ms) * 1e-3)
             out["subject_loop_check"] = dict(subj_check, plain_step_rate=round(plain, 2),

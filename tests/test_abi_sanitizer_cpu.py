@@ -58,7 +58,9 @@ def test_host_half_of_the_abi_is_clean_under_asan_and_ubsan(tmp_path):
     assert rts, "ASan runtime of the ROCm clang not found"
     script = tmp_path / "child.py"
     script.write_text(f"ROOT = {ROOT!r}\nLIBPATH = {libpath!r}\n" + textwrap.dedent(CHILD))
-    env = dict(os.environ, LD_PRELOAD=rts[-1],
+    # the ASan runtime goes first; whatever the environment already preloads stays in the list
+    preload = " ".join([rts[-1]] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else []))
+    env = dict(os.environ, LD_PRELOAD=preload,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=97:verify_asan_link_order=0",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=98")
     r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, env=env, timeout=900)

@@ -281,6 +281,40 @@ def test_bench_headline_is_compact_and_complete():
         assert {"value", "ms_per_step", "batch", "roofline", "cpu_baseline"} <= set(m)
 
 
+def test_bench_plain_headline_and_output_dump(tmp_path):
+    """A plain bench.py run (no --full) prints the headline fields only - metric, value, unit, ms_per_step of ONE timed
+    step, higher_is_better, dtype - and --dump-outputs writes float32 / float64 .npy files named after the outputs."""
+    import argparse
+    import importlib.util
+    import json
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = argparse.Namespace(steps=20, warmup=5)
+    rec = bench.headline_record(args, 1, 64, "single", 20 * 1.25e-3, None)
+    head = json.loads(json.dumps(bench.compact_headline(rec), separators=(",", ":")))
+    assert abs(head["ms_per_step"] - 1.25) < 1e-9 and abs(head["value"] - 64 / 1.25e-3) < 0.01
+    assert head["unit"] == "samples/s" and head["higher_is_better"] is True and head["dtype"] == "f32"
+    assert head["steps"] == 20 and head["warmup"] == 5 and head["scaling"] == "none"
+    assert not {"roofline", "cpu_baseline", "modalities", "detail"} & set(head)
+
+    class Run:
+        def outputs(self, step=True):
+            out = {"param.w": np.ones((3, 4), np.float32), "buffer.n": np.array(7.0)}
+            if step:
+                out.update(scores=np.full((64, 5), 0.2, np.float32), loss=np.ones(1, np.float32))
+            return out
+    bench.dump_outputs(str(tmp_path / "one"), Run(), None)
+    bench.dump_outputs(str(tmp_path / "job"), Run(), {"final_losses": [1.5] * 42})
+    assert sorted(os.listdir(tmp_path / "one")) == ["buffer.n.npy", "loss.npy", "param.w.npy", "scores.npy"]
+    assert sorted(os.listdir(tmp_path / "job")) == ["buffer.n.npy", "param.w.npy", "subject_final_losses.npy"]
+    for d in ("one", "job"):
+        for f in os.listdir(tmp_path / d):
+            assert np.load(tmp_path / d / f).dtype in (np.float32, np.float64), f
+
+
 def test_bench_subject_job_record_and_multi_gpu_headline():
     """The N > 1 headline of bench.py: a fixed-total-work (42 subjects) rate comparable with the N = 1 step rate.  The record
     arithmetic on CPU: value = subjects x steps x batch / seconds (doubling the time of the busiest rank halves it), the

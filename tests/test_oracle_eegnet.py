@@ -52,6 +52,15 @@ def test_oracle_matches_reference_steps(golden_dir, case):
     st = orc.Stepper(P, Bf, lr=float(g["lr"]), drop_p=float(g["drop_p"]))
     training = bool(int(g["train_mode"]))
     for s in range(int(g["steps"])):
+        if s > 0:
+            # step s starts from the reference's own state after step s - 1 (checked just above): the few elements whose
+            # Adam update is ill-conditioned (_close_params) would otherwise reach every output of step s through a
+            # difference that the host CPU's rounding decides, not the oracle's arithmetic
+            with torch.no_grad():
+                for k in orc.PARAM_NAMES:
+                    st.P[k].copy_(torch.from_numpy(g[f"post{s - 1}.{k}"]))
+                for k in orc.BUFFER_NAMES:
+                    st.Bf[k].copy_(torch.from_numpy(g[f"post{s - 1}.{k}"]))
         x, y = synth.eeg_batch(int(g["xseed"]) + s, B, a["chans"], S, a["nb"])
         masks = None
         if float(g["drop_p"]) > 0:
