@@ -142,6 +142,9 @@ SIGNATURES = {
     "eav_peak_copy_variant": [_p, _p, _i64, _i, _i, _p],
     "eav_peak_l2_read": [_p, _i, _i, _i, _i, _p, _p],
     "eav_resize_normalize_u8": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p],
+    "eav_audio_conv5_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _u64, _p, _p, _p],
+    "eav_audio_conv5_dgrad": [_p, _p, _f, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _p],
+    "eav_audio_conv5_wgrad": [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _p],
 }
 # helpers that return a plain value (no status)
 PLAIN = {
@@ -172,6 +175,7 @@ PLAIN = {
     "eav_sp_convert_colsum_nparts": ([_i], _i),
     "eav_attn_sp_npad": ([_i], _i),
     "eav_gemm_sp_splitk_plan": ([_i, _i, _i], _i),
+    "eav_audio_wgrad_nparts": ([_i, _i, _i, _i], _i),
 }
 
 EXPORTS = sorted(list(SIGNATURES) + list(PLAIN))

@@ -545,6 +545,33 @@ int eav_decimate_fir_f64(const double* x, const double* h, double* y, int nch, i
 int eav_sosfilt_f64(const double* x, double* y, const double* sos, const double* H, const double* AL, double* zend,
                     double* zstart, int nch, int64_t n, int nsec, int Lc, void* stream);
 
+/* ---- audio CNN (CNN_torch/CNN_audio.py AudioModel; csrc/audio_cnn.hip) -------------------------------------------
+ * Every conv of the model is Conv1d(kernel 5, padding 2) with a bias; tensors are [B][channels][length] fp32.
+ * Forward: out = ReLU(conv(in) + bias), then (drop_p > 0) dropout - mask (uint8 [B][N][Lin], may be NULL) or the
+ * counter-based generator (seed + 2 * *seed_dev when seed_dev is set) - and with pool = 1 MaxPool1d(8): out is
+ * [B][N][Lout/8] and idx receives the argmax within each window (first index on ties, NaN propagates).  pool = 0 needs
+ * Lout == Lin; pool = 1 needs Lin / 8 == Lout / 8 (the classifier's fixed width: T in Lout...Lout+7) and C % 16 == 0;
+ * C is 1 or a multiple of 16. */
+int eav_audio_conv5_fwd(const float* in, const float* w, const float* bias, float* out, uint8_t* idx, int B, int C,
+                        int N, int Lin, int Lout, int pool, float drop_p, uint64_t seed, const uint8_t* mask,
+                        const uint64_t* seed_dev, void* stream);
+/* Data gradient of a conv whose weight is w [C][N][5] (C = the layer's output channels, N = its input channels):
+ * din[b][n][t] = sum_{c,tap} w[c][n][tap] g[b][c][t - tap + 2] for t < Lout, g = dout [B][C][Lin] times
+ * (gate_in > 0 ? gscale_in : 0) when gate_in is set.  mode 0: din [B][N][Lout], zero where aux [B][N][Lout] <= 0 (ReLU
+ * backward; aux may be NULL).  mode 1 (MaxPool1d(8) + dropout + ReLU backward): din is the dense [B][N][8 Lout] gradient
+ * of the pre-pool activation: at 8 t + idx[b][n][t] it holds the product times gscale_out where the pooled value aux
+ * [B][N][Lout] is > 0, zero elsewhere.  C % 16 == 0. */
+int eav_audio_conv5_dgrad(const float* dout, const float* gate_in, float gscale_in, const float* w, float* din,
+                          const float* aux, const uint8_t* idx, float gscale_out, int B, int C, int N, int Lin, int Lout,
+                          int mode, void* stream);
+/* Weight + bias gradient partials: part[p][m * Cact * 5 + c * 5 + tap] = sum dout[b][m][t] act[b][c][t + tap - 2],
+ * part[p][M * Cact * 5 + m] = sum dout[b][m][t], over the (sample, 32-position) chunks p, p + nparts, ... (dout [B][M][Lout]
+ * times (gate > 0 ? gscale : 0) when gate is set; act [B][Cact][Lact], zero outside).  eav_reduce_partials sums them in
+ * fixed order into the adjacent weight and bias gradients.  nparts must be eav_audio_wgrad_nparts(B, Cact, M, Lout). */
+int eav_audio_wgrad_nparts(int B, int Cact, int M, int Lout);
+int eav_audio_conv5_wgrad(const float* dout, const float* gate, float gscale, const float* act, float* part, int B,
+                          int Cact, int M, int Lact, int Lout, int nparts, void* stream);
+
 /* ---- measured peaks (bench.py): register-only fp32 MFMA loop (FLOP = blocks*4 waves*iters*4*4096) and a float4
  *      streaming copy, to quote roofline fractions against what this chip sustains. */
 int eav_peak_mfma_f32(float* sink, int blocks, int iters, void* stream);
