@@ -98,6 +98,45 @@ def post_close(got, ref, lr, what):
     assert err.max() <= 2 * lr + 1e-3 * np.abs(ref).max(), f"{what}: {err.max():.3e}"
 
 
+def kernels_match_restatement(model, opt, ref, x, y, masks, keep, ref_logits, ref_loss, rgrads, tag=""):
+    """One forward and backward of the kernels from `model`'s parameters against the CPU restatement's (ref_logits,
+    ref_loss, rgrads and keep from cpu_logits at the same parameters; ref: a module to copy for the rerouted restatement):
+    logits and loss 5e-5, every gradient element 1e-3 of its tensor's max (plus conv1's ReLU boundary slack)."""
+    import copy
+    from eav_amd.optim import CrossEntropyLoss
+    named = dict(model.named_parameters())
+    ref_crit = torch.nn.CrossEntropyLoss()
+    if masks is not None:
+        model.set_dropout_masks(tuple(torch.from_numpy(m).cuda() for m in masks))
+    logits = model(torch.from_numpy(x).cuda().permute(0, 2, 1))
+    loss = CrossEntropyLoss()(logits, torch.from_numpy(y).cuda())
+    opt.zero_grad()
+    loss.backward()
+    close(logits, ref_logits.detach().numpy(), 0, 5e-5, f"logits{tag}")
+    close(loss, ref_loss.detach().numpy(), 0, 5e-5, f"loss{tag}")
+    # MaxPool(8) decides by comparison: where the kernels' argmax differs from the restatement's, the two window
+    # values must tie to fp32 rounding; the comparison target is then the restatement routed like the kernels
+    gidx = model._ws.idx2.long().cpu()
+    h = keep["h"][..., :176].unflatten(2, (22, 8))
+    cidx = h.argmax(3)
+    diff = gidx != cidx
+    if diff.any():
+        hv = lambda i: h.gather(3, i.unsqueeze(3)).squeeze(3)[diff]  # noqa: E731
+        assert ((hv(gidx) - hv(cidx)).abs() <= 1e-5 * h.abs().max()).all(), "pool argmax differs beyond a tie"
+        rr = copy.deepcopy(ref)
+        with torch.no_grad():
+            for k, v in rr.named_parameters():
+                v.copy_(named[k].detach().cpu())
+        keep = {}
+        ref_crit(cpu_logits(rr, torch.from_numpy(x).permute(0, 2, 1), masks, keep, gidx),
+                 torch.from_numpy(y)).backward()
+        rgrads = {k: v.grad for k, v in rr.named_parameters()}
+    slack = relu_boundary_slack(torch.from_numpy(x).permute(0, 2, 1), keep)
+    for k in PN:
+        r = rgrads[k].numpy()
+        close(named[k].grad, r, 0, 1e-3 * np.abs(r).max() + 1e-9 + slack.get(k, 0.0), f"grad{tag}.{k}")
+
+
 @pytest.mark.parametrize("case", ["t180_adam", "eval", "t176", "t183"])
 def test_steps_match_reference_golden(golden_dir, case):
     """The golden holds the imported reference's logits and loss, and strided samples plus |sum| / max of every gradient
@@ -109,7 +148,7 @@ def test_steps_match_reference_golden(golden_dir, case):
     its own throughout."""
     import copy
     from eav_amd.cnn_audio import AudioModel
-    from eav_amd.optim import CrossEntropyLoss, FusedAdam
+    from eav_amd.optim import FusedAdam
     g = np.load(os.path.join(golden_dir, f"audio_cnn_{case}.npz"))
     B, T, lr, steps = int(g["B"]), int(g["T"]), float(g["lr"]), int(g["steps"])
     training = bool(int(g["train_mode"]))
@@ -118,7 +157,7 @@ def test_steps_match_reference_golden(golden_dir, case):
     ref = copy.deepcopy(model).train(training)
     ref_crit, ref_opt = torch.nn.CrossEntropyLoss(), torch.optim.Adam(ref.parameters(), lr=lr)
     model = model.cuda().train(training)
-    crit, opt = CrossEntropyLoss(), FusedAdam(model.parameters(), lr=lr)
+    opt = FusedAdam(model.parameters(), lr=lr)
     named, rnamed = dict(model.named_parameters()), dict(ref.named_parameters())
     for s in range(steps):
         x = synth.normal(int(g["xseed"]) + s, (B, T, 1))
@@ -141,43 +180,35 @@ def test_steps_match_reference_golden(golden_dir, case):
             if f"post{s}.{k}" in g.files:
                 pin(rnamed[k], g, f"post{s}.{k}", 1e-4)
         # the kernels, from the same parameters
-        if training:
-            model.set_dropout_masks(tuple(torch.from_numpy(m).cuda() for m in masks))
-        logits = model(torch.from_numpy(x).cuda().permute(0, 2, 1))
-        loss = crit(logits, torch.from_numpy(y).cuda())
-        opt.zero_grad()
-        loss.backward()
-        close(logits, ref_logits.detach().numpy(), 0, 5e-5, f"logits{s}")
-        close(loss, ref_loss.detach().numpy(), 0, 5e-5, f"loss{s}")
-        # MaxPool(8) decides by comparison: where the kernels' argmax differs from the restatement's, the two window
-        # values must tie to fp32 rounding; the comparison target is then the restatement routed like the kernels
-        gidx = model._ws.idx2.long().cpu()
-        h = keep["h"][..., :176].unflatten(2, (22, 8))
-        cidx = h.argmax(3)
-        diff = gidx != cidx
-        if diff.any():
-            hv = lambda i: h.gather(3, i.unsqueeze(3)).squeeze(3)[diff]  # noqa: E731
-            assert ((hv(gidx) - hv(cidx)).abs() <= 1e-5 * h.abs().max()).all(), "pool argmax differs beyond a tie"
-            rr = copy.deepcopy(ref)
-            with torch.no_grad():
-                for k, v in rr.named_parameters():
-                    v.copy_(named[k].detach().cpu())
-            keep = {}
-            ref_crit(cpu_logits(rr, torch.from_numpy(x).permute(0, 2, 1), masks, keep, gidx),
-                     torch.from_numpy(y)).backward()
-            rgrads = {k: v.grad for k, v in rr.named_parameters()}
-        else:
-            rgrads = {k: rnamed[k].grad for k in PN}
-        slack = relu_boundary_slack(torch.from_numpy(x).permute(0, 2, 1), keep)
-        for k in PN:
-            r = rgrads[k].numpy()
-            close(named[k].grad, r, 0, 1e-3 * np.abs(r).max() + 1e-9 + slack.get(k, 0.0), f"grad{s}.{k}")
+        kernels_match_restatement(model, opt, ref, x, y, masks, keep, ref_logits, ref_loss,
+                                  {k: rnamed[k].grad for k in PN}, str(s))
         opt.step()
         torch.cuda.synchronize()
         if f"post{s}.{PN[0]}" in g.files:
             for k in PN:
                 post_close(named[k], rnamed[k], lr, f"post{s}.{k}")
 
+
+
+@pytest.mark.parametrize("B,T", [(1, 181), (130, 177)])
+def test_step_matches_restatement_off_golden(B, T):
+    """The model's own wiring at two lengths and batch sizes the goldens do not hold, with explicit dropout masks: B = 1
+    puts every weight gradient through the clamped nparts path (one 32-position chunk per part), B = 130 through the
+    split one; held to the CPU restatement as in test_steps_match_reference_golden."""
+    import copy
+    from eav_amd.optim import FusedAdam
+    ref = seeded_model(31, "cpu").train()
+    model = copy.deepcopy(ref).cuda().train()
+    opt = FusedAdam(model.parameters(), lr=1e-3)
+    x = synth.normal(40 + B, (B, T, 1))
+    y = synth.labels(41 + B, B, 5)
+    masks = golden_masks(42 + B, 0, B, T)
+    keep = {}
+    ref_logits = cpu_logits(ref, torch.from_numpy(x).permute(0, 2, 1), masks, keep)
+    ref_loss = torch.nn.CrossEntropyLoss()(ref_logits, torch.from_numpy(y))
+    ref_loss.backward()
+    kernels_match_restatement(model, opt, ref, x, y, masks, keep, ref_logits, ref_loss,
+                              {k: p.grad for k, p in ref.named_parameters()})
 
 def _one_step(x, y, masks=None, seed=21):
     from eav_amd.optim import CrossEntropyLoss
