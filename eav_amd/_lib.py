@@ -145,6 +145,20 @@ SIGNATURES = {
     "eav_audio_conv5_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _u64, _p, _p, _p],
     "eav_audio_conv5_dgrad": [_p, _p, _f, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _p],
     "eav_audio_conv5_wgrad": [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "eav_video_conv_relayout": [_p, _p, _p, _i, _i, _i, _p],
+    "eav_video_conv_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "eav_video_conv_dgrad": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "eav_video_conv_wgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "eav_video_bn_stats": [_p, _p, _i64, _i, _p],
+    "eav_video_bn_apply": [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _p],
+    "eav_video_bn_bwd": [_p, _p, _p, _p, _p, _p, _i64, _i, _p],
+    "eav_video_maxpool_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "eav_video_maxpool_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "eav_video_head_pool": [_p, _p, _p, _i, _i, _i, _p],
+    "eav_video_head_scale_pool": [_p, _p, _p, _p, _i, _i, _i, _p],
+    "eav_video_head_attn_bwd": [_p, _p, _p, _i, _i, _i, _p],
+    "eav_video_head_feat_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "eav_video_counters_inc": [_p, _i, _p],
 }
 # helpers that return a plain value (no status)
 PLAIN = {
@@ -176,6 +190,8 @@ PLAIN = {
     "eav_attn_sp_npad": ([_i], _i),
     "eav_gemm_sp_splitk_plan": ([_i, _i, _i], _i),
     "eav_audio_wgrad_nparts": ([_i, _i, _i, _i], _i),
+    "eav_video_wgrad_nparts": ([_i, _i, _i, _i64], _i),
+    "eav_video_bn_nparts": ([_i64], _i),
 }
 
 EXPORTS = sorted(list(SIGNATURES) + list(PLAIN))

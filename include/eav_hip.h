@@ -572,6 +572,61 @@ int eav_audio_wgrad_nparts(int B, int Cact, int M, int Lout);
 int eav_audio_conv5_wgrad(const float* dout, const float* gate, float gscale, const float* act, float* part, int B,
                           int Cact, int M, int Lact, int Lout, int nparts, void* stream);
 
+/* ---- video CNN (CNN_torch/CNN_Vision.py VideoModel: torchvision ResNet-50 trunk + channel-attention head;
+ *      csrc/video_cnn.hip) ------------------------------------------------------------------------------------------
+ * Activations are NHWC fp32 (rows [B*H*W][C]); weights keep torchvision's layout w [Cout][Cin][kh][kw] and are re-laid for
+ * the implicit GEMMs by eav_video_conv_relayout: wf [Cout][kh][kw][Cin] (forward), wd [Cin][kh][kw][Cout] (data gradient).
+ * A conv geometry is (B, C = input channels, H, W, N = output channels, KH, KW, S = stride, P = pad, OH, OW), with
+ * OH = (H + 2P - KH) / S + 1 (floor) and OW likewise; channels <= 4096, kernel <= 15, stride <= 4, P < kernel.
+ * nchw = 1 reads the input image as [B][C][H][W] (the pre-processed frames of the stem conv).  Operands need 16-byte
+ * alignment only where they are read as float4: an NHWC image with C % 8 == 0, an output gradient with N % 8 == 0, a
+ * re-laid weight whose rows are a multiple of 8 floats. */
+int eav_video_conv_relayout(const float* w, float* wf, float* wd, int Co, int Ci, int KK, void* stream);
+/* out [B*OH*OW][N] = sum_{kh,kw,c} in[b][oh*S-P+kh][ow*S-P+kw][c] w[n][c][kh][kw] (zero outside the image). */
+int eav_video_conv_fwd(const float* x, const float* wf, float* out, int B, int C, int H, int W, int N, int KH, int KW,
+                       int S, int P, int OH, int OW, int nchw, void* stream);
+/* din [B*H*W][C] = (add, may be NULL) + sum over (kh, kw, n) with (ih + P - kh) and (iw + P - kw) non-negative multiples
+ * of S inside the output map of dout[b][oh][ow][n] w[n][c][kh][kw]. */
+int eav_video_conv_dgrad(const float* dout, const float* wd, const float* add, float* din, int B, int C, int H, int W,
+                         int N, int KH, int KW, int S, int P, int OH, int OW, void* stream);
+/* Weight-gradient partials part[p][n][c][kh][kw] = sum over the 32-pixel chunks q = p, p + nparts, ... of the B*OH*OW
+ * output pixels of dout[pixel][n] in[window][c]; eav_reduce_partials sums them in fixed order.  nparts must be
+ * eav_video_wgrad_nparts(N, C, KH*KW, B*OH*OW). */
+int eav_video_wgrad_nparts(int N, int C, int KK, int64_t M);
+int eav_video_conv_wgrad(const float* dout, const float* x, float* part, int B, int C, int H, int W, int N, int KH, int KW,
+                         int S, int P, int OH, int OW, int nchw, int nparts, void* stream);
+/* BatchNorm over rows [M][C] (C <= 4096): part [eav_video_bn_nparts(M)][2C] = per-channel sum x, sum x^2 of 256-row
+ * chunks (input of eav_bn_finalize), two rows per chunk: the fp32 rounding of the chunk's fp64 sum and its remainder. */
+int eav_video_bn_nparts(int64_t M);
+int eav_video_bn_stats(const float* x, float* part, int64_t M, int C, void* stream);
+/* out = ReLU?(x * scale[c] + shift[c] + r), r = res * rscale[c] + rshift[c] (rscale / rshift set), res (only res set) or
+ * 0 (res NULL).  out may alias x or res. */
+int eav_video_bn_apply(const float* x, const float* scale, const float* shift, const float* res, const float* rscale,
+                       const float* rshift, float* out, int64_t M, int C, int relu, void* stream);
+/* Backward sums: g = dy, zero where y <= 0 when y (the stored ReLU output) is set; g is written to `g` when set (needed
+ * with y); part [eav_video_bn_nparts(M)][2C] = sum g, sum g * (x - mean) * invstd for eav_bn_bwd_finalize; bn = mean,
+ * invstd, ... as eav_bn_finalize writes them.  The input gradient is eav_bn_rows_bwd on the same rows. */
+int eav_video_bn_bwd(const float* dy, const float* y, const float* x, const float* bn, float* g, float* part, int64_t M,
+                     int C, void* stream);
+/* nn.MaxPool2d(K, S, P) on NHWC: idx = kh * K + kw of the window maximum (scan order, first index on ties, a NaN
+ * propagates - torch's CPU max_pool2d); the backward gathers dx from the windows whose argmax is the position. */
+int eav_video_maxpool_fwd(const float* x, float* out, uint8_t* idx, int B, int H, int W, int C, int OH, int OW, int K,
+                          int S, int P, void* stream);
+int eav_video_maxpool_bwd(const float* dout, const uint8_t* idx, float* dx, int B, int H, int W, int C, int OH, int OW,
+                          int K, int S, int P, void* stream);
+/* Channel-attention head on the trunk output y [B][HW][C] (HW <= 256):
+ * head_pool: pooled [2B][C] = AdaptiveAvgPool (rows 0..B-1) and AdaptiveMaxPool (rows B..2B-1, argmax idx [B][C]);
+ * head_scale_pool: attn = A[b] + A[B+b] (the fc2 outputs of both rows), z [B][C] = mean_hw(y * attn);
+ * head_attn_bwd: dA [2B][C] = d attn = sum_hw (dz / HW) y, in both halves;
+ * head_feat_bwd: dy = (dz / HW) attn + dP[b] / HW + (hw == argmax ? dP[B+b] : 0), dP = d pooled. */
+int eav_video_head_pool(const float* y, float* pooled, uint8_t* idx, int B, int HW, int C, void* stream);
+int eav_video_head_scale_pool(const float* y, const float* A, float* attn, float* z, int B, int HW, int C, void* stream);
+int eav_video_head_attn_bwd(const float* y, const float* dz, float* dA, int B, int HW, int C, void* stream);
+int eav_video_head_feat_bwd(const float* dz, const float* attn, const float* dP, const uint8_t* idx, float* dy, int B,
+                            int HW, int C, void* stream);
+/* c[i] += 1 for i < n (the BatchNorm num_batches_tracked counters, one device array) */
+int eav_video_counters_inc(int64_t* c, int n, void* stream);
+
 /* ---- measured peaks (bench.py): register-only fp32 MFMA loop (FLOP = blocks*4 waves*iters*4*4096) and a float4
  *      streaming copy, to quote roofline fractions against what this chip sustains. */
 int eav_peak_mfma_f32(float* sink, int blocks, int iters, void* stream);
