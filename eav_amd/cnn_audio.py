@@ -20,8 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .eegnet import DeviceLoader, GraphStep, cached_workspace
-from .optim import CrossEntropyLoss, FusedAdam, flatten_parameters
+from .optim import CrossEntropyLoss, FusedAdam
+from .runtime import DeviceLoader, GraphStep, KernelFn, KernelModule, eager_step
 
 _PARAM_ORDER = ["features.0.weight", "features.0.bias", "features.2.weight", "features.2.bias", "features.6.weight",
                 "features.6.bias", "features.8.weight", "features.8.bias", "classifier.weight", "classifier.bias"]
@@ -53,20 +53,9 @@ class _Workspace:
         self.part = f(max(self.np[k] * size[k] for k in size))
 
 
-class _AudioFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        ctx.model = model
-        ctx.token = model._launch_forward(x)
-        return model._ws.logits.clone()
+class AudioModel(KernelModule):
+    _PARAM_ORDER = _PARAM_ORDER
 
-    @staticmethod
-    def backward(ctx, dlogits):
-        grads = ctx.model._launch_backward(dlogits.contiguous(), ctx.token)
-        return (None, None, *grads)
-
-
-class AudioModel(nn.Module):
     def __init__(self, num_classes: int = 5):
         super().__init__()
         if not 1 <= num_classes <= NCMAX:
@@ -91,31 +80,10 @@ class AudioModel(nn.Module):
         )
         self.classifier = nn.Linear(128 * 22, num_classes)
         self.num_classes = num_classes
-        self._ws = None
-        self._flat = None
-        self._token = 0
-        self._saved = None
+        # (set_dropout_masks, tests: uint8 keep-masks [B,128,T] after conv2, [B,128,22] after conv4)
         self.dropout_seed = 0xA0D10C
-        self._dropout_masks = None
-        self._fwd_counter = None
 
     # ------------------------------------------------------------------ plumbing
-    def _ensure_flat(self):
-        p0 = self.features[0].weight
-        if self._flat is None or self._flat[0].device != p0.device or getattr(p0, "_eav_flat", None) is None \
-                or p0.data_ptr() != self._flat[0].data_ptr():
-            assert list(dict(self.named_parameters())) == _PARAM_ORDER
-            self._flat = flatten_parameters(self)
-
-    def _params(self):
-        n = dict(self.named_parameters())
-        return [n[k] for k in _PARAM_ORDER]
-
-    def set_dropout_masks(self, masks):
-        """Testing hook: explicit uint8 keep-masks ([B,128,T] after conv2, [B,128,22] after conv4) instead of the
-        counter-based generator; None restores the generator."""
-        self._dropout_masks = masks
-
     def forward(self, x):
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or (x.shape[1] != 1 and x.shape[2] != 1):
             raise ValueError(f"expected input [B,1,T] (or the permuted loader view [B,T,1]), got "
@@ -124,13 +92,10 @@ class AudioModel(nn.Module):
         if not T_MIN <= T <= T_MAX:
             raise NotImplementedError(f"eav_amd.AudioModel: T = {T}; the classifier's fixed 128*22 inputs need "
                                       f"{T_MIN} <= T <= {T_MAX} (floor(T/8) = 22), as in the reference")
-        if not x.is_cuda:
-            raise _lib.EavError("eav_amd.AudioModel runs on an MI355X only: move the model and the input to the ROCm "
-                                "device (there is no CPU fallback)")
-        if self.features[0].weight.device != x.device:
-            raise _lib.EavError("model and input are on different devices")
+        self._require_gpu(x)
+        self._require_same_device(x)
         self._ensure_flat()
-        return _AudioFn.apply(x.reshape(B, T).float().contiguous(), self, *self._params())
+        return KernelFn.apply(x.reshape(B, T).float().contiguous(), self, *self._params())
 
     def _drop(self):
         return (float(self.features[4].p), float(self.features[10].p)) if self.training else (0.0, 0.0)
@@ -142,10 +107,7 @@ class AudioModel(nn.Module):
         # one workspace per batch size, never freed while a captured hipGraph holds its raw pointers (cached_workspace);
         # three replaceable slots: train_model meets a full batch, a ragged last training batch and a ragged validation
         # batch in every epoch
-        if not hasattr(self, "_wss"):
-            self._wss = {}
-        ws = self._ws = cached_workspace(self._wss, (B, T, str(x.device)), lambda: _Workspace(self, B, T, x.device),
-                                         keep_unpinned=3)
+        ws = self._workspace((B, T, str(x.device)), lambda: _Workspace(self, B, T, x.device), keep_unpinned=3)
         w1, b1, w2, b2, w3, b3, w4, b4, wc, bc = [P(p) for p in self._params()]
         d1, d2 = self._drop()
         masks = self._dropout_masks if self.training else None
@@ -160,10 +122,8 @@ class AudioModel(nn.Module):
         seed1, seed2 = self.dropout_seed, self.dropout_seed + 1
         cnt = None
         if (d1 > 0.0 or d2 > 0.0) and masks is None:   # device-resident dropout counter: graph replays draw fresh masks
-            if self._fwd_counter is None or self._fwd_counter.device != x.device:
-                self._fwd_counter = torch.zeros((), dtype=torch.int64, device=x.device)
-            L("eav_counter_inc", P(self._fwd_counter), st)
-            cnt = P(self._fwd_counter)
+            cnt = P(self._counter(x.device))
+            L("eav_counter_inc", cnt, st)
         m1 = P(masks[0]) if masks is not None else None
         m2 = P(masks[1]) if masks is not None else None
         L("eav_audio_conv5_fwd", P(x), w1, b1, P(ws.a1), None, B, 1, 256, T, T, 0, 0.0, 0, None, None, st)
@@ -178,9 +138,7 @@ class AudioModel(nn.Module):
         return self._token
 
     def _launch_backward(self, dlogits, token):
-        if self._saved is None or self._saved[0] != token:
-            raise _lib.EavError("AudioModel.backward: the activations of this forward were overwritten by a later "
-                                "forward (one outstanding forward per backward)")
+        self._check_token(token)
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
         _, x, d1, d2, masks, ws = self._saved
         B, T = x.shape
@@ -294,15 +252,7 @@ def train_model(model, train_loader, val_loader, epochs=100, lr=1e-3, save_dir="
                 y = train_loader.gather_labels(idx)
             else:
                 x, y = train_loader.gather(idx)
-                x = x.permute(0, 2, 1)
-                optimizer.zero_grad()
-                out = model(x)
-                loss = criterion(out, y)
-                loss.backward()
-                optimizer.step()
-                # drop the eager step's autograd graph now: its AccumulateGrad nodes, kept alive into the next
-                # GraphStep capture, would tie that capture to this stream
-                out, loss = out.detach(), loss.detach()
+                out, loss = eager_step(model, optimizer, criterion, x.permute(0, 2, 1), y, grad_sync)
             losses[k].copy_(loss)
             correct += (out.argmax(dim=1) == y).sum()
             total += len(idx)

@@ -18,8 +18,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .eegnet import DeviceLoader, GraphStep, cached_workspace
-from .optim import CrossEntropyLoss, FusedAdam, flatten_parameters
+from .optim import CrossEntropyLoss, FusedAdam
+from .runtime import DeviceLoader, GraphStep, KernelFn, KernelModule, eager_step
 
 _PARAM_ORDER = [
     "block1.0.weight", "block1.1.weight", "block1.1.bias", "block1.2.weight", "block1.3.weight", "block1.3.bias",
@@ -60,20 +60,8 @@ class _Workspace:
         self.part_dw = f(B, C2 * K2)
 
 
-class _EEGNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        ctx.model = model
-        ctx.token = model._launch_forward(x)
-        return model._ws.logits.clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        grads = ctx.model._launch_backward(dlogits.contiguous(), ctx.token)
-        return (None, None, *grads)
-
-
-class EEGNet(nn.Module):
+class EEGNet(KernelModule):
+    _PARAM_ORDER = _PARAM_ORDER
     K2 = 16   # taps of the depthwise temporal conv of block2 (CNN_EEG.py:35)
 
     def __init__(self, nb_classes, Chans=64, Samples=128, dropoutRate=0.5, kernLength=64, F1=8, D=2, F2=16,
@@ -112,53 +100,26 @@ class EEGNet(nn.Module):
 
         self.nb_classes, self.kernLength, self.F1, self.D, self.F2 = nb_classes, kernLength, F1, D, F2
         self.dropoutRate, self.norm_rate = float(dropoutRate), norm_rate      # norm_rate: accepted, unused (:13)
-        self._ws = None
-        self._flat = None
-        self._token = 0
-        self._saved = None
-        self.dropout_seed = 0x0CA2EED
-        self._dropout_masks = None
-        self._fwd_counter = None
+        self.dropout_seed = 0x0CA2EED          # (set_dropout_masks, tests: uint8 keep-masks [B,C2,S/4], [B,F2,S/32])
 
     # ------------------------------------------------------------------ plumbing
-    def _ensure_flat(self):
-        p0 = self.block1[0].weight
-        if self._flat is None or self._flat[0].device != p0.device or getattr(p0, "_eav_flat", None) is None \
-                or p0.data_ptr() != self._flat[0].data_ptr():
-            assert list(dict(self.named_parameters())) == _PARAM_ORDER
-            self._flat = flatten_parameters(self)
-
-    def _params(self):
-        n = dict(self.named_parameters())
-        return [n[k] for k in _PARAM_ORDER]
-
-    def set_dropout_masks(self, masks):
-        """Testing hook: explicit uint8 keep-masks ([B,C2,S/4], [B,F2,S/32]) instead of the generator."""
-        self._dropout_masks = masks
-
     def forward(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise _lib.EavError("eav_amd.EEGNet runs on an MI355X only: move the model and the input to the ROCm "
-                                "device (there is no CPU fallback)")
+        self._require_gpu(x)
         if x.dim() == 3:
             x = x.unsqueeze(1)                                                           # :61-62
         if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != self.Chans or x.shape[3] != self.Samples:
             raise ValueError(f"expected input [B,{self.Chans},{self.Samples}], got {tuple(x.shape)}")
-        if self.block1[0].weight.device != x.device:
-            raise _lib.EavError("model and input are on different devices")
+        self._require_same_device(x)
         self._ensure_flat()
-        return _EEGNetFn.apply(x.contiguous().float(), self, *self._params())
+        return KernelFn.apply(x.contiguous().float(), self, *self._params())
 
     # ------------------------------------------------------------------ kernels
     def _launch_forward(self, x):
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
         B, C, S, K, K2 = x.shape[0], self.Chans, self.Samples, self.kernLength, self.K2
         F1, D, F2, C2 = self.F1, self.D, self.F2, self.F1 * self.D
-        # one workspace per batch size, never freed: captured hipGraphs hold its raw pointers (see EEGNet_tor._workspace)
-        wkey = (B, C, S, str(x.device))
-        if not hasattr(self, "_wss"):
-            self._wss = {}
-        ws = self._ws = cached_workspace(self._wss, wkey, lambda: _Workspace(self, B, x.device))
+        # one workspace per batch size, never freed while a captured hipGraph holds its raw pointers (cached_workspace)
+        ws = self._workspace((B, C, S, str(x.device)), lambda: _Workspace(self, B, x.device))
         training = bool(self.training)
         w1, g1w, g1b, wd, g2w, g2b, wdw, wp, g3w, g3b, wc, bc = [P(p) for p in self._params()]
         drop = self.dropoutRate if training else 0.0
@@ -167,10 +128,8 @@ class EEGNet(nn.Module):
         seed1, seed2 = self.dropout_seed, self.dropout_seed + 1
         cnt = None
         if drop > 0.0 and masks is None:    # device-resident dropout counter: graph replays draw fresh masks
-            if self._fwd_counter is None or self._fwd_counter.device != x.device:
-                self._fwd_counter = torch.zeros((), dtype=torch.int64, device=x.device)
-            L("eav_counter_inc", P(self._fwd_counter), st)
-            cnt = P(self._fwd_counter)
+            cnt = P(self._counter(x.device))
+            L("eav_counter_inc", cnt, st)
         m1 = P(masks[0]) if masks is not None else None
         m2 = P(masks[1]) if masks is not None else None
 
@@ -194,9 +153,7 @@ class EEGNet(nn.Module):
         return self._token
 
     def _launch_backward(self, dlogits, token):
-        if self._saved is None or self._saved[0] != token:
-            raise _lib.EavError("EEGNet.backward: the activations of this forward were overwritten by a later forward "
-                                "(one outstanding forward per backward)")
+        self._check_token(token)
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
         _, x, training, drop, seed1, seed2, masks, cnt, ws = self._saved
         B, C, S, K, K2 = x.shape[0], self.Chans, self.Samples, self.kernLength, self.K2
@@ -244,7 +201,7 @@ class EEGNet(nn.Module):
 
 class EEGNetTrainer:
     """CNN_EEG.py:70-162.  The datasets are ``TensorDataset(x, y)``; both splits are moved to HBM once and batches
-    are assembled there (eav_amd.eegnet.DeviceLoader: same samplers and torch RNG consumption as DataLoader)."""
+    are assembled there (eav_amd.runtime.DeviceLoader: same samplers and torch RNG consumption as DataLoader)."""
 
     def __init__(self, model, train_dataset, val_dataset, batch_size=32, epochs=100, lr=0.001):
         if not torch.cuda.is_available():
@@ -274,15 +231,7 @@ class EEGNetTrainer:
                                             self.grad_sync)
                 _, loss = self._graph.run(idx)
             else:
-                inputs, labels = dl.gather(idx)
-                self.optimizer.zero_grad()
-                outputs = self.model(inputs)
-                loss = self.criterion(outputs, labels)
-                loss.backward()
-                if self.grad_sync is not None:
-                    self.grad_sync()
-                self.optimizer.step()
-                loss = loss.detach()
+                _, loss = eager_step(self.model, self.optimizer, self.criterion, *dl.gather(idx), self.grad_sync)
             running_loss += loss          # accumulated on the device: one host read per epoch, not per step (:106)
         self.criterion.check()            # labels outside [0, classes) seen by any step of this epoch raise here
         return running_loss.item() / len(batches)

@@ -22,8 +22,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .eegnet import DeviceLoader, cached_workspace
-from .optim import CrossEntropyLoss, FusedAdam, flatten_parameters
+from .optim import CrossEntropyLoss, FusedAdam
+from .runtime import DeviceLoader, KernelFn, KernelModule, eager_step
 
 NCMAX = 16                  # classes the head kernels take (eav_dense_softmax_*)
 FEAT = 2048
@@ -162,20 +162,7 @@ class _Workspace:
         self.dA, self.dH1, self.dP = f(B2 * FEAT), f(B2 * FEAT), f(B2 * FEAT)
 
 
-class _VideoFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        ctx.model = model
-        ctx.token = model._launch_forward(x)
-        return model._ws.logits.clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        grads = ctx.model._launch_backward(dlogits.contiguous(), ctx.token)
-        return (None, None, *grads)
-
-
-class VideoModel(nn.Module):
+class VideoModel(KernelModule):
     def __init__(self, num_labels: int = 5, ratio: int = 1, backbone_weights=None):
         super().__init__()
         if ratio != 1:
@@ -207,10 +194,7 @@ class VideoModel(nn.Module):
             nn.ReLU(),
             nn.Linear(1024, num_labels),
         )
-        self._flat = None
         self._nbt = None
-        self._token = 0
-        self._saved = None
 
     def load_backbone(self, weights):
         """A torchvision-format ResNet-50 state_dict (``conv1.weight``, ``bn1.*``, ``layer1.0...``; ``fc.*`` ignored) or a
@@ -247,10 +231,8 @@ class VideoModel(nn.Module):
                                  "track_running_stats=False is not supported (torchvision's ResNet-50 uses none of them)")
 
     def _ensure_flat(self):
+        super()._ensure_flat()
         p0 = next(self.parameters())
-        if self._flat is None or getattr(p0, "_eav_flat", None) is None or p0.data_ptr() != self._flat[0].data_ptr() \
-                or self._flat[0].device != p0.device:
-            self._flat = flatten_parameters(self)
         # every num_batches_tracked as a view of one device array: one launch counts them all
         bns = self._bns()
         if self._nbt is None or self._nbt.device != p0.device or any(
@@ -269,19 +251,14 @@ class VideoModel(nn.Module):
             raise ValueError(f"expected images [B,3,H,W], got "
                              f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
         self._check_bns()
-        if not x.is_cuda:
-            raise _lib.EavError("eav_amd.VideoModel runs on an MI355X only: move the model and the input to the ROCm "
-                                "device (there is no CPU fallback)")
-        p0 = next(self.parameters())
-        if p0.device != x.device:
-            raise _lib.EavError("model and input are on different devices")
+        self._require_gpu(x)
+        self._require_same_device(x)
         H, W = x.shape[2], x.shape[3]
         _, _, _, (FH, FW) = _plan(self, H, W)
         if FH < 1 or FW < 1 or FH * FW > 256:
             raise ValueError(f"VideoModel: a {H}x{W} image gives a {FH}x{FW} trunk output (1..256 positions supported)")
         self._ensure_flat()
-        params = list(self.parameters())
-        return _VideoFn.apply(x.float().contiguous(), self, *params)
+        return KernelFn.apply(x.float().contiguous(), self, *self.parameters())
 
     # ------------------------------------------------------------------ kernels
     def _conv_fwd(self, u, src, dst, nchw=0):
@@ -319,10 +296,7 @@ class VideoModel(nn.Module):
     def _launch_forward(self, x):
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
         B, _, H, W = x.shape
-        if not hasattr(self, "_wss"):
-            self._wss = {}
-        ws = self._ws = cached_workspace(self._wss, (B, H, W, str(x.device)), lambda: _Workspace(self, B, H, W, x.device),
-                                         keep_unpinned=3)
+        ws = self._workspace((B, H, W, str(x.device)), lambda: _Workspace(self, B, H, W, x.device), keep_unpinned=3)
         tr = self.training
         if tr:
             L("eav_video_counters_inc", P(self._nbt), self._nbt.numel(), st)
@@ -410,9 +384,7 @@ class VideoModel(nn.Module):
               u.OH, u.OW, st)
 
     def _launch_backward(self, dlogits, token):
-        if self._saved is None or self._saved[0] != token:
-            raise _lib.EavError("VideoModel.backward: the activations of this forward were overwritten by a later "
-                                "forward (one outstanding forward per backward)")
+        self._check_token(token)
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
         _, x, tr, ws = self._saved
         B, B2, HW = ws.B, 2 * ws.B, ws.HW
@@ -525,12 +497,8 @@ class ImageClassifierTrainer:
             accs = []
 
             for x, y in self.train_loader:
-                self.optimizer.zero_grad()
-                out = self.model(x)
-                loss = self.criterion(out, y)
-                loss.backward()
-                self.optimizer.step()
-                accs.append(self.accuracy(out.detach(), y))
+                out, _ = eager_step(self.model, self.optimizer, self.criterion, x, y)
+                accs.append(self.accuracy(out, y))
 
             self.criterion.check()
             train_acc = 0.0

@@ -25,7 +25,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .optim import CrossEntropyLoss, FusedAdam, flatten_parameters, unit_gradient
+from .optim import CrossEntropyLoss, FusedAdam
+# re-exported: bench.py, tools/ and the tests import GraphStep, gather_batch and DeviceLoader from this module
+from .runtime import (DeviceLoader, GraphStep, KernelFn, KernelModule, cached_workspace, eager_step,  # noqa: F401
+                      gather_batch)
 
 _PARAM_ORDER = [
     "firstConv.weight", "firstBN.weight", "firstBN.bias",
@@ -98,24 +101,6 @@ class _GenericWorkspace:
         self.part_cw = f(B, F2 * C2 * 16)
 
 
-def cached_workspace(cache, key, make, keep_unpinned=2):
-    """Workspace cache shared by the EEG models.  A captured hipGraph (GraphStep) has the raw device pointers of the
-    workspace it was captured with baked in, so THOSE workspaces (marked `pinned` by GraphStep after capture) live as long
-    as the model; eager sizes - ragged last batches, validation, user-chosen inference batches - share `keep_unpinned`
-    replaceable slots (most recently used first), so varying batch sizes do not accumulate multi-GB workspaces."""
-    ws = cache.get(key)
-    if ws is None:
-        if not torch.cuda.is_current_stream_capturing():
-            loose = [k for k, w in cache.items() if not getattr(w, "pinned", False)]
-            for k in loose[:max(0, len(loose) - (keep_unpinned - 1))]:     # dict order = insertion / last-use order
-                del cache[k]
-        ws = make()
-    else:
-        del cache[key]          # re-insert: most recently used last
-    cache[key] = ws
-    return ws
-
-
 class IndexedBatch:
     """A batch addressed in place: samples `idx` (device int64 [B]) of an HBM-resident data set `data` [N,1,C,S].  The FIR
     kernels - the only readers of the network input - take the index vector, so no gathered copy of the batch is made."""
@@ -126,17 +111,17 @@ class IndexedBatch:
         self.device = data.device
 
 
-class _EEGNetFn(torch.autograd.Function):
+class _EEGNetFn(KernelFn):
     @staticmethod
     def forward(ctx, x, model, *params):
-        ctx.model = model
-        ctx.token = model._launch_forward(x)
-        # the probabilities tensor this forward wrote: no copy kernel.  (A detached alias, not the saved object itself:
-        # returning the very tensor that the model also keeps for its backward crashes hipGraph capture in torch 2.10.)
-        # The alias shares its version counter with the saved tensor: an in-place edit of the returned scores before
-        # backward (clamp_, += eps ...) would silently corrupt dense_softmax_bwd's input - checked in backward.
+        # EEGNet_tor._forward_output: the probabilities tensor this forward wrote, no copy kernel.  (A detached alias, not
+        # the saved object itself: returning the very tensor that the model also keeps for its backward crashes hipGraph
+        # capture in torch 2.10.)  The alias shares its version counter with the saved tensor: an in-place edit of the
+        # returned scores before backward (clamp_, += eps ...) would silently corrupt dense_softmax_bwd's input - checked
+        # in backward.
+        out = KernelFn.forward(ctx, x, model, *params)
         ctx.probs_version = model._saved[-1]._version
-        return model._saved[-1].detach()
+        return out
 
     @staticmethod
     def backward(ctx, dprobs):
@@ -144,11 +129,12 @@ class _EEGNetFn(torch.autograd.Function):
         if saved is not None and saved[0] == ctx.token and saved[-1]._version != ctx.probs_version:
             raise _lib.EavError("EEGNet_tor: the scores returned by forward() were modified in place before backward(); "
                                 "they alias the probabilities the backward reads - clone() them first")
-        grads = ctx.model._launch_backward(dprobs.contiguous(), ctx.token)
-        return (None, None, *grads)
+        return KernelFn.backward(ctx, dprobs)
 
 
-class EEGNet_tor(nn.Module):
+class EEGNet_tor(KernelModule):
+    _PARAM_ORDER = _PARAM_ORDER
+
     def __init__(self, nb_classes, Chans=30, Samples=500, dropoutRate=0.5, kernLength=300, F1=8, D=8, F2=64,
                  norm_rate=1.0, dropoutType='Dropout'):
         super().__init__()
@@ -182,13 +168,8 @@ class EEGNet_tor(nn.Module):
         # any other dropoutType is nn.Dropout2d in the reference (:21): one keep decision per (sample, channel) map - the
         # kernels take it as a negative probability (eav_hip.h)
         self.spatial_dropout = dropoutType != 'Dropout'
-        self._ws = None
-        self._wss = {}                         # workspaces by (B, Chans, Samples, device): see _workspace()
-        self._flat = None
-        self._token = 0
-        self._saved = None
         self.dropout_seed = 0x0EA5EED          # base seed of the counter-based dropout generator
-        self._dropout_masks = None             # tests: (mask1 uint8 [B,64,S/4], mask2 uint8 [B,64,S/32])
+        # (set_dropout_masks, tests: (mask1 uint8 [B,64,S/4], mask2 uint8 [B,64,S/32]))
         self.apply_max_norm = True
         self.kernel_events = None              # bench: {kernel name: [(start_event, end_event), ...]}
         # (the round-2 "split" mode - FIR / separableConv products on the fp16 matrix cores with two-piece operands - was
@@ -201,9 +182,8 @@ class EEGNet_tor(nn.Module):
         # (the reference's own [B,1,30,500], where one FFT block would be mostly padding).  EAV_FIR_ALGO overrides.
         self.fir_algo = os.environ.get("EAV_FIR_ALGO", "auto")
         self.conv_algo = os.environ.get("EAV_CONV_ALGO", "auto")      # separableConv: see _use_conv_fft
-        self._fwd_counter = None               # device uint64: number of training forwards (dropout stream)
         self._infer = False                    # set per call: no-grad eval-mode forward
-        # GraphStep: (optimiser step counter, labels, idx, targets, batch) - raw pointers for eav_step_begin, taken by the next
+        # forward_batch: (optimiser step counter, labels, idx, targets, batch) - raw pointers for eav_step_begin, taken by the next
         # forward's counter launch (left in place if that forward has none to merge them into)
         self._step_begin = None
         # validate()'s forward with block 1 as ONE kernel (eav_eegnet_block1_infer: y1 / z never written).  Opt-in: at the
@@ -230,32 +210,13 @@ class EEGNet_tor(nn.Module):
             return False
         return self.conv_algo == "fft" or B * (self.Samples // 4) >= 40000
 
-    def _ensure_flat(self):
-        p0 = self.firstConv.weight
-        if self._flat is None or self._flat[0].device != p0.device or getattr(p0, "_eav_flat", None) is None \
-                or p0.data_ptr() != self._flat[0].data_ptr():
-            ordered = dict(self.named_parameters())
-            assert list(ordered) == _PARAM_ORDER, list(ordered)
-            self._flat = flatten_parameters(self)
-
-    def _params(self):
-        n = dict(self.named_parameters())
-        return [n[k] for k in _PARAM_ORDER]
-
-    def set_dropout_masks(self, masks):
-        """Testing hook: explicit uint8 keep-masks instead of the counter-based generator."""
-        self._dropout_masks = masks
-
     def forward(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise _lib.EavError("eav_amd.EEGNet_tor runs on an MI355X only: move the model and the input to the "
-                                "ROCm device (there is no CPU fallback)")
+        self._require_gpu(x)
         if x.dim() == 3:
             x = x.unsqueeze(1)
         if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != self.Chans or x.shape[3] != self.Samples:
             raise ValueError(f"expected input [B,1,{self.Chans},{self.Samples}], got {tuple(x.shape)}")
-        if self.firstConv.weight.device != x.device:
-            raise _lib.EavError("model and input are on different devices")
+        self._require_same_device(x)
         x = x.contiguous().float()
         self._ensure_flat()
         # no-grad evaluation (validate(), EEGNet_tor.py:118-135): block 1 runs as one fused kernel, see _launch_forward
@@ -275,8 +236,7 @@ class EEGNet_tor(nn.Module):
             _lib.call("eav_gather_rows", data.data_ptr(), idx.data_ptr(), out.data_ptr(), idx.numel(), data[0].numel(),
                       _lib.stream_ptr())
             return self.forward(out)
-        if self.firstConv.weight.device != data.device:
-            raise _lib.EavError("model and input are on different devices")
+        self._require_same_device(data)
         self._ensure_flat()
         self._infer = (not torch.is_grad_enabled()) and (not self.training)
         return _EEGNetFn.apply(IndexedBatch(data, idx), self, *self._params())
@@ -295,19 +255,37 @@ class EEGNet_tor(nn.Module):
         else:
             _lib.call(name, *args)
 
-    def _workspace(self, B, dev):
-        """One workspace per problem size; the ones a hipGraph was captured with are pinned for the life of the model,
-        the others share a small replaceable set (cached_workspace)."""
-        key = (B, self.Chans, self.Samples, str(dev))
-        return cached_workspace(self._wss, key, lambda: _Workspace(B, self.Chans, self.Samples, self.kernLength,
-                                                                   self.nb_classes, dev))
+    def _forward_output(self):
+        return self._saved[-1].detach()          # see _EEGNetFn
+
+    def forward_batch(self, xs, ys, idx, optimizer):
+        """GraphStep's batch: read in place through the index vector (forward_indexed); only the labels are gathered - by
+        the model's own step-counter launch where it has one (eav_step_begin: the label gather, the optimiser's step
+        count and the dropout / BatchNorm counters in ONE graph node instead of three)."""
+        if not (xs.is_cuda and xs.dim() == 4 and xs.is_contiguous()):
+            return super().forward_batch(xs, ys, idx, optimizer)
+        batch = idx.numel()
+        targets = torch.empty(batch, dtype=torch.long, device=xs.device)
+        optimizer.step_counted = False       # (a step that failed between its two halves must not leave the flag set)
+        if not self._generic:
+            # raw pointers for eav_step_begin, taken by the forward's counter launch (left in place if that forward has
+            # none to merge them into); FusedAdam.step() then skips its own eav_counter_inc for this one step
+            cnt = optimizer.device_step_counter()
+            self._step_begin = (cnt.data_ptr(), ys.data_ptr(), idx.data_ptr(), targets.data_ptr(), batch)
+        scores = self.forward_indexed(xs, idx)
+        merged = not self._generic and self._step_begin is None        # taken: eav_step_begin ran
+        self._step_begin = None
+        optimizer.step_counted = merged
+        if not merged:
+            _lib.call("eav_gather_i64", ys.data_ptr(), idx.data_ptr(), targets.data_ptr(), batch, _lib.stream_ptr())
+        return scores, targets
 
     def _launch_forward(self, x):
         if self._generic:
             return self._launch_forward_generic(x)
         L, P, st = self._call, _lib.ptr, _lib.stream_ptr()
         B, C, S, K, nb = x.shape[0], self.Chans, self.Samples, self.kernLength, self.nb_classes
-        ws = self._ws = self._workspace(B, x.device)
+        ws = self._workspace((B, C, S, str(x.device)), lambda: _Workspace(B, C, S, K, nb, x.device))
         training = bool(self.training)
         w1, g1w, g1b, w2, g2w, g2b, w3, g3w, g3b, wd, bd = [P(p) for p in self._params()]
         bn1, bn2, bn3 = self.firstBN, self.depthwiseBN, self.separableBN
@@ -321,9 +299,7 @@ class EEGNet_tor(nn.Module):
         seed1, seed2 = self.dropout_seed, self.dropout_seed + 1
         cnt = None
         if drop != 0.0 and masks is None:
-            if self._fwd_counter is None or self._fwd_counter.device != x.device:
-                self._fwd_counter = torch.zeros((), dtype=torch.int64, device=x.device)
-            cnt = P(self._fwd_counter)
+            cnt = P(self._counter(x.device))
         m1 = P(masks[0]) if masks is not None else None
         m2 = P(masks[1]) if masks is not None else None
 
@@ -411,8 +387,7 @@ class EEGNet_tor(nn.Module):
         B, C, S, K, nb = x.shape[0], self.Chans, self.Samples, self.kernLength, self.nb_classes
         F1, D, F2 = self.F1, self.D, self.F2
         C2 = F1 * D
-        key = ("generic", B, C, S, str(x.device))
-        ws = self._ws = cached_workspace(self._wss, key, lambda: _GenericWorkspace(self, B, x.device))
+        ws = self._workspace(("generic", B, C, S, str(x.device)), lambda: _GenericWorkspace(self, B, x.device))
         training = bool(self.training)
         w1, g1w, g1b, w2, g2w, g2b, w3, g3w, g3b, wd, bd = [P(p) for p in self._params()]
         bn1, bn2, bn3 = self.firstBN, self.depthwiseBN, self.separableBN
@@ -424,9 +399,7 @@ class EEGNet_tor(nn.Module):
         seed1, seed2 = self.dropout_seed, self.dropout_seed + 1
         cnt = None
         if drop != 0.0 and masks is None:
-            if self._fwd_counter is None or self._fwd_counter.device != x.device:
-                self._fwd_counter = torch.zeros((), dtype=torch.int64, device=x.device)
-            cnt = P(self._fwd_counter)
+            cnt = P(self._counter(x.device))
         if cnt is not None or training:
             L("eav_counter_inc4", cnt, *([P(bn.num_batches_tracked) for bn in (bn1, bn2, bn3)] if training else [None] * 3),
               st)
@@ -497,9 +470,7 @@ class EEGNet_tor(nn.Module):
         return [g[k].view(named[k].shape) if named[k].requires_grad else None for k in _PARAM_ORDER]
 
     def _launch_backward(self, dprobs, token):
-        if self._saved is None or self._saved[0] != token:
-            raise _lib.EavError("EEGNet_tor.backward: the activations of this forward were overwritten by a later "
-                                "forward (one outstanding forward per backward)")
+        self._check_token(token)
         if self._generic:
             return self._launch_backward_generic(dprobs)
         L, P, st = self._call, _lib.ptr, _lib.stream_ptr()
@@ -587,166 +558,6 @@ class EEGNet_tor(nn.Module):
         return [g[k].view(named[k].shape) if named[k].requires_grad else None for k in _PARAM_ORDER]
 
 
-def gather_batch(xs, ys, idx_dev):
-    """(xs[idx], ys[idx]) assembled in HBM by the library's gather kernels (eav_gather_rows / eav_gather_i64)."""
-    n = idx_dev.numel()
-    if not xs.is_cuda:   # host tensors (CPU-side unit tests of the loader only)
-        return xs.index_select(0, idx_dev), ys.index_select(0, idx_dev)
-    data = torch.empty((n,) + tuple(xs.shape[1:]), dtype=torch.float32, device=xs.device)
-    targets = torch.empty(n, dtype=torch.long, device=xs.device)
-    st = _lib.stream_ptr()
-    _lib.call("eav_gather_rows", xs.data_ptr(), idx_dev.data_ptr(), data.data_ptr(), n, xs[0].numel(), st)
-    _lib.call("eav_gather_i64", ys.data_ptr(), idx_dev.data_ptr(), targets.data_ptr(), n, st)
-    return data, targets
-
-
-class GraphStep:
-    """One EEGNet training step (batch gather, forward, CE, backward, [grad sync], fused Adam) captured in a
-    hipGraph and replayed: at the reference's own shape ([32,1,30,500]) the step is ~35 tiny kernels and is
-    bound by launch overhead, not by the GPU.  Everything that varies between steps lives in device memory
-    (batch indices, dropout counter, Adam step count), so a replay needs no host-side argument updates."""
-
-    def __init__(self, model, optimizer, criterion, xs, ys, batch, grad_sync=None, post_step=None):
-        if not getattr(optimizer, "capturable", False):
-            raise _lib.EavError("GraphStep needs FusedAdam(capturable=True)")
-        self.model, self.batch, self.grad_sync = model, batch, grad_sync
-        dev = xs.device
-        self.idx = torch.zeros(batch, dtype=torch.long, device=dev)
-
-        def compute():       # batch gather + forward + loss + backward
-            if hasattr(model, "forward_indexed") and xs.is_cuda and xs.dim() == 4 and xs.is_contiguous():
-                # EEGNet_tor reads the batch in place through the index vector: only the labels are gathered - by the
-                # model's own step-counter launch where it has one (eav_step_begin: the label gather, the optimiser's step
-                # count and the dropout / BatchNorm counters in ONE graph node instead of three)
-                targets = torch.empty(batch, dtype=torch.long, device=dev)
-                merged = False
-                optimizer.step_counted = False       # (a step that failed between its two halves must not leave the flag set)
-                if hasattr(model, "_step_begin") and not getattr(model, "_generic", False):
-                    cnt = optimizer.device_step_counter()
-                    model._step_begin = (cnt.data_ptr(), ys.data_ptr(), self.idx.data_ptr(), targets.data_ptr(), batch)
-                    scores = model.forward_indexed(xs, self.idx)
-                    merged = model._step_begin is None
-                    model._step_begin = None
-                    if merged:
-                        optimizer.step_counted = True
-                else:
-                    scores = model.forward_indexed(xs, self.idx)
-                if not merged:
-                    _lib.call("eav_gather_i64", ys.data_ptr(), self.idx.data_ptr(), targets.data_ptr(), batch, _lib.stream_ptr())
-            else:
-                data, targets = gather_batch(xs, ys, self.idx)
-                scores = model(data)
-            loss = criterion(scores, targets)
-            optimizer.zero_grad(set_to_none=True)
-            loss.backward(gradient=unit_gradient(loss.device))      # no ones_like fill, no scaling launch
-            return scores, loss
-
-        def update():        # fused Adam (+ e.g. the max-norm projection of Transformer_EEG.py:195-199)
-            optimizer.step()
-            if post_step is not None:
-                post_step()
-
-        self.warm_steps = 0
-        self.graph = None          # compute (and, without a grad_sync, update) graph
-        self.graph_update = None   # data parallel: the update is its own graph, the all-reduce runs between the two
-        self._compute, self._update = compute, update
-
-    def _eager(self):
-        scores, loss = self._compute()
-        if self.grad_sync is not None:
-            self.grad_sync()
-        self._update()
-        return scores, loss
-
-    def run(self, idx):
-        """idx: sequence of `batch` dataset indices.  The first two calls run eagerly (they are real training
-        steps), the third is captured, later ones are replays.  Under data parallelism (grad_sync) the collective is
-        not captured: replay(compute) -> all-reduce on the live stream -> replay(update)."""
-        self.idx.copy_(torch.as_tensor(idx, dtype=torch.long))     # pageable source: staged, no host race
-        if self.graph is None:
-            if self.warm_steps < 2:
-                self.warm_steps += 1
-                scores, loss = self._eager()
-                return scores.detach(), loss.detach()     # keep no reference to the autograd graph
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                scores, loss = self._compute()
-                self.scores, self.loss = scores.detach(), loss.detach()
-                if self.grad_sync is None:
-                    self._update()
-            del scores, loss
-            if getattr(self.model, "_ws", None) is not None:
-                self.model._ws.pinned = True       # the graph holds this workspace's raw pointers (cached_workspace)
-            if self.grad_sync is not None:
-                # the gradients the update graph reads live in the model's flat buffer (static address); capture the
-                # update on its own (its launches are recorded, not executed)
-                self.graph_update = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_update, pool=self.graph.pool()):
-                    self._update()
-            # capture does not execute: fall through to a replay so that this call is a real step too
-        self.graph.replay()
-        if self.grad_sync is not None:
-            self.grad_sync()
-            self.graph_update.replay()
-        return self.scores, self.loss
-
-
-# ----------------------------------------------------------------------------- data plumbing
-class DeviceLoader:
-    """DataLoader-shaped iterator over a device-resident TensorDataset.
-
-    The reference builds ``DataLoader(TensorDataset(x, y), batch_size, shuffle)`` on
-    the host and copies every batch to the device inside the loop
-    (EEGNet_tor.py:91-94,100-101).  Here the whole split lives in HBM once and a
-    batch is assembled by one gather; the *index order* is produced by the same
-    torch samplers (RandomSampler / SequentialSampler + BatchSampler), consuming
-    the torch RNG exactly as ``iter(DataLoader)`` does, so a seeded run visits
-    the same batches as the reference.
-    """
-
-    def __init__(self, x, y, batch_size, shuffle, device):
-        from torch.utils.data import TensorDataset
-        self.x = torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
-        self.y = torch.as_tensor(y, dtype=torch.long).to(device).contiguous()
-        self.dataset = TensorDataset(self.x, self.y)
-        self.batch_size, self.shuffle, self.device = batch_size, shuffle, device
-        self.order_override = None  # tests: list of index arrays, one per epoch
-
-    def __len__(self):
-        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
-
-    def index_batches(self):
-        """The index lists iter(DataLoader) would visit (same samplers, same torch RNG consumption)."""
-        from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
-        n = len(self.dataset)
-        # iter(DataLoader) draws its base seed first (torch/utils/data/dataloader.py, _BaseDataLoaderIter)
-        torch.empty((), dtype=torch.int64).random_()
-        if self.order_override:
-            order = [int(i) for i in self.order_override.pop(0)]
-            return [order[i:i + self.batch_size] for i in range(0, n, self.batch_size)]
-        sampler = RandomSampler(range(n)) if self.shuffle else SequentialSampler(range(n))
-        return list(BatchSampler(sampler, self.batch_size, drop_last=False))
-
-    def gather(self, idx):
-        if idx[-1] - idx[0] == len(idx) - 1 and all(b - a == 1 for a, b in zip(idx, idx[1:])):
-            return self.x[idx[0]:idx[-1] + 1], self.y[idx[0]:idx[-1] + 1]
-        return gather_batch(self.x, self.y, torch.as_tensor(idx, dtype=torch.long, device=self.device))
-
-    def gather_labels(self, idx):
-        """The labels of a batch only (a step that already holds the batch's features needs no copy of x)."""
-        if idx[-1] - idx[0] == len(idx) - 1 and all(b - a == 1 for a, b in zip(idx, idx[1:])):
-            return self.y[idx[0]:idx[-1] + 1]
-        i = torch.as_tensor(idx, dtype=torch.long, device=self.device)
-        out = torch.empty(len(idx), dtype=torch.long, device=self.device)
-        _lib.call("eav_gather_i64", self.y.data_ptr(), i.data_ptr(), out.data_ptr(), len(idx), _lib.stream_ptr())
-        return out
-
-    def __iter__(self):
-        for idx in self.index_batches():
-            yield self.gather(idx)
-
-
 class Trainer_uni:
     def __init__(self, model, data, lr=1e-4, batch_size=32, num_epochs=10, device=None):
         self.lr = lr
@@ -786,14 +597,7 @@ class Trainer_uni:
                                                       len(idx), self.grad_sync)
                     scores, loss = self._graphs[key].run(idx)
                 else:
-                    data, targets = dl.gather(idx)
-                    scores = self.model(data)
-                    loss = self.criterion(scores, targets)
-                    self.optimizer.zero_grad()
-                    loss.backward()
-                    if self.grad_sync is not None:
-                        self.grad_sync()
-                    self.optimizer.step()
+                    scores, loss = eager_step(self.model, self.optimizer, self.criterion, *dl.gather(idx), self.grad_sync)
                 if batch_idx % 100 == 0:
                     print(f"Epoch [{epoch+1}/{self.num_epochs}], Step [{batch_idx}/{len(self.train_dataloader)}], "
                           f"Loss: {loss.item():.4f}")

@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .eegnet import DeviceLoader
 from .optim import CrossEntropyLoss, FusedAdam
+from .runtime import DeviceLoader
 from .transformer import Encoder
 
 

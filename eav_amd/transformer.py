@@ -35,6 +35,7 @@ import torch.nn as nn
 
 from . import _lib
 from .optim import flatten_parameters
+from .runtime import KernelFn
 
 
 DEFAULT_PRECISION = "split"
@@ -144,18 +145,6 @@ def _set_param(root, dotted, value):
 class _Out:
     def __init__(self, logits, loss=None):
         self.logits, self.loss = logits, loss
-
-
-class _EncFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        ctx.model = model
-        ctx.token = model._launch_forward(x)
-        return model._ws.logits.clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        return (None, None, *ctx.model._launch_backward(dlogits.contiguous(), ctx.token))
 
 
 class _HeadFn(torch.autograd.Function):
@@ -348,6 +337,9 @@ class Encoder(nn.Module):
             self._flat = flatten_parameters(self, order=self._names)
             self._pmap = dict(self.named_parameters())
 
+    def _forward_output(self):          # what KernelFn hands to autograd
+        return self._ws.logits.clone()
+
     def forward(self, x=None, labels=None, pixel_values=None, input_values=None):
         x = x if x is not None else (pixel_values if pixel_values is not None else input_values)
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -361,7 +353,7 @@ class Encoder(nn.Module):
         self._ensure_flat()
         self._want_full = torch.is_grad_enabled() and any(
             p.requires_grad for k, p in self._pmap.items() if not k.startswith("classifier."))
-        logits = _EncFn.apply(x, self, *[self._pmap[k] for k in self._names])
+        logits = KernelFn.apply(x, self, *[self._pmap[k] for k in self._names])
         loss = None
         if labels is not None:
             from .optim import CrossEntropyLoss

@@ -29,8 +29,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .eegnet import DeviceLoader, GraphStep, cached_workspace
-from .optim import CrossEntropyLoss, FusedAdam, flatten_parameters
+from .optim import CrossEntropyLoss, FusedAdam
+from .runtime import DeviceLoader, GraphStep, KernelFn, KernelModule, eager_step
 
 NF, KC, POOL, STRIDE, HD = 40, 13, 35, 7, 64     # filters / conv taps / pool window / pool stride / attention tile
 SLOT = 4128                                      # floats per operand-scale slot (EAV_SP_SLOT, include/eav_hip.h)
@@ -71,19 +71,9 @@ class TransformerLayer(nn.Module):
         self.dropout = nn.Dropout(drop_p)
 
 
-class _Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        ctx.model = model
-        ctx.token = model._launch_forward(x)
-        return model._ws.probs.clone()
+class ShallowConvNet(KernelModule):
+    _OUTPUT = "probs"
 
-    @staticmethod
-    def backward(ctx, dprobs):
-        return (None, None, *ctx.model._launch_backward(dprobs.contiguous(), ctx.token))
-
-
-class ShallowConvNet(nn.Module):
     def __init__(self, nb_classes: int, chans: int = 30, samples: int = 500, dropout: float = 0.5,
                  num_layers: int = 12):
         super().__init__()
@@ -100,41 +90,24 @@ class ShallowConvNet(nn.Module):
         self.drop_p = float(dropout)
         if not 1 <= nb_classes <= 16:
             raise NotImplementedError("eav_amd.ShallowConvNet: nb_classes <= 16")
-        self._ws = None
-        self._flat = None
-        self._token = 0
-        self._saved = None
-        self.dropout_seed = 0x5A110EED
-        self._dropout_masks = None     # tests: list of uint8 keep masks in the reference's call order
-        self._fwd_counter = None
+        self.dropout_seed = 0x5A110EED     # (set_dropout_masks, tests: list of uint8 keep masks in the reference's call order)
         # "split": softmax(QK^T)V and its backward on the fp16 matrix cores with fp16 hi + lo operand planes
         # (fp32-grade, eav_attn_*_sp); "fp32": the exact-fp32 MFMA kernels
         self.attention_precision = os.environ.get("EAV_SHALLOW_ATTENTION", "split")
 
     # ------------------------------------------------------------------ plumbing
-    def _ensure_flat(self):
-        p0 = self.conv.weight
-        if self._flat is None or self._flat[0].device != p0.device or getattr(p0, "_eav_flat", None) is None \
-                or p0.data_ptr() != self._flat[0].data_ptr():
-            # W_q / W_k / W_v [40,40] become rows 0..39 of three consecutive zero-padded [64,40] blocks: one [192,40]
-            # operand for a single fused q/k/v GEMM whose output columns match the 64-wide attention tile
-            pads = {f"transformer.{l}.attn.W_{n}.weight": (HD - NF) * NF for l in range(self.num_layers) for n in "qkv"}
-            self._flat = flatten_parameters(self, pad_after=pads)
-            self._names = [n for n, _ in self.named_parameters()]
-
-    def set_dropout_masks(self, masks):
-        self._dropout_masks = masks
+    def _pad_after(self):
+        # W_q / W_k / W_v [40,40] become rows 0..39 of three consecutive zero-padded [64,40] blocks: one [192,40]
+        # operand for a single fused q/k/v GEMM whose output columns match the 64-wide attention tile
+        return {f"transformer.{l}.attn.W_{n}.weight": (HD - NF) * NF for l in range(self.num_layers) for n in "qkv"}
 
     def forward(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise _lib.EavError("eav_amd.ShallowConvNet runs on an MI355X only: move the model and the input to the "
-                                "ROCm device (there is no CPU fallback)")
+        self._require_gpu(x)
         if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != 30 or (x.shape[3] - KC + 1 - POOL) // STRIDE + 1 != 65:
             raise ValueError(f"expected input [B,1,30,S] with 65 pooled frames (S in 495..501), got {tuple(x.shape)}")
-        if self.conv.weight.device != x.device:
-            raise _lib.EavError("model and input are on different devices")
+        self._require_same_device(x)
         self._ensure_flat()
-        return _Fn.apply(x.contiguous().float(), self, *self.parameters())
+        return KernelFn.apply(x.contiguous().float(), self, *self.parameters())
 
     # ------------------------------------------------------------------ kernels
     def _alloc(self, B, S, dev):
@@ -203,11 +176,8 @@ class ShallowConvNet(nn.Module):
         st = self._st = _lib.stream_ptr()
         B, S = x.shape[0], x.shape[3]
         # one workspace per batch size, never freed: captured hipGraphs hold its raw pointers, and the zero pad columns
-        # of ws.ao / ws.dao must survive from step to step (see EEGNet_tor._workspace)
-        wkey = (B, S, str(x.device))
-        if not hasattr(self, "_wss"):
-            self._wss = {}
-        ws = self._ws = cached_workspace(self._wss, wkey, lambda: self._alloc(B, S, x.device))
+        # of ws.ao / ws.dao must survive from step to step (cached_workspace)
+        ws = self._workspace((B, S, str(x.device)), lambda: self._alloc(B, S, x.device))
         T, M = ws.T, ws.M
         n = dict(self.named_parameters())
         w = lambda k: P(n[k])  # noqa: E731
@@ -217,10 +187,8 @@ class ShallowConvNet(nn.Module):
         self._token += 1
         cnt = None
         if drop > 0.0 and masks is None:
-            if self._fwd_counter is None or self._fwd_counter.device != x.device:
-                self._fwd_counter = torch.zeros((), dtype=torch.int64, device=x.device)
-            L("eav_counter_inc", P(self._fwd_counter), st)
-            cnt = P(self._fwd_counter)
+            cnt = P(self._counter(x.device))
+            L("eav_counter_inc", cnt, st)
         mk = (lambda i: P(masks[i])) if masks is not None else (lambda i: None)
         scale = 1.0 / math.sqrt(NF)
         split = self._split_attention()
@@ -271,9 +239,7 @@ class ShallowConvNet(nn.Module):
         return self._token
 
     def _launch_backward(self, dprobs, token):
-        if self._saved is None or self._saved[0] != token:
-            raise _lib.EavError("ShallowConvNet.backward: the activations of this forward were overwritten by a later "
-                                "forward (one outstanding forward per backward)")
+        self._check_token(token)
         L, P = _lib.call, _lib.ptr
         st = self._st = _lib.stream_ptr()
         _, x, training, drop, masks, cnt, ws, split = self._saved
@@ -340,7 +306,7 @@ class ShallowConvNet(nn.Module):
             else:
                 L("eav_attn_bwd", qkv, P(ws.ao[l]), P(ws.dao), P(ws.lse[l]), P(ws.delta), dqkv, B, 1, T, HD, scale, st)
             L("eav_add_strided", dqkv + 8 * HD, 3 * HD, da, NF, dqkv + 8 * HD, 3 * HD, M, NF, st)   # the "+ V" branch
-            k = p + "attn.W_q.weight"          # the padded [192,40] block that starts at W_q (see _ensure_flat)
+            k = p + "attn.W_q.weight"          # the padded [192,40] block that starts at W_q (see _pad_after)
             self._wgrad(dqkv, hin, gp(k), 3 * HD, NF, M, 3 * HD, NF)
             self._gemm(dqkv, w(k), dh, M, NF, 3 * HD, 3 * HD, NF, NF, tB=1, acc=1)
         # conv taps and channel projections (the input needs no gradient)
@@ -392,15 +358,7 @@ class TrainerUni:
                                                 self.grad_sync, post_step=self._max_norm)
                     self._graph.run(idx)
                     continue
-                x, y = dl.gather(idx)
-                out = self.model(x)
-                loss = self.criterion(out, y)
-                self.optimizer.zero_grad()
-                loss.backward()
-                if self.grad_sync is not None:
-                    self.grad_sync()
-                self.optimizer.step()
-                self._max_norm()
+                eager_step(self.model, self.optimizer, self.criterion, *dl.gather(idx), self.grad_sync, self._max_norm)
             self.criterion.check()        # labels outside [0, classes) seen by any step of this epoch raise here
             acc = self.validate()
             if epoch == self.epochs - 1:

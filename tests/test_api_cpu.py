@@ -358,6 +358,35 @@ def test_bench_subject_job_record_and_multi_gpu_headline():
     assert mg["eegnet_subjects_ideal_speedup"] == 8.0 and "predicted_strong_scaling_at_8" not in head
 
 
+def test_runtime_module_is_shared_by_the_models_and_reexported_by_eegnet():
+    """eav_amd.runtime holds the training runtime and the models' base class: it imports no model module, eegnet keeps the
+    old import path alive with the same objects, the five models derive from KernelModule, and GraphStep refuses
+    anything else."""
+    import copy
+    import eav_amd.eegnet as eg
+    import eav_amd.runtime as rt
+    from eav_amd import _lib
+    from eav_amd.cnn_audio import AudioModel
+    from eav_amd.cnn_eeg import EEGNet
+    from eav_amd.optim import FusedAdam
+    from eav_amd.transformer_eeg import ShallowConvNet
+    src = open(rt.__file__).read()
+    assert sorted(set(re.findall(r"^from \.(\w*) import", src, flags=re.M))) == ["", "optim"] and "\nimport eav_amd" not in src
+    for name in ("cached_workspace", "gather_batch", "GraphStep", "DeviceLoader"):
+        assert getattr(eg, name) is getattr(rt, name) and getattr(rt, name).__module__ == "eav_amd.runtime"
+    for model in (eg.EEGNet_tor(5), EEGNet(5), ShallowConvNet(5, num_layers=1), AudioModel()):
+        assert isinstance(model, rt.KernelModule) and model._wss == {} and model._flat is None
+        twin = copy.deepcopy(model)
+        assert list(twin.state_dict()) == list(model.state_dict()) and twin._wss is not model._wss
+        with pytest.raises(_lib.EavError, match=f"eav_amd.{type(model).__name__} runs on an MI355X only"):
+            model._require_gpu(torch.zeros(1))
+        with pytest.raises(_lib.EavError, match=f"{type(model).__name__}.backward: the activations of this forward"):
+            model._check_token(1)
+    lin = torch.nn.Linear(2, 2)
+    with pytest.raises(_lib.EavError, match="KernelModule"):
+        rt.GraphStep(lin, FusedAdam(lin.parameters(), capturable=True), None, torch.zeros(4, 2), torch.zeros(4), 2)
+
+
 def test_split_gemm_instantiations_are_scratch_free():
     """Every instantiation of gemm_sp_kernel `dispatch` can pick compiles for gfx950 without scratch (round 5: 36-196 bytes per
     lane in all the default forms - the epilogue's tile-invariant index arithmetic, hoisted out of the persistent tile loop
