@@ -106,14 +106,18 @@ __global__ void relu_dropout_kernel(float* __restrict__ h, int64_t n, float drop
   const uint64_t seed = dropout_seed(seed_in, seed_dev);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float v = h[i];
-    h[i] = v > 0.f ? v * dropout_mult(drop_p, seed, mask, i) : 0.f;
+    // nn.ReLU hands a NaN through (and Dropout keeps it a NaN whatever the keep decision): a diverged run must show
+    h[i] = v > 0.f ? v * dropout_mult(drop_p, seed, mask, i) : (v != v ? v : 0.f);
   }
 }
-// act is the OUTPUT of the forward (relu(pre) * mult): act > 0  <=>  pre > 0 and kept
+// act is the OUTPUT of the forward (relu(pre) * mult): act > 0  <=>  pre > 0 and kept.  A NaN act passes the gradient as a
+// kept element does: torch's ReLU backward passes it at a NaN, and act does not record the keep decision of a NaN
 __global__ void relu_dropout_bwd_kernel(float* __restrict__ dact, const float* __restrict__ act, int64_t n,
                                         float scale) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    dact[i] = act[i] > 0.f ? dact[i] * scale : 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float a = act[i];
+    dact[i] = (a > 0.f || a != a) ? dact[i] * scale : 0.f;
+  }
 }
 // out = resid + y * mult   (out may alias resid)
 __global__ void dropout_add_kernel(const float* __restrict__ y, const float* __restrict__ resid,
@@ -185,7 +189,9 @@ __global__ __launch_bounds__(256) void sqpool_log_fwd_kernel(const float* __rest
     a /= (float)WIN;
     const int64_t oi = ((int64_t)b * NF + f) * NP + p;
     pooled[oi] = a;
-    out[oi] = logf(fminf(fmaxf(a, lo), hi)) * dropout_mult(drop_p, seed, mask, oi);
+    // fminf / fmaxf return the other operand for a NaN: select it back, as torch.clamp propagates it
+    const float cl = a != a ? a : fminf(fmaxf(a, lo), hi);
+    out[oi] = logf(cl) * dropout_mult(drop_p, seed, mask, oi);
   }
 }
 // g[b,t,f] = dL/do = (2/WIN) * o * sum_{p: window p covers t} dy[b,f,p] * drop / m[b,f,p]  (0 outside the clamp range)

@@ -176,21 +176,23 @@ int eav_conv64_wgrad_nparts(int B, int T);
 /* part [nparts][64*64*16]; sum over parts = dL/dW[o,i,k]. */
 int eav_conv64_wgrad(const float* du, const float* in, float* part, int B, int T, int padl, void* stream);
 
-/* ---- canonical EEGNet (CNN_torch/CNN_EEG.py:7-67): run-time F1<=16, D<=8, F2<=64, K1<=512, K2<=32 ----------- */
+/* ---- canonical EEGNet (CNN_torch/CNN_EEG.py:7-67): run-time F1<=16, D<=8, F2<=64, K1<=1024, K2<=32, Chans<=256 -- */
 /* block1[0] nn.Conv2d(1,F1,(1,K),padding='same',bias=False) (CNN_EEG.py:22): x [B,C,S] -> y1 [B,F1,C,S];
  * stat_part [eav_tconv_fwd_nparts()][2*F1] = per-filter sum / sum of squares (input of eav_bn_finalize).
- * F1 == 8 with K <= 300 runs the fp32-MFMA Toeplitz kernels of eav_eegnet_fir_*; other shapes a direct kernel. */
+ * F1 == 8 with K <= 300 runs the fp32-MFMA Toeplitz kernels of eav_eegnet_fir_* (nparts = eav_eegnet_fir_fwd_nparts);
+ * other shapes a direct kernel with one row per (sample, electrode, 1024-sample tile): nparts = B*C*ceil(S/1024). */
 int eav_tconv_fwd_nparts(int B, int C, int S, int F1, int K);
 int eav_tconv_fwd(const float* x, const float* w, float* y1, float* stat_part, int B, int C, int S, int F1, int K,
                   void* stream);
 /* its weight gradient with the block1[1] BatchNorm backward folded in; bn_params = mean, invstd, scale, shift,
- * m1, m2 (F1 each); part [eav_tconv_wgrad_nparts()][F1*K]. */
+ * m1, m2 (F1 each); part [eav_tconv_wgrad_nparts()][F1*K], nparts = min(B*C*ceil(S/512), 1024) for the direct kernel
+ * (eav_eegnet_fir_wgrad_nparts for F1 == 8, K <= 300). */
 int eav_tconv_wgrad_nparts(int B, int C, int S, int F1, int K);
 int eav_tconv_wgrad(const float* x, const float* y1, const float* g1, const float* bn_params, float* part, int B,
                     int C, int S, int F1, int K, void* stream);
 /* block1[1..2]: BatchNorm affine -> depthwise nn.Conv2d(F1,D*F1,(Chans,1),groups=F1) (CNN_EEG.py:23-25):
- * y1 -> z [B,D*F1,S]; stat_part [eav_spatial_nparts()][2*D*F1].  elu != 0 puts an ELU between the BatchNorm and the
- * conv: firstBN -> ELU -> depthwiseConv of EEGNet_tor (EEGNet_tor.py:52-54) for widths the specialised
+ * y1 -> z [B,D*F1,S]; stat_part [eav_spatial_nparts() = B*ceil(S/1024)][2*D*F1], row (b, tile).  elu != 0 puts an ELU
+ * between the BatchNorm and the conv: firstBN -> ELU -> depthwiseConv of EEGNet_tor (EEGNet_tor.py:52-54) for widths the specialised
  * eav_eegnet_dw_* kernels do not cover. */
 int eav_spatial_nparts(int B, int S);
 int eav_spatial_fwd(const float* y1, const float* bn1, const float* wd, float* z, float* stat_part, int B, int C,
@@ -200,8 +202,9 @@ int eav_spatial_bwd(const float* y1, const float* dz, const float* bn1, const fl
                     float* w_part, int B, int C, int S, int F1, int D, int elu, void* stream);
 /* Dense temporal conv nn.Conv2d(Cin,Cout,(1,K),padding='same',bias=False), K <= 16, channels <= 64: the
  * "separableConv" of EEGNet_tor (EEGNet_tor.py:37,59) at widths other than 64 -> 64 (those run eav_conv64_*).
- * in [B,Cin,T], w [Cout,Cin,K] -> out [B,Cout,T]; stat_part (or NULL) [eav_dconv_fwd_nparts()][2*Cout] = per-channel
- * sum / sum of squares.  transposed != 0: the data gradient - in = dL/dout [B,Cin,T] (Cin = the conv's OUTPUT
+ * in [B,Cin,T], w [Cout,Cin,K] -> out [B,Cout,T]; stat_part (or NULL) [eav_dconv_fwd_nparts() = B*ceil(T/64)][2*Cout],
+ * row (b, tile) = per-channel sum / sum of squares.
+ * transposed != 0: the data gradient - in = dL/dout [B,Cin,T] (Cin = the conv's OUTPUT
  * channels), out = dL/din [B,Cout,T], w = the forward weight [Cin,Cout,K]. */
 int eav_dconv_fwd_nparts(int B, int T);
 int eav_dconv_fwd(const float* in, const float* w, float* out, float* stat_part, int B, int Cin, int Cout, int T,
@@ -209,11 +212,12 @@ int eav_dconv_fwd(const float* in, const float* w, float* out, float* stat_part,
 /* its weight gradient: part [B][Cout*Cin*K] (finish with eav_reduce_partials over the B rows). */
 int eav_dconv_wgrad(const float* dy, const float* x, float* part, int B, int Cin, int Cout, int T, int K, void* stream);
 /* block2[0..1]: depthwise (1,K2) 'same' conv then pointwise 1x1 conv (CNN_EEG.py:35-37): a [B,C2,T] ->
- * d3 [B,C2,T] (kept for the backward) and z [B,F2,T]; stat_part [eav_sepconv_fwd_nparts()][2*F2]. */
+ * d3 [B,C2,T] (kept for the backward) and z [B,F2,T]; stat_part [eav_sepconv_fwd_nparts() = B*ceil(T/128)][2*F2],
+ * row (b, tile).  C2 = D*F1 <= 64. */
 int eav_sepconv_fwd_nparts(int B, int T);
 int eav_sepconv_fwd(const float* a, const float* wdw, const float* wp, float* d3, float* z, float* stat_part, int B,
                     int C2, int F2, int T, int K2, void* stream);
-/* pointwise backward: dd3 [B,C2,T] and w_part [eav_pointwise_bwd_nparts()][F2*C2]. */
+/* pointwise backward: dd3 [B,C2,T] and w_part [eav_pointwise_bwd_nparts() = min(B*ceil(T/64), 512)][F2*C2]. */
 int eav_pointwise_bwd_nparts(int B, int T);
 int eav_pointwise_bwd(const float* du, const float* d3, const float* wp, float* dd3, float* w_part, int B, int C2,
                       int F2, int T, void* stream);
@@ -486,14 +490,18 @@ int eav_pair_mean(float* seq, float* pooled, int B, int D, int backward, void* s
 
 /* ---- ShallowConvNet + single-head transformer (Transformer_torch/Transformer_EEG.py:14-148) ------------------- */
 /* conv(1->NF,(1,KC),valid) fused with PatchEmbedding's per-filter Linear(Chans->1) (:117,:28-35):
- * x [B,C,S] -> u [B,NF,S] (channel-projected input, kept for the backward) and v [B,S-KC+1,NF] tokens. */
+ * x [B,C,S] -> u [B,NF,S] (channel-projected input, kept for the backward) and v [B,S-KC+1,NF] tokens.
+ * Chans <= 32, NF <= 48, KC <= 16, S >= KC; the columns of wv beyond Chans are not read.
+ * eav_shallow_embed_nparts(B, S) = B*ceil(S/64). */
 int eav_shallow_embed_nparts(int B, int S);
 int eav_shallow_embed_fwd(const float* x, const float* wc, const float* wv /*[NF] rows, stride ldv*/, int ldv, float* u,
                           float* v, int B, int C, int S, int NF, int KC, void* stream);
 /* weight gradients: part_c [nparts][NF*KC] (conv taps), part_v [nparts][NF*C] (channel projections). */
 int eav_shallow_embed_bwd(const float* dv, const float* x, const float* u, const float* wc, float* part_c,
                           float* part_v, int B, int C, int S, int NF, int KC, void* stream);
-/* nn.ReLU -> nn.Dropout in place (:84-85) and its backward (act = the forward's output). */
+/* nn.ReLU -> nn.Dropout in place (:84-85) and its backward (act = the forward's output).  A NaN propagates, as in
+ * nn.ReLU: the forward leaves it a NaN whatever its keep decision; the backward passes the gradient (times the dropout
+ * scale) where act is NaN, as torch's ReLU backward does - act does not record whether a NaN was kept. */
 int eav_relu_dropout(float* h, int64_t n, float drop_p, uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev,
                      void* stream);
 int eav_relu_dropout_bwd(float* dact, const float* act, int64_t n, float drop_p, void* stream);
@@ -503,15 +511,19 @@ int eav_dropout_add(const float* y, const float* resid, float* out, int64_t n, f
 /* out[m,0:n) = a[m,0:n) (+ b[m,0:n)) with leading dimensions - the "+ V" residual of MultiHeadAttention (:74-76). */
 int eav_add_strided(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int64_t M, int n,
                     void* stream);
-/* per-column sum / sum of squares of x [M,N<=256]: part [eav_colstats_nparts(M)][2N] (BatchNorm over tokens, :136). */
+/* per-column sum / sum of squares of x [M,N<=256]: part [eav_colstats_nparts(M) = ceil(M/256)][2N], row p = rows
+ * [256 p, 256 p + 256) (BatchNorm over tokens, :136). */
 int eav_colstats_nparts(int64_t M);
 int eav_colstats(const float* x, float* part, int64_t M, int N, int ld, void* stream);
 /* head (:136-144): BatchNorm affine -> square -> AvgPool(1,win)/stride -> log(clamp(lo,hi)) -> Dropout.
- * v [B,T,NF] tokens -> pooled [B,NF,NP] (pre-log means, kept for the backward) and out [B,NF*NP]. */
+ * v [B,T,NF] tokens -> pooled [B,NF,NP] (pre-log means, kept for the backward) and out [B,NF*NP].  A NaN mean propagates
+ * (torch.clamp), it is not clamped to lo.  NF <= 256, (NP-1)*stride + win <= T, NF*NP + 512 floats within 64 KB. */
 int eav_sqpool_log_fwd(const float* v, const float* bn, float* pooled, float* out, int B, int T, int NF, int NP,
                        int win, int stride, float lo, float hi, float drop_p, uint64_t seed, const uint8_t* mask,
                        const uint64_t* seed_dev, void* stream);
-/* g [B,T,NF] = dL/d(BatchNorm output); part [B][2*NF] = sums for eav_bn_bwd_finalize. */
+/* g [B,T,NF] = dL/d(BatchNorm output) (zero for tokens no window covers); part [B][2*NF] = sums for
+ * eav_bn_bwd_finalize.  The gradient passes where lo <= pooled <= hi, bounds included (torch.clamp's backward), and is zero
+ * at a NaN mean. */
 int eav_sqpool_log_bwd(const float* dy, const float* pooled, const float* v, const float* bn, float* g, float* part,
                        int B, int T, int NF, int NP, int win, int stride, float lo, float hi, float drop_p,
                        uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev, void* stream);

@@ -1,0 +1,96 @@
+"""Checking helpers shared by the kernel-level GPU tests (test_audio_cnn_kernels_gpu.py, test_eegnet_canon_kernels_gpu.py,
+test_shallow_tf_kernels_gpu.py): sentinel-filled output buffers with a guard band, deterministic data, and the two
+comparisons - bit equality and an element-wise bound.
+
+Every output is filled with a NaN sentinel (payload 0x7fc0dead; 0xFF for uint8) and carries a guard band past its end:
+everything the contract says is written must be overwritten, the guard band must be untouched."""
+import zlib
+
+import numpy as np
+import torch
+
+from eav_amd import synth
+
+SENT = 0x7FC0DEAD           # fp32 sentinel: a NaN no arithmetic on the data produces
+GUARD = 4096                # default guard band (elements) past every output
+
+_KEEP = []
+
+
+def dev(a):
+    """Host array -> device tensor that stays alive until the test module is torn down
+    (a temporary's memory would be recycled by the caching allocator before the kernel ran)."""
+    t = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).contiguous().cuda()
+    _KEEP.append(t)
+    if len(_KEEP) > 64:
+        torch.cuda.synchronize()
+        del _KEEP[:32]
+    return t
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def sentinel_buf(n, dtype=torch.float32, guard=GUARD):
+    """n elements plus the guard band, all sentinel."""
+    if dtype == torch.uint8:
+        return dev(torch.full((n + guard,), 0xFF, dtype=torch.uint8))
+    return dev(torch.full((n + guard,), SENT, dtype=torch.int32)).view(torch.float32)
+
+
+def take(buf, n, shape, what):
+    """The first n elements of a sentinel buffer after the launch: all written, guard band intact."""
+    torch.cuda.synchronize()
+    h = buf.cpu()
+    bits = h if h.dtype == torch.uint8 else h.view(torch.int32)
+    s = 0xFF if h.dtype == torch.uint8 else SENT
+    unwritten = int((bits[:n] == s).sum())
+    assert unwritten == 0, f"{what}: {unwritten} of {n} elements never written"
+    assert (bits[n:] == s).all(), f"{what}: guard band written at {int((bits[n:] != s).nonzero()[0])} past the end"
+    return h[:n].view(shape)
+
+
+def seed_of(*case):
+    return zlib.crc32(repr(case).encode())
+
+
+def ints(seed, shape, lo, hi):
+    """float32 integers uniform in [lo, hi]."""
+    n = int(np.prod(shape))
+    return torch.from_numpy((lo + (synth.splitmix64(seed, n) % np.uint64(hi - lo + 1)).astype(np.int64))
+                            .astype(np.float32).reshape(shape))
+
+
+def normal(seed, shape, std=1.0):
+    return torch.from_numpy(synth.normal(seed, shape, 0.0, std))
+
+
+def keep_mask(seed, shape, p):
+    return torch.from_numpy((synth.uniform(seed, shape) >= p).astype(np.uint8))
+
+
+def assert_exact(bound, quantum, what):
+    """Every partial sum is a multiple of quantum of magnitude <= bound: exact in fp32 if bound / quantum < 2^24."""
+    assert bound / quantum < 2.0 ** 24, f"{what}: partial sums up to {bound} in steps of {quantum} are not exact in fp32"
+
+
+def same(got, ref, what):
+    """Bit-for-bit as values (NaN equal to NaN)."""
+    got, ref = got.double(), ref.double()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    gn, rn = torch.isnan(got), torch.isnan(ref)
+    assert torch.equal(gn, rn), f"{what}: NaN at {int((gn != rn).sum())} other places"
+    bad = (got != ref) & ~gn
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.numel()} differ, max "
+                           f"{(got - ref)[bad].abs().max():.3e}, first at {tuple(bad.nonzero()[0].tolist())}")
+
+
+def within(got, ref, tol, what):
+    got, ref = got.double(), ref.double()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert not torch.isnan(got).any(), f"{what}: NaN"
+    err = (got - ref).abs()
+    bad = err > tol
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.numel()} beyond the bound, worst {(err - tol).max():.3e}, "
+                           f"first at {tuple(bad.nonzero()[0].tolist())}")
