@@ -102,6 +102,14 @@ SIGNATURES = {
     "eav_attn_dqkv_bound": [_p, _p, _p, _i, _f, _p],
     "eav_attn_fwd": [_p, _p, _p, _i, _i, _i, _i, _f, _p],
     "eav_attn_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
+    "eav_attn_fwd_dropout": [_p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _p, _p],
+    "eav_attn_bwd_dropout": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _p, _p],
+    "eav_attn_fwd_sp_dropout": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _p, _p],
+    "eav_attn_bwd_sp_dropout": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _p, _p],
+    "eav_tf_dropout_mask": [_p, _i64, _f, _u64, _p, _p],
+    "eav_tf_dropout_add": [_p, _p, _p, _i64, _f, _u64, _p, _p, _p],
+    "eav_softmax_dropout_fwd": [_p, _p, _i64, _i, _i, _f, _u64, _p, _p, _p],
+    "eav_softmax_dropout_bwd": [_p, _p, _p, _i64, _i, _i, _f, _u64, _p, _p, _p],
     "eav_layernorm_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _f, _p],
     "eav_layernorm_bwd": [_p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _p],
     "eav_softmax_fwd": [_p, _i64, _i, _i, _p],

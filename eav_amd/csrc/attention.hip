@@ -15,6 +15,13 @@
 //           (key tile stationary, S[q][key] = Q-tile . K^T in the untransposed orientation)   128 MFMAs
 // Inputs are the fused projection output qkv [B*N, 3*D] (Q | K | V, head h at columns h*64) and, for the
 // backward, dO [B*N, D], the saved log-sum-exp and delta = rowsum(dO * O).
+//
+// Attention-probability dropout (HF attention_probs_dropout_prob, training only) is a second instantiation of each kernel
+// (DROP = true; the DROP = false code is the kernel without it).  The keep decision of element (b, h, q, key) is
+// dropout_mult(p, seed', ((b H + h) N + q) N + key): a hash of the index, or an explicit mask byte - never stored, each
+// kernel regenerates it.  The softmax statistics (running maximum, l, the log-sum-exp) are those of the UNDROPPED scores;
+// O = (M o P / (1 - p)) V, and in the backward dP = (dO V^T) o M / (1 - p), delta = rowsum(dO o O) with the dropped O,
+// dS = P o (dP - delta), dV = (M o P / (1 - p))^T dO.
 #include "eav_common.h"
 #include "../../include/eav_hip.h"
 
@@ -31,6 +38,13 @@ __device__ __forceinline__ int kappa(int ks, int kk) { return (ks & 3) + 8 * (ks
 // work between the MFMA phases was a third of a key-tile iteration.  lse stays in natural-log units at the ABI.
 constexpr float LOG2E = 1.44269504088896340736f, LN2 = 0.69314718055994530942f;
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+struct DropArgs {               // attention-probability dropout (DROP instantiations only)
+  float p;
+  uint64_t seed;
+  const uint8_t* mask;          // explicit keep-mask [B, H, N, N] (tests) or nullptr: the generator
+  const uint64_t* seed_dev;     // device-resident forward counter folded into the seed
+};
 
 // stage a [32][64] tile (rows r0.., zero beyond nrows) of a [*, ld] matrix into LDS with row stride `stride`
 __device__ __forceinline__ void fetch_tile(const float* __restrict__ base, int ld, int r0, int nrows, float4 (&reg)[2]) {
@@ -53,8 +67,10 @@ __device__ __forceinline__ void commit_tile(float* __restrict__ lds, int stride,
 
 // ------------------------------------------------------------------------------------------ forward
 // grid (ceil(N/128), B*H).  out: ao [B*N, D] (head columns), lse [B*H, N] = m + log(l) of the scaled scores.
+template <bool DROP>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ ao,
-                                                          float* __restrict__ lse, int N, int H, float scale) {
+                                                          float* __restrict__ lse, int N, int H, float scale,
+                                                          DropArgs dr) {
   __shared__ __attribute__((aligned(16))) float smem[2 * 32 * KS + 2 * 32 * HD];   // one array: carved below
   float (*Ks)[32 * KS] = reinterpret_cast<float (*)[32 * KS]>(smem);
   float (*Vs)[32 * HD] = reinterpret_cast<float (*)[32 * HD]>(smem + 2 * 32 * KS);
@@ -114,6 +130,15 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const float* __restric
     rs += __shfl_xor(rs, 32, 64);
     l = l * alpha + rs;
     m = mn;
+    if constexpr (DROP) {                        // after the row sum: l and the lse stay those of the undropped scores
+      const uint64_t seed = dropout_seed(dr.seed, dr.seed_dev);
+      const uint64_t base = ((uint64_t)bh * N + q) * N + 32 * kt;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kq = kappa(r, kk);
+        s[r] *= (q < N && 32 * kt + kq < N) ? dropout_mult(dr.p, seed, dr.mask, base + kq) : 0.f;
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
     // O^T[d][q] += V^T[d][kappa] * P^T[kappa][q]
@@ -197,9 +222,11 @@ __device__ __forceinline__ void store_rows_T(float* __restrict__ patch, const f3
 }
 
 // dQ: query tile stationary.  grid (ceil(N/128), B*H)
+template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                             const float* __restrict__ lse, const float* __restrict__ delta,
-                                                            float* __restrict__ dqkv, int N, int H, float scale) {
+                                                            float* __restrict__ dqkv, int N, int H, float scale,
+                                                            DropArgs dr) {
   __shared__ __attribute__((aligned(16))) float smem[4 * 32 * KS];      // Ks[2], Vs[2], stride KS
   float (*Ks)[32 * KS] = reinterpret_cast<float (*)[32 * KS]>(smem);
   float (*Vs)[32 * KS] = reinterpret_cast<float (*)[32 * KS]>(smem + 2 * 32 * KS);
@@ -251,6 +278,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const float* __restr
       for (int r = 0; r < 16; ++r)
         if (32 * kt + kappa(r, kk) >= N) s[r] = -INFINITY;
     }
+    if constexpr (DROP) {                                                                // dP^T o M / (1 - p)
+      const uint64_t seed = dropout_seed(dr.seed, dr.seed_dev);
+      const uint64_t base = ((uint64_t)bh * N + q) * N + 32 * kt;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kq = kappa(r, kk);
+        dp[r] *= (q < N && 32 * kt + kq < N) ? dropout_mult(dr.p, seed, dr.mask, base + kq) : 0.f;
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = ex2(s[r] - lq) * (dp[r] - dq_);                   // dS^T = P^T o (dP^T - delta)
     const float* kd = Ks[buf] + j;
@@ -271,9 +307,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const float* __restr
 }
 
 // dK, dV: key tile stationary.  grid (ceil(N/128), B*H)
+template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                              const float* __restrict__ lse, const float* __restrict__ delta,
-                                                             float* __restrict__ dqkv, int N, int H, float scale) {
+                                                             float* __restrict__ dqkv, int N, int H, float scale,
+                                                             DropArgs dr) {
   __shared__ __attribute__((aligned(16))) float smem[4 * 32 * KS + 4 * 32];   // Qs[2], dOs[2], lse[2][32], delta[2][32]
   float (*Qs)[32 * KS] = reinterpret_cast<float (*)[32 * KS]>(smem);
   float (*Os)[32 * KS] = reinterpret_cast<float (*)[32 * KS]>(smem + 2 * 32 * KS);
@@ -326,6 +364,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const float* __rest
   __syncthreads();
   for (int qt = 0; qt < nqt; ++qt) {
     const int buf = qt & 1;
+    // keep bits of this lane's 16 (query, key) elements first - before the next tile's prefetch registers and the
+    // score tiles are live (the kernel sits at 229 VGPRs without them)
+    unsigned keep = 0u;
+    if constexpr (DROP) {
+      if (key < N) {
+        const uint64_t seed = dropout_seed(dr.seed, dr.seed_dev);
+        const uint64_t base = ((uint64_t)bh * N + 32 * qt) * N + key;
+        // a real loop (two elements per trip), not 16 unrolled hashes: unrolled, their 64-bit products are scheduled side by
+        // side and the kernel - at 229 VGPRs without dropout - spills
+#pragma unroll 2
+        for (int r = 0; r < 16; ++r) {
+          const int qi = kappa(r, kk);
+          if (32 * qt + qi < N && dropout_keep(dr.p, seed, dr.mask, base + (uint64_t)qi * N)) keep |= 1u << r;
+        }
+      }
+    }
+    if constexpr (DROP) __builtin_amdgcn_sched_barrier(0);
     if (qt + 1 < nqt) fetch(qt + 1);
     f32x16 s, dp;
 #pragma unroll
@@ -347,8 +402,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const float* __rest
     for (int r = 0; r < 16; ++r) {
       const int qi = kappa(r, kk);
       const float p = ex2(s[r] - Ls[buf * 32 + qi]);
+      if constexpr (DROP) {
+        const float mlt = (keep >> r & 1u) ? dropout_scale(dr.p) : 0.f;
+        dp[r] = p * (dp[r] * mlt - Ds[buf * 32 + qi]);   // dS = P o (dP o M / (1 - p) - delta)
+        s[r] = p * mlt;                                   // the dropped probabilities, for dV
+      } else {
       dp[r] = p * (dp[r] - Ds[buf * 32 + qi]);     // dS[q][key]
       s[r] = p;                                     // P[q][key]
+      }
     }
     const float* od = Os[buf] + j;
     const float* qd = Qs[buf] + j;
@@ -370,29 +431,71 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const float* __rest
 
 }  // namespace
 
-extern "C" int eav_attn_fwd(const float* qkv, float* ao, float* lse, int B, int H, int N, int head_dim, float scale,
-                            void* stream) {
-  EAV_REQUIRE(qkv && ao && lse && B > 0 && H > 0 && N > 0, "eav_attn_fwd: bad arguments");
-  EAV_REQUIRE(head_dim == HD, "eav_attn_fwd: head_dim %d unsupported by the fused kernel (needs %d)", head_dim, HD);
+static int attn_fwd_launch(const float* qkv, float* ao, float* lse, int B, int H, int N, int head_dim, float scale,
+                           const DropArgs* dr, void* stream, const char* who) {
+  EAV_REQUIRE(qkv && ao && lse && B > 0 && H > 0 && N > 0, "%s: bad arguments", who);
+  EAV_REQUIRE(head_dim == HD, "%s: head_dim %d unsupported by the fused kernel (needs %d)", who, head_dim, HD);
   dim3 grid(cdiv(N, TQ), B * H);
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, qkv, ao, lse, N, H, scale);
-  EAV_CHECK_LAUNCH("eav_attn_fwd");
+  if (dr)
+    hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ao, lse, N, H, scale, *dr);
+  else
+    hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ao, lse, N, H, scale,
+                       DropArgs{});
+  EAV_CHECK_LAUNCH(who);
   return EAV_OK;
 }
 
 // delta: scratch [B*H, N].  dqkv [B*N, 3*H*64] receives dQ | dK | dV in the layout of qkv.
-extern "C" int eav_attn_bwd(const float* qkv, const float* ao, const float* dout, const float* lse, float* delta,
-                            float* dqkv, int B, int H, int N, int head_dim, float scale, void* stream) {
-  EAV_REQUIRE(qkv && ao && dout && lse && delta && dqkv && B > 0 && H > 0 && N > 0, "eav_attn_bwd: bad arguments");
-  EAV_REQUIRE(head_dim == HD, "eav_attn_bwd: head_dim %d unsupported by the fused kernel (needs %d)", head_dim, HD);
+static int attn_bwd_launch(const float* qkv, const float* ao, const float* dout, const float* lse, float* delta,
+                           float* dqkv, int B, int H, int N, int head_dim, float scale, const DropArgs* dr, void* stream,
+                           const char* who) {
+  EAV_REQUIRE(qkv && ao && dout && lse && delta && dqkv && B > 0 && H > 0 && N > 0, "%s: bad arguments", who);
+  EAV_REQUIRE(head_dim == HD, "%s: head_dim %d unsupported by the fused kernel (needs %d)", who, head_dim, HD);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)cdiv64((int64_t)B * N * H, 4)), dim3(256), 0, st, ao, dout, delta,
                      B, N, H);
-  EAV_CHECK_LAUNCH("eav_attn_bwd(delta)");
+  EAV_CHECK_LAUNCH(who);
   dim3 grid(cdiv(N, TQ), B * H);
-  hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, N, H, scale);
-  EAV_CHECK_LAUNCH("eav_attn_bwd(dQ)");
-  hipLaunchKernelGGL(attn_bwd_kv_kernel, grid, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, N, H, scale);
-  EAV_CHECK_LAUNCH("eav_attn_bwd(dK,dV)");
+  if (dr)
+    hipLaunchKernelGGL(attn_bwd_q_kernel<true>, grid, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, N, H, scale, *dr);
+  else
+    hipLaunchKernelGGL(attn_bwd_q_kernel<false>, grid, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, N, H, scale,
+                       DropArgs{});
+  EAV_CHECK_LAUNCH(who);
+  if (dr)
+    hipLaunchKernelGGL(attn_bwd_kv_kernel<true>, grid, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, N, H, scale, *dr);
+  else
+    hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, grid, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, N, H, scale,
+                       DropArgs{});
+  EAV_CHECK_LAUNCH(who);
   return EAV_OK;
+}
+
+extern "C" int eav_attn_fwd(const float* qkv, float* ao, float* lse, int B, int H, int N, int head_dim, float scale,
+                            void* stream) {
+  return attn_fwd_launch(qkv, ao, lse, B, H, N, head_dim, scale, nullptr, stream, "eav_attn_fwd");
+}
+
+extern "C" int eav_attn_bwd(const float* qkv, const float* ao, const float* dout, const float* lse, float* delta,
+                            float* dqkv, int B, int H, int N, int head_dim, float scale, void* stream) {
+  return attn_bwd_launch(qkv, ao, dout, lse, delta, dqkv, B, H, N, head_dim, scale, nullptr, stream, "eav_attn_bwd");
+}
+
+// The same with attention-probability dropout 0 < drop_p < 1 (mask: explicit uint8 keep-mask [B, H, N, N] or NULL for the
+// generator; seed_dev: optional device counter folded into the seed).  ao receives the DROPPED output, lse the undropped
+// statistics; the backward must be given the same (drop_p, seed, mask, seed_dev value) as its forward.
+extern "C" int eav_attn_fwd_dropout(const float* qkv, float* ao, float* lse, int B, int H, int N, int head_dim,
+                                    float scale, float drop_p, uint64_t seed, const uint8_t* mask,
+                                    const uint64_t* seed_dev, void* stream) {
+  EAV_REQUIRE(drop_p > 0.f && drop_p < 1.f, "eav_attn_fwd_dropout: need 0 < drop_p < 1");
+  const DropArgs dr{drop_p, seed, mask, seed_dev};
+  return attn_fwd_launch(qkv, ao, lse, B, H, N, head_dim, scale, &dr, stream, "eav_attn_fwd_dropout");
+}
+
+extern "C" int eav_attn_bwd_dropout(const float* qkv, const float* ao, const float* dout, const float* lse, float* delta,
+                                    float* dqkv, int B, int H, int N, int head_dim, float scale, float drop_p,
+                                    uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev, void* stream) {
+  EAV_REQUIRE(drop_p > 0.f && drop_p < 1.f, "eav_attn_bwd_dropout: need 0 < drop_p < 1");
+  const DropArgs dr{drop_p, seed, mask, seed_dev};
+  return attn_bwd_launch(qkv, ao, dout, lse, delta, dqkv, B, H, N, head_dim, scale, &dr, stream, "eav_attn_bwd_dropout");
 }

@@ -151,10 +151,14 @@ __device__ __forceinline__ uint32_t eav_hash32(uint64_t seed, uint64_t idx) {
 __device__ __forceinline__ uint64_t dropout_seed(uint64_t seed, const uint64_t* seed_dev) {
   return seed_dev ? seed + 2ull * (*seed_dev) : seed;
 }
+// the keep decision alone (drop_p > 0): kernels that hold keep BITS and apply the scale elsewhere share it with dropout_mult
+__device__ __forceinline__ bool dropout_keep(float drop_p, uint64_t seed, const uint8_t* mask, uint64_t idx) {
+  return mask ? (mask[idx] != 0) : ((float)eav_hash32(seed, idx) * (1.0f / 16777216.0f) >= drop_p);
+}
+__device__ __forceinline__ float dropout_scale(float drop_p) { return 1.f / (1.f - drop_p); }
 __device__ __forceinline__ float dropout_mult(float drop_p, uint64_t seed, const uint8_t* mask, uint64_t idx) {
   if (drop_p <= 0.f) return 1.f;
-  bool keep = mask ? (mask[idx] != 0) : ((float)eav_hash32(seed, idx) * (1.0f / 16777216.0f) >= drop_p);
-  return keep ? 1.f / (1.f - drop_p) : 0.f;
+  return dropout_keep(drop_p, seed, mask, idx) ? dropout_scale(drop_p) : 0.f;
 }
 // drop_p < 0 selects nn.Dropout2d semantics with probability -drop_p: ONE draw per (sample, channel) row (the keep
 // decision hashes the row index instead of the element index; an explicit mask stays per element)

@@ -196,10 +196,15 @@ def backend_name():
 def attach(trainer, force=False, group=None):
     """Give a Trainer_uni (or any trainer exposing .model with a flat gradient buffer) a gradient
     all-reduce when running under torchrun with WORLD_SIZE > 1 (force: also in a one-rank group).
-    group: a process sub-group (SubjectSchedule.make_groups) - the replicas of ONE subject's training."""
+    group: a process sub-group (SubjectSchedule.make_groups) - the replicas of ONE subject's training.
+    Dropout: the replicas see different shards of a batch and must not share a mask, so a model that offers
+    mix_dropout_rank (transformer.Encoder) gets its rank WITHIN THE GROUP mixed into its dropout_seed here (rank 0 keeps
+    the seed; transformer.rank_dropout_seed)."""
     if not dist.is_initialized() or (dist.get_world_size(group) == 1 and not force):
         return trainer
     model = trainer.model
+    if hasattr(model, "mix_dropout_rank"):
+        model.mix_dropout_rank(dist.get_rank(group))
     model._ensure_flat()
     trainer.grad_sync = GradSync([model._flat[1]], group=group, force=force)
     if hasattr(model, "grad_ready_hook"):

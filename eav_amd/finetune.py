@@ -66,10 +66,20 @@ class FineTuneBase:
     # state are bit-equal to the uncached run; in "split" precision the patch planes' scale depends on which samples share
     # a batch, so the two runs agree to rounding (~1e-6) instead.  `cache_frozen_features = False` restores the literal
     # schedule.  A trainer-level saving: it never enters bench.py's step metric.
+    #
+    # A checkpoint whose config sets hidden_dropout_prob or attention_probs_dropout_prob has no constant features: the
+    # reference calls model.train() every epoch (Transformer_Audio.py:63), so HF drops inside the frozen backbone too.  The
+    # cache is then bypassed - the frozen phase runs the backbone forward every step, in training mode - and one line says so.
     cache_frozen_features = True
 
     def _begin_phase_cache(self, freeze):
         self._feat_cache = None
+        cfg = self.model.cfg
+        if freeze and self.cache_frozen_features and self.grad_sync is None and (cfg.hidden_dropout > 0.0
+                                                                                 or cfg.attention_dropout > 0.0):
+            print(f"frozen-phase feature cache bypassed: the model drops (hidden {cfg.hidden_dropout:g}, attention "
+                  f"{cfg.attention_dropout:g}), its features differ from step to step")
+            return
         if freeze and self.cache_frozen_features and self.grad_sync is None:
             hid = self.model.cfg.hidden
             self._feat_cache = {"train": torch.empty(len(self.train_dataloader.dataset), hid, device=self.device),

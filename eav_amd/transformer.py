@@ -42,7 +42,12 @@ DEFAULT_PRECISION = "split"
 
 # ----------------------------------------------------------------------------- configuration
 def make_config(kind, hidden=768, layers=12, heads=12, ff=3072, eps=1e-12, num_labels=5, patch=16, mel=128,
-                frames=1024, fstride=10, tstride=10, image=224, channels=3):
+                frames=1024, fstride=10, tstride=10, image=224, channels=3, hidden_dropout=0.0, attention_dropout=0.0):
+    """hidden_dropout / attention_dropout: HF hidden_dropout_prob / attention_probs_dropout_prob, applied in training mode
+    at the four sites of Encoder.dropout_sites; 0 <= p < 1 (0: the site does not exist)."""
+    for name, p in (("hidden_dropout", hidden_dropout), ("attention_dropout", attention_dropout)):
+        if not (isinstance(p, (int, float)) and 0.0 <= float(p) < 1.0):
+            raise ValueError(f"make_config: {name} must satisfy 0 <= p < 1, got {p!r}")
     if kind == "ast":
         ny, nx = (mel - patch) // fstride + 1, (frames - patch) // tstride + 1
         geo = dict(C=1, H=mel, W=frames, sy=fstride, sx=tstride, transposed=1)
@@ -55,7 +60,8 @@ def make_config(kind, hidden=768, layers=12, heads=12, ff=3072, eps=1e-12, num_l
         raise ValueError(kind)
     return SimpleNamespace(kind=kind, hidden=hidden, layers=layers, heads=heads, ff=ff, eps=eps,
                            num_labels=num_labels, patch=patch, ny=ny, nx=nx, npatch=ny * nx, nextra=nextra,
-                           ntok=ny * nx + nextra, prefix=prefix, kp=geo["C"] * patch * patch, **geo)
+                           ntok=ny * nx + nextra, prefix=prefix, kp=geo["C"] * patch * patch,
+                           hidden_dropout=float(hidden_dropout), attention_dropout=float(attention_dropout), **geo)
 
 
 def config_from_hf(cfg_json: dict):
@@ -63,7 +69,9 @@ def config_from_hf(cfg_json: dict):
     common = dict(hidden=cfg_json.get("hidden_size", 768), layers=cfg_json.get("num_hidden_layers", 12),
                   heads=cfg_json.get("num_attention_heads", 12), ff=cfg_json.get("intermediate_size", 3072),
                   eps=cfg_json.get("layer_norm_eps", 1e-12), patch=cfg_json.get("patch_size", 16),
-                  num_labels=len(cfg_json["id2label"]) if "id2label" in cfg_json else cfg_json.get("num_labels", 2))
+                  num_labels=len(cfg_json["id2label"]) if "id2label" in cfg_json else cfg_json.get("num_labels", 2),
+                  hidden_dropout=cfg_json.get("hidden_dropout_prob", 0.0),
+                  attention_dropout=cfg_json.get("attention_probs_dropout_prob", 0.0))
     if cfg_json.get("hidden_act", "gelu") != "gelu":
         raise NotImplementedError("only the exact erf GELU is implemented")
     if mt == "audio-spectrogram-transformer":
@@ -126,6 +134,22 @@ def normalise_key(k):
     for a, b in _HF4:
         k = k.replace(a, b)
     return k
+
+
+def rank_dropout_seed(seed, rank):
+    """The dropout seed of replica `rank` of a data-parallel group: replicas of one model see different shards of the batch
+    and must draw different masks (rank 0 keeps the seed).  The rank goes through a splitmix64 finaliser of its own before it
+    is added: eav_hash32 forms seed + (index + 1) * 0x9E3779B97F4A7C15, so an offset that is a small multiple of that
+    constant (or of anything the index stride reaches within a tensor) would hand rank r the mask of rank 0 shifted by r
+    elements; the finalised value is a multiple of the stride only for a shift of ~2^63 elements."""
+    if int(rank) == 0:
+        return int(seed) & 0xFFFFFFFFFFFFFFFF
+    m = 0xFFFFFFFFFFFFFFFF
+    z = (int(rank) * 0xD6E8FEB86659FD93) & m
+    z = ((z ^ (z >> 32)) * 0xD6E8FEB86659FD93) & m
+    z = ((z ^ (z >> 32)) * 0xD6E8FEB86659FD93) & m
+    z ^= z >> 32
+    return (int(seed) + z) & m
 
 
 class _Node(nn.Module):
@@ -206,6 +230,13 @@ class Encoder(nn.Module):
         self._token = 0
         self._saved = None
         self.kernel_events = None
+        # Dropout (cfg.hidden_dropout / cfg.attention_dropout, training mode only): every keep decision is a hash of
+        # (dropout_seed, site, device-resident forward counter, element index) - no mask is stored, the backward
+        # regenerates it, and a captured step draws fresh masks on every replay.  The default seed follows
+        # torch.manual_seed; set_dropout_masks (tests) replaces the generator by explicit masks.
+        self.dropout_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        self._fwd_counter = None
+        self._dropout_masks = None
         # GEMM / attention operand precision: "split" (default: fp32-grade on the fp16 matrix cores - every operand as
         # fp16 hi + lo planes, three MFMAs per product, csrc/gemm_sp.hip + attention_sp.hip; measured against float64
         # it is not worse than the exact-fp32 kernels and it passes the same parity bounds), "fp32" (exact-fp32 MFMA),
@@ -382,6 +413,92 @@ class Encoder(nn.Module):
         materialised-score path (GEMM + softmax kernels).  `use_fused_attention = False` forces the latter."""
         return getattr(self, "use_fused_attention", True) and self.cfg.hidden // self.cfg.heads == 64
 
+    # ------------------------------------------------------------------ dropout
+    def dropout_active(self):
+        """Whether a training-mode forward of this model drops anything."""
+        return self.cfg.hidden_dropout > 0.0 or self.cfg.attention_dropout > 0.0
+
+    def dropout_sites(self, B):
+        """{site name: (site id, shape, probability)} of the dropout sites that exist for a batch of B, in HF's call order:
+        "emb" [B, ntok, D] after tokens + position embeddings; per layer i "attn.i" [B, H, N, N] on the softmax
+        probabilities, "attn_out.i" and "mlp_out.i" [B, N, D] on the o_proj / fc2 outputs before their residual adds."""
+        c = self.cfg
+        ph, pa = c.hidden_dropout, c.attention_dropout
+        sites = {}
+        if ph > 0.0:
+            sites["emb"] = (0, (B, c.ntok, c.hidden), ph)
+        for i in range(c.layers):
+            if pa > 0.0:
+                sites[f"attn.{i}"] = (1 + 3 * i, (B, c.heads, c.ntok, c.ntok), pa)
+            if ph > 0.0:
+                sites[f"attn_out.{i}"] = (2 + 3 * i, (B, c.ntok, c.hidden), ph)
+                sites[f"mlp_out.{i}"] = (3 + 3 * i, (B, c.ntok, c.hidden), ph)
+        return sites
+
+    def _site_seed(self, site_id):
+        return (int(self.dropout_seed) + ((site_id + 1) << 40)) & 0xFFFFFFFFFFFFFFFF
+
+    def set_dropout_masks(self, masks):
+        """Testing hook (the convention of KernelModule.set_dropout_masks): a dict of contiguous uint8 keep-masks on the
+        model's device, keyed and shaped as in dropout_sites(B), used instead of the generator by every training forward
+        (and its backward) until None restores the generator."""
+        self._dropout_masks = masks
+
+    def mix_dropout_rank(self, rank):
+        """Data parallelism: give replica `rank` its own dropout stream (rank_dropout_seed)."""
+        self.dropout_seed = rank_dropout_seed(self.dropout_seed, rank)
+
+    def forward_counter(self):
+        """Number of generator-mode dropout forwards so far (reads the device counter back)."""
+        return 0 if self._fwd_counter is None else int(self._fwd_counter.item())
+
+    def generated_dropout_masks(self, B, counter, seed=None):
+        """The keep-masks the generator draws in the forward whose counter value is `counter` (the value
+        forward_counter() returns after that forward), as set_dropout_masks takes them."""
+        dev = next(self.parameters()).device
+        cnt = torch.tensor(int(counter), dtype=torch.int64, device=dev)
+        old = self.dropout_seed
+        if seed is not None:
+            self.dropout_seed = seed
+        out = {}
+        try:
+            for name, (sid, shape, p) in self.dropout_sites(B).items():
+                m = torch.empty(shape, dtype=torch.uint8, device=dev)
+                _lib.call("eav_tf_dropout_mask", m.data_ptr(), m.numel(), float(p), self._site_seed(sid), cnt.data_ptr(),
+                          _lib.stream_ptr())
+                out[name] = m
+        finally:
+            self.dropout_seed = old
+        return out
+
+    def _begin_dropout(self, ws, B, dev):
+        """Dropout state of this forward, kept on the workspace for its backward: probabilities (0 in eval mode), the
+        explicit masks or the device counter (advanced here, by a launch)."""
+        c = self.cfg
+        ph, pa = (c.hidden_dropout, c.attention_dropout) if self.training else (0.0, 0.0)
+        d = SimpleNamespace(ph=ph, pa=pa, masks=None, cnt=None)
+        if ph > 0.0 or pa > 0.0:
+            if self._dropout_masks is not None:
+                d.masks = dict(self._dropout_masks)
+                for name, (_, shape, _) in self.dropout_sites(B).items():
+                    m = d.masks.get(name)
+                    if not (isinstance(m, torch.Tensor) and m.dtype == torch.uint8 and m.device == dev
+                            and tuple(m.shape) == shape and m.is_contiguous()):
+                        raise _lib.EavError(f"set_dropout_masks: site {name!r} needs a contiguous uint8 mask {shape} on {dev}")
+            else:
+                if self._fwd_counter is None or self._fwd_counter.device != dev:
+                    self._fwd_counter = torch.zeros((), dtype=torch.int64, device=dev)
+                self._call("eav_counter_inc", self._fwd_counter.data_ptr(), self._st)
+                d.cnt = self._fwd_counter.data_ptr()
+        d.mk = (lambda name: d.masks[name].data_ptr()) if d.masks is not None else (lambda name: None)
+        ws.drop = d
+        return d
+
+    def _drop_add(self, y, resid, out, n, p, site_id, name):
+        """out = resid + Dropout(y) at a hidden-dropout site (resid None: the gate alone - the site's backward)."""
+        d = self._ws.drop
+        self._call("eav_tf_dropout_add", y, resid, out, n, float(p), self._site_seed(site_id), d.mk(name), d.cnt, self._st)
+
     def _gemm_name(self):
         p = self.precision
         if p not in ("fp32", "split", "bf16", "bf16_bwd"):
@@ -411,6 +528,8 @@ class Encoder(nn.Module):
             ws.delta = f(B * H, N)
         else:
             ws.P = [torch.zeros(B * H, N, ldn, dtype=torch.float32, device=dev) for _ in range(nsave)]
+            if c.attention_dropout > 0.0:     # the dropped probabilities of the current layer (P itself feeds the Jacobian)
+                ws.Pd = torch.zeros(B * H, N, ldn, dtype=torch.float32, device=dev)
         ws.ao = [f(M, D) for _ in range(nsave)]
         ws.hmid = [f(M, D) for _ in range(nsave)]
         ws.y2 = [f(M, D) for _ in range(1 if sp else nsave)]
@@ -424,6 +543,8 @@ class Encoder(nn.Module):
         if full_backward:
             ws.dh, ws.dy, ws.dao = f(M, D), f(M, D), f(M, D)
             ws.dact, ws.dqkv = f(M, FF), f(M, 3 * D)
+            if c.hidden_dropout > 0.0:        # dh o M / (1 - p): what enters the fc2 / o_proj gradient products
+                ws.dhd = f(M, D)
             if not ws.fused:
                 ws.dP = torch.zeros(B * H, N, ldn, dtype=torch.float32, device=dev)
             ws.demb = f(B * c.npatch, D)
@@ -479,6 +600,8 @@ class Encoder(nn.Module):
             ws.np_attn = ws.B * ((c.ntok + 31) // 32)          # bias-gradient partials of the attention backward: one row per 32-token tile
             ws.part_attn_pool = [torch.zeros(ws.np_attn, 3 * D, dtype=torch.float32, device=dev) for _ in range(4)]
             ws.bslots = torch.zeros(2 + self.BS * Lr, self.SLOT, dtype=torch.float32, device=dev)
+            if c.hidden_dropout > 0.0:        # measured scales of the two gated gradients of every layer
+                ws.dslots = torch.zeros(2 * Lr, self.SLOT, dtype=torch.float32, device=dev)
             if ws.fused:
                 ws.dorow = torch.empty(M, 2 * D, dtype=torch.float16, device=dev)
 
@@ -810,8 +933,8 @@ class Encoder(nn.Module):
 
     def last_features(self):
         """The classifier's input of the most recent forward ([B, hidden], a copy): constant per sample while the backbone
-        is frozen (every dropout of the reference checkpoints is 0.0), which is what the trainers' frozen-phase feature
-        cache stores (finetune.FineTuneBase)."""
+        is frozen AND the model has no dropout (dropout_active() false - every dropout of the reference checkpoints is 0.0),
+        which is what the trainers' frozen-phase feature cache stores (finetune.FineTuneBase)."""
         ws = self._ws
         if ws is None:
             raise _lib.EavError("Encoder.last_features: no forward has run")
@@ -849,6 +972,7 @@ class Encoder(nn.Module):
                     torch.cuda.empty_cache()
                 ws = self._ws_cache[B] = self._alloc(B, x.device, full)
             self._ws = ws
+        drop = self._begin_dropout(ws, B, x.device)
         if sp:
             self._refresh_weight_planes(x.device, full)
             ws.fslots.zero_()
@@ -874,6 +998,8 @@ class Encoder(nn.Module):
         L("eav_embed_finish", P(h0), w(f"{pre}.embeddings.cls_token"),
           w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None,
           w(f"{pre}.embeddings.position_embeddings"), B, N, D, c.nextra, st)
+        if drop.ph > 0.0:
+            self._drop_add(P(h0), None, P(h0), M * D, drop.ph, 0, "emb")
         scale = hd ** -0.5
         for i in range(c.layers):
             j = i if ws.full else 0
@@ -891,23 +1017,33 @@ class Encoder(nn.Module):
             qkv = P(ws.qkv[j])
             self._gemm(P(ws.y1[j]), w(f"{Lk}.attention.q_proj.weight"), qkv, M, 3 * D, D, D, D, 3 * D,
                        bias=w(f"{Lk}.attention.q_proj.bias"))
-            if ws.fused:
+            if ws.fused and drop.pa > 0.0:
+                L("eav_attn_fwd_dropout", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, drop.pa,
+                  self._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
+            elif ws.fused:
                 L("eav_attn_fwd", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, st)
             else:
                 Pm = P(ws.P[j])
                 self._gemm(qkv, qkv + 4 * D, Pm, N, N, hd, 3 * D, 3 * D, ldn, batch=B * H, heads=H,
                            sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(H * N * ldn, N * ldn), alpha=scale)
-                L("eav_softmax_fwd", Pm, B * H * N, N, ldn, st)
-                self._gemm(Pm, qkv + 8 * D, P(ws.ao[j]), N, hd, N, ldn, 3 * D, D, tB=1, batch=B * H, heads=H,
+                Pv = self._softmax_forward(i, Pm, B * H * N, N, ldn)
+                self._gemm(Pv, qkv + 8 * D, P(ws.ao[j]), N, hd, N, ldn, 3 * D, D, tB=1, batch=B * H, heads=H,
                            sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
+            # (hidden dropout sits between the bias and the residual add: the product leaves without the residual and one
+            # element-wise pass forms resid + Dropout(product))
+            hd_on = drop.ph > 0.0
             self._gemm(P(ws.ao[j]), w(f"{Lk}.attention.o_proj.weight"), P(ws.hmid[j]), M, D, D, D, D, D,
-                       bias=w(f"{Lk}.attention.o_proj.bias"), resid=P(hin), ldr=D)
+                       bias=w(f"{Lk}.attention.o_proj.bias"), resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
+            if hd_on:
+                self._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
             L("eav_layernorm_fwd", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"), w(f"{Lk}.layernorm_after.bias"),
               P(ws.y2[j]), stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
             self._gemm(P(ws.y2[j]), w(f"{Lk}.mlp.fc1.weight"), P(ws.act[j]), M, FF, D, D, D, FF,
                        bias=w(f"{Lk}.mlp.fc1.bias"), gelu=1, pre=P(ws.pre[j]))
             self._gemm(P(ws.act[j]), w(f"{Lk}.mlp.fc2.weight"), P(hout), M, D, FF, FF, FF, D,
-                       bias=w(f"{Lk}.mlp.fc2.bias"), resid=P(ws.hmid[j]), ldr=D)
+                       bias=w(f"{Lk}.mlp.fc2.bias"), resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
+            if hd_on:
+                self._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
         hlast = ws.hs[c.layers] if ws.full else ws.hs[c.layers & 1]
         R = B * c.nextra
         L("eav_token_rows", P(hlast), P(ws.rows), B, N, D, c.nextra, 0, st)
@@ -920,6 +1056,41 @@ class Encoder(nn.Module):
         self._token += 1
         self._saved = (self._token, x, full, None)
         return self._token
+
+    def _softmax_forward(self, i, Pm, rows, N, ldn):
+        """Materialised-score path: softmax in place over the scores of layer i; returns the operand of the P.V product -
+        P itself, or with attention dropout the dropped probabilities (P stays undropped for the Jacobian)."""
+        ws = self._ws
+        d = ws.drop
+        if d.pa > 0.0:
+            self._call("eav_softmax_dropout_fwd", Pm, _lib.ptr(ws.Pd), rows, N, ldn, d.pa, self._site_seed(1 + 3 * i),
+                       d.mk(f"attn.{i}"), d.cnt, self._st)
+            return _lib.ptr(ws.Pd)
+        self._call("eav_softmax_fwd", Pm, rows, N, ldn, self._st)
+        return Pm
+
+    def _attention_backward_scores(self, g, i, qkv, dao, dqkv, scale):
+        """Materialised-score path, backward of the attention core of layer i with the batched product `g`: dV = Pd^T dO,
+        dP = dO V^T, dS = softmax backward (in place over dP), dQ = s dS K, dK = s dS^T Q.  With attention dropout the
+        softmax backward gates dP and regenerates the dropped probabilities Pd, so it runs before the dV product."""
+        c, ws = self.cfg, self._ws
+        D, N, H = c.hidden, c.ntok, c.heads
+        hd, ldn, B = D // H, ws.ldn, ws.B
+        P, d = _lib.ptr, ws.drop
+        Pm, dP = P(ws.P[i]), P(ws.dP)
+        sP, sQ, sO = (H * N * ldn, N * ldn), (N * 3 * D, hd), (N * D, hd)
+        if d.pa > 0.0:
+            g(dao, qkv + 8 * D, dP, N, N, hd, D, 3 * D, ldn, batch=B * H, heads=H, sA=sO, sB=sQ, sC=sP)
+            self._call("eav_softmax_dropout_bwd", Pm, dP, P(ws.Pd), B * H * N, N, ldn, d.pa, self._site_seed(1 + 3 * i),
+                       d.mk(f"attn.{i}"), d.cnt, self._st)
+            g(P(ws.Pd), dao, dqkv + 8 * D, N, hd, N, ldn, D, 3 * D, tA=1, tB=1, batch=B * H, heads=H, sA=sP, sB=sO, sC=sQ)
+        else:
+            g(Pm, dao, dqkv + 8 * D, N, hd, N, ldn, D, 3 * D, tA=1, tB=1, batch=B * H, heads=H, sA=sP, sB=sO, sC=sQ)
+            g(dao, qkv + 8 * D, dP, N, N, hd, D, 3 * D, ldn, batch=B * H, heads=H, sA=sO, sB=sQ, sC=sP)
+            self._call("eav_softmax_bwd", Pm, dP, B * H * N, N, ldn, self._st)
+        g(dP, qkv + 4 * D, dqkv, N, hd, N, ldn, 3 * D, 3 * D, tB=1, batch=B * H, heads=H, sA=sP, sB=sQ, sC=sQ, alpha=scale)
+        g(dP, qkv, dqkv + 4 * D, N, hd, N, ldn, 3 * D, 3 * D, tA=1, tB=1, batch=B * H, heads=H, sA=sP, sB=sQ, sC=sQ,
+          alpha=scale)
 
     def _forward_scales(self, fslot):
         """A-priori operand scales (rigorous bounds: eav_tf_forward_scales_qkv) of y1, qkv, y2, act of EVERY layer in one
@@ -997,7 +1168,13 @@ class Encoder(nn.Module):
             if not qkvp:
                 # row planes of Q | K | V and the per-head transposes (V^T for the forward; Q^T, K^T for the backward)
                 L("eav_attn_sp_prep", qkv, s_qkv, P(ws.qkvrow[j]), None, ws.B, N, 3 * D, D, 0, st)
-            if fusedp and self.fused_ao:
+            if ws.drop.pa > 0.0:
+                # attention dropout: the DROP instantiation, fp32 output and its measured maximum (the o-proj planes come
+                # from the conversion pass below) - the plane-writing form's scale |O| <= max|V| assumes rows of P sum to 1
+                ws.delta_from_planes = False
+                L("eav_attn_fwd_sp_dropout", P(ws.qkvrow[j]), s_qkv, P(ao), P(ws.lse[j]), s_ao, ws.B, H, N, hd, scale,
+                  ws.drop.pa, self._site_seed(1 + 3 * i), ws.drop.mk(f"attn.{i}"), ws.drop.cnt, st)
+            elif fusedp and self.fused_ao:
                 # the attention output leaves as the planes of the o-proj products (scale: qkv's own, |O| <= max|V|); its
                 # fp32 copy is written only when a backward will read it
                 # (... and only by the unfused gradient flow: the fused one forms delta = dO . O from these planes)
@@ -1016,14 +1193,20 @@ class Encoder(nn.Module):
             Pm = P(ws.P[j])
             self._gemm_f32(qkv, qkv + 4 * D, Pm, N, N, hd, 3 * D, 3 * D, ldn, batch=ws.B * H, heads=H,
                            sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(H * N * ldn, N * ldn), alpha=scale)
-            L("eav_softmax_fwd", Pm, ws.B * H * N, N, ldn, st)
-            self._gemm_f32(Pm, qkv + 8 * D, P(ao), N, hd, N, ldn, 3 * D, D, tB=1, batch=ws.B * H, heads=H,
+            Pv = self._softmax_forward(i, Pm, ws.B * H * N, N, ldn)
+            self._gemm_f32(Pv, qkv + 8 * D, P(ao), N, hd, N, ldn, 3 * D, D, tB=1, batch=ws.B * H, heads=H,
                            sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
-        if not (ws.fused and fusedp and self.fused_ao):
+        if not (ws.fused and fusedp and self.fused_ao) or (ws.fused and ws.drop.pa > 0.0):
             self._to_planes(P(ao), M, D, D, s_ao, ws.aop[j], amax_done=ws.fused)
         wpl, wsl = self._wp(f"o{i}")
+        # (hidden dropout: the product leaves without the residual, one element-wise pass forms resid + Dropout(product) - the
+        # split GEMM's epilogue stays as it is)
+        drop = ws.drop
+        hd_on = drop.ph > 0.0
         self._gemm_sp(P(ws.aop[j]), s_ao, wpl, wsl, P(ws.hmid[j]), M, D, D, D, bias=w(f"{Lk}.attention.o_proj.bias"),
-                      resid=P(hin), ldr=D)
+                      resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
+        if hd_on:
+            self._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
         wpl, wsl = None, None
         if fusedp:
             L("eav_layernorm_fwd_planes", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"),
@@ -1047,7 +1230,9 @@ class Encoder(nn.Module):
             self._call("eav_sp_convert_gelu", pre, M, FF, FF, s_act, P(ws.actp[j]), None, self._st)
         wpl, wsl = self._wp(f"fc2{i}")
         self._gemm_sp(P(ws.actp[j]), s_act, wpl, wsl, P(hout), M, D, FF, D, bias=w(f"{Lk}.mlp.fc2.bias"),
-                      resid=P(ws.hmid[j]), ldr=D)
+                      resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
+        if hd_on:
+            self._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
 
     def _gemm_f32(self, A, B, C, M, N, K, lda, ldb, ldc, tA=0, tB=0, batch=1, heads=1, sA=(0, 0), sB=(0, 0),
                   sC=(0, 0), alpha=1.0):
@@ -1067,28 +1252,41 @@ class Encoder(nn.Module):
         s_y1, s_qkv, s_ao, s_y2, s_act = (fslot(1 + self.FS * i + k) for k in range(5))
         b_dh2, b_dact, b_dh1, b_dao, b_ds, b_dqkv, b_dy2, b_dy1 = (bslot(1 + self.BS * i + k) for k in range(8))
         fdh = self.fused_dh and self._bwd_three_terms()      # (hi.hi-only gradient products need the tight measured scales)
+        # Hidden dropout: the gradient entering the fc2 / o_proj products is dh o M / (1 - p) (the residual branch keeps dh).
+        # The gate is a pass of its own into ws.dhd; the gated tensor gets its own MEASURED scale slot (s_dh2 / s_dh1) - the
+        # producers' slots hold max|dh| of the ungated tensor, up to 1 / (1 - p) too small.  fused_dh is off on such a step:
+        # the LayerNorm backward's planes (and their a-priori bound) are those of the ungated dh.
+        drop = ws.drop
+        hd_on = drop.ph > 0.0
+        fdh = fdh and not hd_on
+        s_dh2, s_dh1, g_dh = b_dh2, b_dh1, dh
+        if hd_on:
+            dslot = lambda n: ws.dslots.data_ptr() + 4 * self.SLOT * n  # noqa: E731
+            s_dh2, s_dh1, g_dh = dslot(2 * i), dslot(2 * i + 1), P(ws.dhd)
+            self._drop_add(dh, None, g_dh, M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+            L("eav_sp_absmax", g_dh, M, D, D, s_dh2, st)
         # fc2: h_out = h_mid + act.W2^T + b2.  max|dh| is already in b_dh2 (left there by the producer of dh); every
         # conversion pass also yields the bias gradient of its tensor.  (fused_dh: the layer above's LayerNorm backward
         # already wrote these planes and the bias-gradient partials - only the top layer's dh comes from the head)
         if not (fdh and i < c.layers - 1):
-            self._to_planes_bias(dh, M, D, b_dh2, ws.dhp, gp(f"{Lk}.mlp.fc2.bias"))
-        self._wgrad_sp(ws.dhp, b_dh2, ws.actp[i], s_act, gp(f"{Lk}.mlp.fc2.weight"), D, FF, M)
+            self._to_planes_bias(g_dh, M, D, s_dh2, ws.dhp, gp(f"{Lk}.mlp.fc2.bias"))
+        self._wgrad_sp(ws.dhp, s_dh2, ws.actp[i], s_act, gp(f"{Lk}.mlp.fc2.weight"), D, FF, M)
         wpl, wsl = self._wp(f"fc2{i}", transposed=True)
         if self.fused_dact and FF % 8 == 0:
             # data gradient through fc2 and the GELU in one pass, result straight into the planes of dact: its scale comes
             # from |dact| = |(dh W2) gelu'(pre)| <= 1.13 sqrt(D) max|dh| max_j ||W2[:, j]||_2 (max|dh| is in b_dh2, the column
             # norms are refreshed with the weight planes); the epilogue also leaves fc1's bias-gradient partials
-            L("eav_sp_bound_scale", b_dact, b_dh2, self._wplanes["_wcolnorm_fc2"].data_ptr() + 4 * i,
+            L("eav_sp_bound_scale", b_dact, s_dh2, self._wplanes["_wcolnorm_fc2"].data_ptr() + 4 * i,
               1.13 * float(np.sqrt(D)), st)
             self._before_overwrite(ws.dactp)
             part = self._part_buf("part_cs2_pool")
             flags = (1 if self._terms("dgrad") == 1 else 0) | (2 if self._two_streams() else 0)
-            L("eav_gemm_sp_ex", P(ws.dhp), wpl, None, b_dh2, wsl, M, FF, D, FF, 1, 0, 0, 1.0, None, 2, P(ws.pre[i]), None, 0,
+            L("eav_gemm_sp_ex", P(ws.dhp), wpl, None, s_dh2, wsl, M, FF, D, FF, 1, 0, 0, 1.0, None, 2, P(ws.pre[i]), None, 0,
               0, None, P(ws.dactp), b_dact, P(part), flags, st)
             self._reduce_async(part, 0, ws.np_cs2, FF, FF, gp(f"{Lk}.mlp.fc1.bias"))
         else:
             # ... the epilogue multiplies by gelu'(pre) and emits max|dact|; one conversion pass (planes + bias gradient)
-            self._gemm_sp(P(ws.dhp), b_dh2, wpl, wsl, dact, M, FF, D, FF, gelu=2, pre=P(ws.pre[i]), amax=b_dact)
+            self._gemm_sp(P(ws.dhp), s_dh2, wpl, wsl, dact, M, FF, D, FF, gelu=2, pre=P(ws.pre[i]), amax=b_dact)
             self._to_planes_bias(dact, M, FF, b_dact, ws.dactp, gp(f"{Lk}.mlp.fc1.bias"))
         # fc1
         self._wgrad_sp(ws.dactp, b_dact, ws.y2p[i], s_y2, gp(f"{Lk}.mlp.fc1.weight"), FF, D, M)
@@ -1105,11 +1303,14 @@ class Encoder(nn.Module):
               1, P(part), M, D, b_dh1, st)
             self._reduce_ln(part, gp(f"{Lk}.layernorm_after.weight"), gp(f"{Lk}.layernorm_after.bias"))
             # o_proj
-            self._to_planes_bias(dh, M, D, b_dh1, ws.dhp2, gp(f"{Lk}.attention.o_proj.bias"))
-        self._wgrad_sp(ws.dhp2, b_dh1, ws.aop[i], s_ao, gp(f"{Lk}.attention.o_proj.weight"), D, D, M)
+            if hd_on:
+                self._drop_add(dh, None, g_dh, M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+                L("eav_sp_absmax", g_dh, M, D, D, s_dh1, st)
+            self._to_planes_bias(g_dh, M, D, s_dh1, ws.dhp2, gp(f"{Lk}.attention.o_proj.bias"))
+        self._wgrad_sp(ws.dhp2, s_dh1, ws.aop[i], s_ao, gp(f"{Lk}.attention.o_proj.weight"), D, D, M)
         wpl, wsl = self._wp(f"o{i}", transposed=True)
         # (dao goes to the attention operand preparation: one scale per tensor, no row-block maxima needed)
-        self._gemm_sp(P(ws.dhp2), b_dh1, wpl, wsl, dao, M, D, D, D, amax=b_dao if ws.fused else None, blockmax=False)
+        self._gemm_sp(P(ws.dhp2), s_dh1, wpl, wsl, dao, M, D, D, D, amax=b_dao if ws.fused else None, blockmax=False)
         # attention core
         if ws.fused:
             L("eav_attn_sp_prep", dao, b_dao, P(ws.dorow), None, ws.B, N, D, D, 0, st)
@@ -1126,22 +1327,16 @@ class Encoder(nn.Module):
                   None, None, P(ws.lse[i]), P(ws.delta), None, None, P(ws.dqkvp), b_dqkv, P(part), P(ws.aop[i]), s_ao,
                   ws.B, H, N, hd, scale, st)
                 self._reduce_async(part, 0, ws.np_attn, 3 * D, 3 * D, gp(f"{Lk}.attention.q_proj.bias"))
+            elif drop.pa > 0.0:
+                # (fused_dqkv is off on such a step - delta_from_planes is false: fp32 dqkv, the conversion pass measures it)
+                L("eav_attn_bwd_sp_dropout", P(ws.qkvrow[i]), P(ws.dorow), s_qkv, b_dao, b_ds, P(ws.ao[i]), dao,
+                  P(ws.lse[i]), P(ws.delta), dqkv, b_dqkv, ws.B, H, N, hd, scale, drop.pa, self._site_seed(1 + 3 * i),
+                  drop.mk(f"attn.{i}"), drop.cnt, st)
             else:
                 L("eav_attn_bwd_sp", P(ws.qkvrow[i]), None, P(ws.dorow), None, s_qkv, b_dao, b_ds,
                   P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, b_dqkv, ws.B, H, N, hd, scale, st)
         else:
-            qkv = P(ws.qkv[i])
-            ldn = ws.ldn
-            Pm, dP = P(ws.P[i]), P(ws.dP)
-            sP, sQ, sO = (H * N * ldn, N * ldn), (N * 3 * D, hd), (N * D, hd)
-            g = self._gemm_f32
-            g(Pm, dao, dqkv + 8 * D, N, hd, N, ldn, D, 3 * D, tA=1, tB=1, batch=ws.B * H, heads=H, sA=sP, sB=sO, sC=sQ)
-            g(dao, qkv + 8 * D, dP, N, N, hd, D, 3 * D, ldn, batch=ws.B * H, heads=H, sA=sO, sB=sQ, sC=sP)
-            L("eav_softmax_bwd", Pm, dP, ws.B * H * N, N, ldn, st)
-            g(dP, qkv + 4 * D, dqkv, N, hd, N, ldn, 3 * D, 3 * D, tB=1, batch=ws.B * H, heads=H, sA=sP, sB=sQ, sC=sQ,
-              alpha=scale)
-            g(dP, qkv, dqkv + 4 * D, N, hd, N, ldn, 3 * D, 3 * D, tA=1, tB=1, batch=ws.B * H, heads=H, sA=sP, sB=sQ,
-              sC=sQ, alpha=scale)
+            self._attention_backward_scores(self._gemm_f32, i, P(ws.qkv[i]), dao, dqkv, scale)
         # fused q/k/v projection
         if not ws.fused:
             self._call("eav_sp_absmax", dqkv, M, 3 * D, 3 * D, b_dqkv, st)
@@ -1237,6 +1432,9 @@ class Encoder(nn.Module):
             scale = hd ** -0.5
             dh, dy, dao, dact, dqkv = P(ws.dh), P(ws.dy), P(ws.dao), P(ws.dact), P(ws.dqkv)
             sp = ws.sp
+            drop = ws.drop
+            if sp and drop.ph > 0.0:
+                ws.dslots.zero_()
             if sp:
                 ws.bslots.zero_()
                 bslot = lambda n: ws.bslots.data_ptr() + 4 * self.SLOT * n  # noqa: E731
@@ -1255,10 +1453,14 @@ class Encoder(nn.Module):
                         hi = offs[f"{Lk}.mlp.fc2.bias"][0] + offs[f"{Lk}.mlp.fc2.bias"][1]
                         self.grad_ready_hook(lo, hi)
                     continue
-                # fc2: h_out = h_mid + act.W2^T + b2
-                self._wgrad(dh, P(ws.act[i]), gp(f"{Lk}.mlp.fc2.weight"), D, FF, M, D, FF)
-                self._bias_grad(dh, M, D, D, gp(f"{Lk}.mlp.fc2.bias"))
-                self._gemm(dh, w(f"{Lk}.mlp.fc2.weight"), dact, M, FF, D, D, FF, FF, tB=1)
+                # fc2: h_out = h_mid + Dropout(act.W2^T + b2): the products see dh o M / (1 - p), the residual branch dh
+                g_dh = dh
+                if drop.ph > 0.0:
+                    g_dh = P(ws.dhd)
+                    self._drop_add(dh, None, g_dh, M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+                self._wgrad(g_dh, P(ws.act[i]), gp(f"{Lk}.mlp.fc2.weight"), D, FF, M, D, FF)
+                self._bias_grad(g_dh, M, D, D, gp(f"{Lk}.mlp.fc2.bias"))
+                self._gemm(g_dh, w(f"{Lk}.mlp.fc2.weight"), dact, M, FF, D, D, FF, FF, tB=1)
                 L("eav_gelu_bwd", dact, P(ws.pre[i]), M * FF, st)
                 # fc1
                 self._wgrad(dact, P(ws.y2[i]), gp(f"{Lk}.mlp.fc1.weight"), FF, D, M, FF, D)
@@ -1271,25 +1473,20 @@ class Encoder(nn.Module):
                 L("eav_reduce_partials", P(ws.part_ln) + 4 * D, ws.np_ln, 2 * D, D, 1.0,
                   gp(f"{Lk}.layernorm_after.bias"), st)
                 # o_proj
-                self._wgrad(dh, P(ws.ao[i]), gp(f"{Lk}.attention.o_proj.weight"), D, D, M, D, D)
-                self._bias_grad(dh, M, D, D, gp(f"{Lk}.attention.o_proj.bias"))
-                self._gemm(dh, w(f"{Lk}.attention.o_proj.weight"), dao, M, D, D, D, D, D, tB=1)
+                if drop.ph > 0.0:
+                    self._drop_add(dh, None, g_dh, M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+                self._wgrad(g_dh, P(ws.ao[i]), gp(f"{Lk}.attention.o_proj.weight"), D, D, M, D, D)
+                self._bias_grad(g_dh, M, D, D, gp(f"{Lk}.attention.o_proj.bias"))
+                self._gemm(g_dh, w(f"{Lk}.attention.o_proj.weight"), dao, M, D, D, D, D, D, tB=1)
                 # attention core
                 qkv = P(ws.qkv[i])
-                if ws.fused:
+                if ws.fused and drop.pa > 0.0:
+                    L("eav_attn_bwd_dropout", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale,
+                      drop.pa, self._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
+                elif ws.fused:
                     L("eav_attn_bwd", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale, st)
                 else:     # materialised scores, batched over (image, head)
-                    Pm, dP = P(ws.P[i]), P(ws.dP)
-                    sP, sQ, sO = (H * N * ldn, N * ldn), (N * 3 * D, hd), (N * D, hd)
-                    self._gemm(Pm, dao, dqkv + 8 * D, N, hd, N, ldn, D, 3 * D, tA=1, tB=1, batch=B * H, heads=H,
-                               sA=sP, sB=sO, sC=sQ)                                            # dV = P^T dO
-                    self._gemm(dao, qkv + 8 * D, dP, N, N, hd, D, 3 * D, ldn, batch=B * H, heads=H,
-                               sA=sO, sB=sQ, sC=sP)                                            # dP = dO V^T
-                    L("eav_softmax_bwd", Pm, dP, B * H * N, N, ldn, st)
-                    self._gemm(dP, qkv + 4 * D, dqkv, N, hd, N, ldn, 3 * D, 3 * D, tB=1, batch=B * H, heads=H,
-                               sA=sP, sB=sQ, sC=sQ, alpha=scale)                               # dQ = s dS K
-                    self._gemm(dP, qkv, dqkv + 4 * D, N, hd, N, ldn, 3 * D, 3 * D, tA=1, tB=1, batch=B * H, heads=H,
-                               sA=sP, sB=sQ, sC=sQ, alpha=scale)                               # dK = s dS^T Q
+                    self._attention_backward_scores(self._gemm, i, qkv, dao, dqkv, scale)
                 # fused q/k/v projection
                 self._wgrad(dqkv, P(ws.y1[i]), gp(f"{Lk}.attention.q_proj.weight"), 3 * D, D, M, 3 * D, D)
                 self._bias_grad(dqkv, M, 3 * D, 3 * D, gp(f"{Lk}.attention.q_proj.bias"))
@@ -1303,7 +1500,9 @@ class Encoder(nn.Module):
                     lo = offs[f"{Lk}.attention.q_proj.weight"][0]
                     hi = offs[f"{Lk}.mlp.fc2.bias"][0] + offs[f"{Lk}.mlp.fc2.bias"][1]
                     self.grad_ready_hook(lo, hi)
-            # embeddings
+            # embeddings ("emb" dropout: dh is final here, so its gate runs in place)
+            if drop.ph > 0.0:
+                self._drop_add(dh, None, dh, M * D, drop.ph, 0, "emb")
             L("eav_embed_bwd", dh, gp(f"{pre}.embeddings.position_embeddings"), P(ws.demb), B, N, D, c.nextra, st)
             gpos = gflat[offs[f"{pre}.embeddings.position_embeddings"][0]:]
             gflat[offs[f"{pre}.embeddings.cls_token"][0]:][:D].copy_(gpos[:D])

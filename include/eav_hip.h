@@ -461,6 +461,40 @@ int eav_attn_fwd(const float* qkv, float* ao, float* lse, int B, int H, int N, i
  * the forward; delta: scratch [B*H, N]. */
 int eav_attn_bwd(const float* qkv, const float* ao, const float* dout, const float* lse, float* delta, float* dqkv,
                  int B, int H, int N, int head_dim, float scale, void* stream);
+/* The same with attention-probability dropout 0 < drop_p < 1 (HF attention_probs_dropout_prob, training mode): the keep
+ * decision of element (b, h, q, key) is a pure function of (seed + 2 * *seed_dev, ((b H + h) N + q) N + key) - or the
+ * byte of an explicit uint8 keep-mask [B, H, N, N] - so no mask is stored: the backward kernels regenerate it and must
+ * be given the forward's (drop_p, seed, mask, *seed_dev).  ao receives the dropped output (M o P / (1 - p)) V; lse holds
+ * the statistics of the undropped scores. */
+int eav_attn_fwd_dropout(const float* qkv, float* ao, float* lse, int B, int H, int N, int head_dim, float scale,
+                         float drop_p, uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev, void* stream);
+int eav_attn_bwd_dropout(const float* qkv, const float* ao, const float* dout, const float* lse, float* delta,
+                         float* dqkv, int B, int H, int N, int head_dim, float scale, float drop_p, uint64_t seed,
+                         const uint8_t* mask, const uint64_t* seed_dev, void* stream);
+/* Split-operand fused attention with attention-probability dropout (csrc/attention_sp.hip): same mask addressing; fp32
+ * outputs only (ao with max|O| into amax_slot, dqkv with its maximum into amax_slot) - the fused-plane forms, whose
+ * a-priori bounds assume rows of P sum to 1, are not offered with dropout.  rowp / dorow: row planes of qkv / dO
+ * (eav_attn_sp_prep), slot / slot_do their scale slots, slot_ds a zeroed scratch slot. */
+int eav_attn_fwd_sp_dropout(const void* rowp, const float* slot, float* ao, float* lse, float* amax_slot, int B, int H,
+                            int N, int head_dim, float scale, float drop_p, uint64_t seed, const uint8_t* mask,
+                            const uint64_t* seed_dev, void* stream);
+int eav_attn_bwd_sp_dropout(const void* rowp, const void* dorow, const float* slot, const float* slot_do, float* slot_ds,
+                            const float* ao, const float* dout, const float* lse, float* delta, float* dqkv,
+                            float* amax_slot, int B, int H, int N, int head_dim, float scale, float drop_p, uint64_t seed,
+                            const uint8_t* mask, const uint64_t* seed_dev, void* stream);
+/* Encoder dropout sites (emb, attn_out, mlp_out) and the materialised-score attention path (csrc/tf_dropout.hip).
+ * eav_tf_dropout_mask writes the uint8 keep-mask the generator produces for (drop_p, seed, *seed_dev) over n elements.
+ * eav_tf_dropout_add: out = resid + Dropout(y) over n floats (n % 4 == 0; resid NULL: out = Dropout(y), the gate of the
+ * backward; out may be y).  eav_softmax_dropout_fwd: softmax in place over s (kept undropped for the Jacobian) and
+ * pd = M o P / (1 - p) for the P.V product; element (row, c) draws with index row * N + c.  eav_softmax_dropout_bwd:
+ * dS = P o (M o dP / (1 - p) - rowsum) in place over dP, and (pd not NULL) the forward's pd again for dV = pd^T dO. */
+int eav_tf_dropout_mask(uint8_t* mask, int64_t n, float drop_p, uint64_t seed, const uint64_t* seed_dev, void* stream);
+int eav_tf_dropout_add(const float* y, const float* resid, float* out, int64_t n, float drop_p, uint64_t seed,
+                       const uint8_t* mask, const uint64_t* seed_dev, void* stream);
+int eav_softmax_dropout_fwd(float* s, float* pd, int64_t rows, int N, int ld, float drop_p, uint64_t seed,
+                            const uint8_t* mask, const uint64_t* seed_dev, void* stream);
+int eav_softmax_dropout_bwd(const float* P, float* dP, float* pd, int64_t rows, int N, int ld, float drop_p,
+                            uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev, void* stream);
 /* nn.LayerNorm(D, eps) forward over M rows; mean/rstd [M] saved for the backward (may be NULL). */
 int eav_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                       int M, int D, float eps, void* stream);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Step time of the AST / ViT encoders at chosen batch sizes and precision modes (run on the GPU box).
-usage: encoder_step_bench.py ast|vit B [precision]"""
+usage: encoder_step_bench.py ast|vit B [precision]
+env: HIDDEN_DROPOUT / ATTN_DROPOUT (probabilities of the config, default 0), FREEZE, STEPS, SPLIT_TIMES, NO_OVERLAP"""
 import os
 import sys
 import time
@@ -13,7 +14,9 @@ from eav_amd.optim import CrossEntropyLoss, FusedAdam  # noqa: E402
 
 kind, B = sys.argv[1], int(sys.argv[2])
 prec = sys.argv[3] if len(sys.argv) > 3 else "fp32"
-model = T.Encoder(T.make_config(kind)).cuda().train()
+drop = {k: float(os.environ[e]) for k, e in (("hidden_dropout", "HIDDEN_DROPOUT"), ("attention_dropout", "ATTN_DROPOUT"))
+        if os.environ.get(e)}
+model = T.Encoder(T.make_config(kind, **drop)).cuda().train()
 model.precision = prec
 if os.environ.get("NO_OVERLAP"):
     model.overlap_wgrad = False
@@ -64,5 +67,6 @@ if os.environ.get("SPLIT_TIMES"):     # forward / backward / optimiser separatel
         tf += t1 - t0; tb += t2 - t1; to += t3 - t2
     print(f"   forward {tf / n * 1e3:.2f} ms  backward {tb / n * 1e3:.2f} ms  optimiser {to / n * 1e3:.2f} ms")
 gf = {"ast": 783.1, "vit": 105.4}[kind] * B
-print(f"{kind} B={B} {prec}: {dt * 1e3:.1f} ms/step, {B / dt:.1f} samples/s, {gf / dt / 1e3:.1f} TFLOP/s; "
+tag = f" dropout {model.cfg.hidden_dropout:g}/{model.cfg.attention_dropout:g}" if model.dropout_active() else ""
+print(f"{kind} B={B} {prec}{tag}: {dt * 1e3:.1f} ms/step, {B / dt:.1f} samples/s, {gf / dt / 1e3:.1f} TFLOP/s; "
       f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
