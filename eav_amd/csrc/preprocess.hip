@@ -274,3 +274,100 @@ extern "C" int eav_sosfilt_f64(const double* x, double* y, const double* sos, co
   EAV_CHECK_LAUNCH("eav_sosfilt_f64(fixup)");
   return EAV_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Audio resampling (Dataload_audio.py:40-45 -> torchaudio.transforms.Resample, sinc_interp_hann): a polyphase FIR,
+//   y[f*nw + p] = sum_j taps[p][j] * xp[f*orig + j],   xp = x with `width` zeros in front and width + orig behind.
+// Banded form: tap j of phase p sits at t = ((j - width) / orig - p / nw) * base and the design clamps t to
+// +-lowpass_filter_width, where the Hann window is cos(pi/2)^2 ~ 4e-33; width = ceil(lowpass_filter_width * orig / base),
+// so every tap outside j in [jlo_p, jlo_p + 2 width], jlo_p = floor(p * orig / nw), is such a clamped value and is
+// skipped: K = 2 width + 1 taps per output instead of 2 width + orig (35 of 475 for 441 -> 160).
+// A workgroup stages the K-tap bands of all nw phases in LDS once ([nw][K], K odd: lanes on adjacent phases hit
+// distinct banks), then walks tiles of FT frames: the input tile (FT * orig + 2 width samples, the padding made by
+// predicated loads) goes to LDS, and every thread takes one phase of RS_R frames, so a tap read serves RS_R outputs.
+// Adjacent lanes hold adjacent phases of one frame: coalesced stores.  Each output is one thread's fmaf chain in
+// ascending j - no atomics, the same bits on every run.
+namespace {
+
+constexpr int RS_R = 4;                    // frames per thread
+constexpr int RS_LDS_FLOATS = 16384;       // 64 KiB of LDS per workgroup
+constexpr int RS_TILE_FLOATS = 8192;       // input tile cap: leaves room for a second / third workgroup per CU
+
+__global__ __launch_bounds__(256) void resample_sinc_kernel(const float* __restrict__ x, const float* __restrict__ taps,
+                                                            float* __restrict__ y, int64_t n_in, int64_t n_out,
+                                                            int orig, int nw, int width, int ntaps, int FT, int ntiles,
+                                                            int tiles_per_wg) {
+  extern __shared__ float rs_lds[];
+  const int K = 2 * width + 1;
+  float* tl = rs_lds;                      // [nw][K]
+  float* xs = rs_lds + nw * K;             // [FT * orig + 2 width]
+  const int tid = threadIdx.x;
+  const float* xr = x + (int64_t)blockIdx.y * n_in;
+  float* yr = y + (int64_t)blockIdx.y * n_out;
+  for (int i = tid; i < nw * K; i += 256) {
+    const int p = i / K, k = i - p * K;
+    tl[i] = taps[(int64_t)p * ntaps + p * orig / nw + k];      // jlo_p + k <= orig - 1 + 2 width < ntaps
+  }
+  const int XS = FT * orig + 2 * width, G = FT / RS_R, items = nw * G;
+  const int t0 = blockIdx.x * tiles_per_wg, t1 = min(ntiles, t0 + tiles_per_wg);
+  for (int tile = t0; tile < t1; ++tile) {
+    __syncthreads();                       // the previous tile's readers are done
+    const int64_t g0 = (int64_t)tile * FT * orig - width;
+    for (int i = tid; i < XS; i += 256) {
+      const int64_t m = g0 + i;
+      xs[i] = (m >= 0 && m < n_in) ? xr[m] : 0.f;
+    }
+    __syncthreads();
+    for (int it = tid; it < items; it += 256) {
+      const int fg = it / nw, p = it - fg * nw;
+      const float* tp = tl + p * K;
+      const float* xb = xs + fg * orig + p * orig / nw;        // frames fg, fg + G, ...: lane stride orig when nw == 1
+      float acc[RS_R];
+#pragma unroll
+      for (int r = 0; r < RS_R; ++r) acc[r] = 0.f;
+      for (int k = 0; k < K; ++k) {
+        const float t = tp[k];
+#pragma unroll
+        for (int r = 0; r < RS_R; ++r) acc[r] = fmaf(t, xb[r * G * orig + k], acc[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < RS_R; ++r) {
+        const int64_t o = ((int64_t)tile * FT + r * G + fg) * nw + p;
+        if (o < n_out) yr[o] = acc[r];
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int eav_resample_sinc_f32(const float* x, const float* taps, float* y, int rows, int64_t n_in, int64_t n_out,
+                                     int orig, int nw, int width, int ntaps, void* stream) {
+  EAV_REQUIRE(x && taps && y, "eav_resample_sinc_f32: null pointer");
+  EAV_REQUIRE(rows > 0 && rows <= 65535 && n_in > 0 && n_out > 0 && orig > 0 && nw > 0 && width > 0 && ntaps > 0,
+              "eav_resample_sinc_f32: sizes must be positive (rows <= 65535)");
+  EAV_REQUIRE(orig <= RS_LDS_FLOATS && nw <= RS_LDS_FLOATS && width <= RS_LDS_FLOATS,
+              "eav_resample_sinc_f32: orig %d / new %d / width %d beyond the LDS tile", orig, nw, width);
+  EAV_REQUIRE(ntaps == 2 * width + orig, "eav_resample_sinc_f32: ntaps %d != 2 * width + orig = %d", ntaps,
+              2 * width + orig);
+  EAV_REQUIRE(n_in <= (INT64_MAX - orig) / nw && n_out == ((int64_t)nw * n_in + orig - 1) / orig,
+              "eav_resample_sinc_f32: n_out %lld is not ceil(new * n_in / orig) for n_in %lld", (long long)n_out,
+              (long long)n_in);
+  const int K = 2 * width + 1;
+  const int64_t room = (int64_t)RS_LDS_FLOATS - (int64_t)nw * K - 2 * width;      // floats left for FT * orig
+  const int64_t cap = room < RS_TILE_FLOATS ? room : RS_TILE_FLOATS;
+  const int FT = cap < orig ? 0 : (int)(cap / orig) / RS_R * RS_R;
+  if (FT < RS_R)
+    return eav_set_error(EAV_EUNSUPPORTED, "eav_resample_sinc_f32: the bands of %d phases x %d taps and %d frames of %d "
+                         "samples exceed 64 KiB of LDS (reduce the rates by their gcd)", nw, K, RS_R, orig);
+  const int64_t nframes = cdiv64(n_out, nw), ntiles = cdiv64(nframes, FT);
+  EAV_REQUIRE(ntiles <= INT32_MAX, "eav_resample_sinc_f32: %lld tiles", (long long)ntiles);
+  int64_t tpw = ntiles * rows / 2048;                                              // ~2048 workgroups share the tap staging
+  tpw = tpw < 1 ? 1 : (tpw > 16 ? 16 : tpw);
+  const size_t lds = ((size_t)nw * K + (size_t)FT * orig + 2 * width) * sizeof(float);
+  dim3 grid((unsigned)cdiv64(ntiles, tpw), rows);
+  hipLaunchKernelGGL(resample_sinc_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, taps, y, n_in, n_out, orig, nw,
+                     width, ntaps, FT, (int)ntiles, (int)tpw);
+  EAV_CHECK_LAUNCH("eav_resample_sinc_f32");
+  return EAV_OK;
+}

@@ -5,8 +5,15 @@ through the HF image processor (Transformer_Vision.py:52-59) - Pillow's 8-bit bi
 rescale, (x-mean)/std - for a whole batch of uint8 HWC frames in one kernel launch
 (`eav_resize_normalize_u8`).  The coefficient tables follow Pillow's precompute_coeffs /
 normalize_coeffs_8bpc (src/libImaging/Resample.c) so that the result is bit-identical to the host path.
+
+waveforms_to_input_values: the AST log-mel front-end (`eav_ast_fbank`).
+
+resample_waveforms: torchaudio.transforms.Resample (sinc_interp_hann) for a batch of waveforms in one launch
+(`eav_resample_sinc_f32`); sinc_resample_design is the host-side filter design in torchaudio's published arithmetic.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -102,3 +109,67 @@ def waveforms_to_input_values(wav, max_length=1024, nmel=128, mean=-4.2677393, s
               max_length, nmel, 0.97, 1.192092955078125e-07, float(np.float32(mean)), float(np.float32(std * 2)),
               _lib.stream_ptr())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+def sinc_resample_design(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """torchaudio's sinc_interp_hann resampling kernel (_get_sinc_resample_kernel, dtype=None), computed in float64 and
+    stored as float32: (taps float32 [new, 2*width + orig], width, orig, new) with the rates reduced by their gcd.
+    y[f*new + p] = sum_j taps[p, j] * xp[f*orig + j], xp = x padded by `width` zeros in front and width + orig behind."""
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq <= 0 or new_freq <= 0 or lowpass_filter_width <= 0:
+        raise ValueError("rates and lowpass_filter_width must be positive")
+    g = math.gcd(orig_freq, new_freq)
+    orig, new = orig_freq // g, new_freq // g
+    base = min(orig, new) * rolloff
+    width = int(math.ceil(lowpass_filter_width * orig / base))
+    idx = np.arange(-width, width + orig, dtype=np.float64)[None, :] / orig
+    t = (np.arange(0, -new, -1, dtype=np.float64)[:, None] / new + idx) * base
+    t = np.clip(t, -lowpass_filter_width, lowpass_filter_width)
+    window = np.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t *= math.pi
+    sinc = np.where(t == 0, 1.0, np.sin(t) / np.where(t == 0, 1.0, t))
+    taps = sinc * window * (base / orig)
+    return np.ascontiguousarray(taps, dtype=np.float32), width, orig, new
+
+
+def resampled_length(length, orig, new):
+    """ceil(new * length / orig): the number of outputs torchaudio keeps."""
+    return -((-int(new) * int(length)) // int(orig))
+
+
+_RESAMPLE_TAPS = {}
+
+
+def resample_waveforms(wav, orig_freq, new_freq, lengths=None, device="cuda"):
+    """torchaudio.transforms.Resample(orig_freq, new_freq) of wav [rows, n] (or [n]) -> float32 device tensor [rows, n_out],
+    n_out = ceil(new * n / orig), every row in one launch.  Rows of different lengths come zero-padded to the longest;
+    with `lengths` (valid samples per row) the per-row output lengths (int64 array) are returned too and the caller keeps
+    y[i, :out_lengths[i]] - exact, since torchaudio's own padding is zeros.  Equal rates return the input unchanged."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.EavError("resample_waveforms runs on the MI355X only (no CPU fallback)")
+    w = torch.as_tensor(np.asarray(wav, dtype=np.float32) if not isinstance(wav, torch.Tensor) else wav).float()
+    if w.dim() == 1:
+        w = w[None]
+    if w.dim() != 2 or w.shape[1] == 0:
+        raise ValueError("wav must be [rows, n] with n > 0")
+    w = w.to(dev).contiguous()
+    rows, n = w.shape
+    g = math.gcd(int(orig_freq), int(new_freq))
+    orig, new = int(orig_freq) // g, int(new_freq) // g
+    if orig == new:
+        y = w
+    else:
+        key = (orig, new, str(dev))
+        if key not in _RESAMPLE_TAPS:                    # the table stays alive for every later launch
+            taps, width, _, _ = sinc_resample_design(orig, new)
+            _RESAMPLE_TAPS[key] = (torch.from_numpy(taps).to(dev), width)
+        taps, width = _RESAMPLE_TAPS[key]
+        n_out = resampled_length(n, orig, new)
+        y = torch.empty(rows, n_out, dtype=torch.float32, device=dev)
+        _lib.call("eav_resample_sinc_f32", w.data_ptr(), taps.data_ptr(), y.data_ptr(), rows, n, n_out, orig, new, width,
+                  taps.shape[1], _lib.stream_ptr())
+    if lengths is None:
+        return y
+    return y, np.array([resampled_length(v, orig, new) for v in lengths], dtype=np.int64)

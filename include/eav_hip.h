@@ -591,6 +591,15 @@ int eav_decimate_fir_f64(const double* x, const double* h, double* y, int nch, i
 int eav_sosfilt_f64(const double* x, double* y, const double* sos, const double* H, const double* AL, double* zend,
                     double* zstart, int nch, int64_t n, int nsec, int Lc, void* stream);
 
+/* Audio resampling, torchaudio.transforms.Resample (sinc_interp_hann; Dataload_audio.py:40-45): x [rows][n_in] fp32 ->
+ * y [rows][n_out], n_out = ceil(nw * n_in / orig), y[f*nw + p] = sum_j taps[p][j] xp[f*orig + j] with xp = x padded by
+ * `width` zeros in front and width + orig behind (the padding is implicit).  taps [nw][ntaps = 2 width + orig] fp32 is
+ * the DEVICE table of eav_amd.preprocess.sinc_resample_design; taps the design clamps to the window's edge (~1e-33)
+ * are skipped.  Rows of different lengths: zero-pad to the longest and drop each row's outputs beyond its own
+ * ceil(nw * L / orig).  Fixed accumulation order (no atomics). */
+int eav_resample_sinc_f32(const float* x, const float* taps, float* y, int rows, int64_t n_in, int64_t n_out, int orig,
+                          int nw, int width, int ntaps, void* stream);
+
 /* ---- audio CNN (CNN_torch/CNN_audio.py AudioModel; csrc/audio_cnn.hip) -------------------------------------------
  * Every conv of the model is Conv1d(kernel 5, padding 2) with a bias; tensors are [B][channels][length] fp32.
  * Forward: out = ReLU(conv(in) + bias), then (drop_p > 0) dropout - mask (uint8 [B][N][Lin], may be NULL) or the

@@ -3,6 +3,7 @@
 
     python tools/run_finetune_subjects.py audio  [--subjects 42] [--frozen-epochs 10] [--unfrozen-epochs 15]
     python tools/run_finetune_subjects.py vision [--subjects 42] [--frozen-epochs 10] [--unfrozen-epochs 5]
+    python tools/run_finetune_subjects.py audio --audio-root Datasets/EAV      (the dataset folder, Dataload_audio.py:87-93)
     python -m torch.distributed.run --nproc-per-node 8 tools/run_finetune_subjects.py audio ...
 
 Every subject is one `AudioModelTrainer` / `ImageClassifierTrainer` run with the reference's hyper-parameters
@@ -12,7 +13,9 @@ eav_amd.dist.SubjectSchedule places them: whole rounds one subject per rank with
 ranks - every member holds a replica, every n-th training item and 1 / n of the batch size, gradients all-reduced inside the
 group (the reference's nn.DataParallel wrap, Transformer_Audio.py:59-60 / Transformer_Vision.py:82-83).  At the end ONE
 all_gather of `outputs_test` (SURVEY 8e level 1); vision adds the trial vote + weighted F1 of Transformer_Vision.py:174-185.
-With real data, replace `synthetic_subject` by the pickles the reference drivers read.  The model directory is an HF-format
+`--audio-root DIR` (audio only) loads every subject from DIR/subjectNN/Audio instead: eav_amd.audio_data.DataLoadAudio
+(WAV files, resampled to 16 kHz on the GPU, 5 s clips) and EAVDataSplit(...).get_split(h_idx=56), as the reference driver
+does.  For vision, replace `synthetic_subject` by the pickles the reference driver reads.  The model directory is an HF-format
 directory (`--model-path`); without one a random-init full-size model is written to a temporary directory.
 """
 import argparse
@@ -45,6 +48,14 @@ def synthetic_subject(kind, sub, small):
     return [fr[:ntri], y[:ntri], fr[ntri:], y[ntri:]]
 
 
+def audio_subject(root, sub):
+    """Dataload_audio.py:87-93: one subject's WAV folder -> [tr_x, tr_y, te_x, te_y]."""
+    from eav_amd.audio_data import DataLoadAudio
+    from eav_amd.datasplit import EAVDataSplit
+    x, y = DataLoadAudio(subject=sub, parent_directory=root).process()
+    return list(EAVDataSplit(x, y).get_split(h_idx=56))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("kind", choices=("audio", "vision"))
@@ -53,6 +64,7 @@ def main():
     ap.add_argument("--unfrozen-epochs", type=int, default=None)
     ap.add_argument("--model-path", default=None)
     ap.add_argument("--small", action="store_true", help="tiny synthetic subjects (logic check)")
+    ap.add_argument("--audio-root", default=None, help="audio only: dataset folder holding subjectNN/Audio/*.wav")
     ap.add_argument("--no-hybrid", action="store_true", help="plain round-robin: the remainder one subject per rank")
     ap.add_argument("--backend", default=os.environ.get("EAV_DIST_BACKEND"))
     ap.add_argument("--verbose", action="store_true")
@@ -80,7 +92,10 @@ def main():
         mine = sched.group_of(rank)
         plan = [(s, None) for s in sched.solo[rank]] + ([mine] if mine else [])
         for sub, ranks in plan:
-            data = synthetic_subject(args.kind, sub, args.small)
+            if audio and args.audio_root:
+                data = audio_subject(os.path.join(cwd, args.audio_root), sub)
+            else:
+                data = synthetic_subject(args.kind, sub, args.small)
             n = len(ranks) if ranks else 1
             # this rank's replica sees every n-th training item: equal shard lengths and batch sizes on every member,
             # hence equal step counts (eav_amd.dist.replica_shard)
