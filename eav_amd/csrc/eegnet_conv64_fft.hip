@@ -29,6 +29,7 @@ namespace {
 
 constexpr int NCH = 64, KT = 16, NB = 64, LV = NB - KT + 1;      // 49 valid outputs per 64-sample block
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
 constexpr float C64[50] = {1.0f, 0.995184727f, 0.98078528f, 0.956940336f, 0.923879533f, 0.881921264f, 0.831469612f, 0.773010453f, 0.707106781f, 0.634393284f, 0.555570233f, 0.471396737f, 0.382683432f, 0.290284677f, 0.195090322f, 0.0980171403f, 0.0f, -0.0980171403f, -0.195090322f, -0.290284677f, -0.382683432f, -0.471396737f, -0.555570233f, -0.634393284f, -0.707106781f, -0.773010453f, -0.831469612f, -0.881921264f, -0.923879533f, -0.956940336f, -0.98078528f, -0.995184727f, -1.0f, -0.995184727f, -0.98078528f, -0.956940336f, -0.923879533f, -0.881921264f, -0.831469612f, -0.773010453f, -0.707106781f, -0.634393284f, -0.555570233f, -0.471396737f, -0.382683432f, -0.290284677f, -0.195090322f, -0.0980171403f, 0.0f, 0.0980171403f};
 constexpr float S64[50] = {0.0f, 0.0980171403f, 0.195090322f, 0.290284677f, 0.382683432f, 0.471396737f, 0.555570233f, 0.634393284f, 0.707106781f, 0.773010453f, 0.831469612f, 0.881921264f, 0.923879533f, 0.956940336f, 0.98078528f, 0.995184727f, 1.0f, 0.995184727f, 0.98078528f, 0.956940336f, 0.923879533f, 0.881921264f, 0.831469612f, 0.773010453f, 0.707106781f, 0.634393284f, 0.555570233f, 0.471396737f, 0.382683432f, 0.290284677f, 0.195090322f, 0.0980171403f, 0.0f, -0.0980171403f, -0.195090322f, -0.290284677f, -0.382683432f, -0.471396737f, -0.555570233f, -0.634393284f, -0.707106781f, -0.773010453f, -0.831469612f, -0.881921264f, -0.923879533f, -0.956940336f, -0.98078528f, -0.995184727f, -1.0f, -0.995184727f};
 
@@ -77,8 +78,8 @@ __device__ __forceinline__ void fft64(v2f (&x)[64]) {
 }
 
 struct Geo {
-  int B, T, padl, nblk, npair, ncol, ncolp;      // ncolp = columns rounded up to 128: whole 32-column GEMM tiles and 8 equal
-                                                 // weight-gradient chunks of a multiple of 16 columns; columns >= ncol are ZERO
+  int B, T, padl, nblk, npair, ncol, ncolp;      // ncolp = columns rounded up to 128: whole 32-column GEMM tiles and 4 equal
+                                                 // weight-gradient chunks of whole 32-column K-blocks; columns >= ncol are ZERO
 };
 
 Geo geometry(int B, int T, int padl) {
@@ -183,85 +184,96 @@ __global__ __launch_bounds__(256) void c64_pack_fft_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------- per-bin GEMM
-// C[bin][col][n] = sum_k Z[bin][col][k] BmT[bin][k][n], n, k in [0,128).  grid (wgs per bin, 64 bins), 4 waves; wave w owns
-// outputs [32 w, 32 w + 32): its Bm rows stay in 64 VGPRs (B operand of v_mfma_f32_32x32x2_f32: lane = (k & 1, n)).  Column
-// tiles of 32 are staged into LDS (row stride 129: the A-operand reads hit 32 banks), next tile prefetched in registers.
+// C[bin][col][n] = sum_k Z[bin][col][k] BmT[bin][k][n], n, k in [0,128).  grid (64 bins, GEMM_GW workgroups per bin) - the
+// bin is blockIdx.x: consecutive workgroup ids go to consecutive XCDs, so the workgroups of a bin share one XCD's L2 and the
+// bin's 64 KiB of filter spectra cross the fabric once, not once per workgroup (33 MB per launch, all of it in front of the
+// first MFMA).  4 waves; wave w owns outputs [32 w, 32 w + 32): its Bm rows stay in 64 VGPRs (B operand of
+// v_mfma_f32_32x32x2_f32: lane = (k & 1, n)).  Column tiles of 32 go global -> registers -> LDS (row stride 129: the
+// A-operand reads AND the commit's writes hit 32 banks), one tile ahead of the MFMAs.  A tile of a wave: the fetch of tile
+// t + 1, 64 MFMAs with their A operands read GEMM_AW MFMAs ahead (a rolling window of ds_reads, waited for by count), the
+// 16 stores - which nothing in the loop waits for: they drain under the next tile's MFMAs -, the commit of tile t + 1.
+// The waves of one workgroup meet at one barrier per tile; the other workgroup of the CU issues meanwhile.
+// The contraction order per output is k = 0 .. 127: bit for bit the k-ordered fmaf chain.
 constexpr int XS = 129;
 
-#ifndef C64V_WPE        // A/B builds: minimum waves per SIMD asked of the register allocator for the per-bin GEMM (0 = none)
-#define C64V_WPE 0
+#ifndef C64V_GW         // tuning builds: workgroups per bin of the per-bin GEMM (profiles/c64_gemm_before_after.txt)
+#define C64V_GW 8
 #endif
-__global__ __launch_bounds__(256, C64V_WPE) void c64_bin_gemm_kernel(const float* __restrict__ Z, const float* __restrict__ Bm,
-                                                           float* __restrict__ C, int ncolp) {
+constexpr int GEMM_GW = C64V_GW, GEMM_AW = 8;
+
+__global__ __launch_bounds__(256, 4) void c64_bin_gemm_kernel(const float* __restrict__ Z, const float* __restrict__ Bm,
+                                                              float* __restrict__ C, int ncolp) {
   __shared__ float xs[2][32 * XS];
-  const int bin = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int bin = blockIdx.x, step = gridDim.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 31, kk = lane >> 5;
+  const int ntiles = ncolp >> 5;
+  // the walk starts at a tile that rotates with the bin: the workgroups that get one tile more than the others are not
+  // the same blockIdx.y in every bin
+  int tile = (blockIdx.y + bin) % step;
+  const float* zb = Z + (int64_t)bin * ncolp * 128;
+  float* cb = C + (int64_t)bin * ncolp * 128;
+  // staging: thread -> column threadIdx.x >> 3, float4 pieces (threadIdx.x & 7) + 8 i: 128-byte runs in global memory, and
+  // the 32 lanes of a half-wave write banks (4 g + (l >> 3) + 4 (l & 7) + j) mod 32 - all different
+  const int scol = threadIdx.x >> 3, sk4 = threadIdx.x & 7;
+  float4 pre[4];
+  auto fetch = [&](int t) {
+    const float4* src = reinterpret_cast<const float4*>(zb + ((int64_t)t * 32 + scol) * 128) + sk4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pre[i] = src[8 * i];
+  };
+  auto commit = [&](int buf) {
+    float* d = xs[buf] + scol * XS + 4 * sk4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      d[32 * i] = pre[i].x; d[32 * i + 1] = pre[i].y; d[32 * i + 2] = pre[i].z; d[32 * i + 3] = pre[i].w;
+    }
+  };
+  if (tile < ntiles) fetch(tile);
   float wreg[64];
   {
     const float* bp = Bm + ((int64_t)bin * 128 + kk) * 128 + 32 * wave + n;      // BmT[bin][k][n]: 128-byte rows per half-wave
 #pragma unroll
     for (int ks = 0; ks < 64; ++ks) wreg[ks] = bp[(int64_t)2 * ks * 128];
   }
-  const int ntiles = ncolp >> 5;
-  const float* zb = Z + (int64_t)bin * ncolp * 128;
-  float* cb = C + (int64_t)bin * ncolp * 128;
-  float4 pre[4];
-  auto fetch = [&](int tile) {
-    const float4* src = reinterpret_cast<const float4*>(zb + (int64_t)tile * 32 * 128);
+  if (tile < ntiles) commit(0);
+  // the weights are complete HERE: left to the first use, hipcc's waits for them (vmcnt counts loads and stores in one
+  // queue) stay in the tile loop, where they wait for the previous tile's stores in front of the fifth MFMA
 #pragma unroll
-    for (int i = 0; i < 4; ++i) pre[i] = src[threadIdx.x + 256 * i];
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx4 = threadIdx.x + 256 * i, col = idx4 >> 5, k4 = idx4 & 31;
-      float* d = xs[buf] + col * XS + 4 * k4;
-      d[0] = pre[i].x; d[1] = pre[i].y; d[2] = pre[i].z; d[3] = pre[i].w;
-    }
-  };
-  int tile = blockIdx.x, buf = 0;
-  if (tile < ntiles) {
-    fetch(tile);
-    commit(0);
-  }
+  for (int ks = 0; ks < 64; ++ks) asm volatile("" : "+v"(wreg[ks]));
   __syncthreads();
-  for (; tile < ntiles; tile += gridDim.x) {
-    const int nxt = tile + gridDim.x;
-#ifndef C64V_ABL_NOFETCH
+  for (int buf = 0; tile < ntiles; tile += step, buf ^= 1) {
+    const int nxt = tile + step;
     if (nxt < ntiles) fetch(nxt);
-#endif
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // the tile's 64 A operands are read before the first MFMA (left to itself hipcc reads them pairwise just in time:
-    // an LDS round trip in front of every second MFMA)
     const float* ap = xs[buf] + n * XS + kk;
     float av[64];
 #pragma unroll
-#ifdef C64V_ABL_NOLDS
-    for (int ks = 0; ks < 64; ++ks) av[ks] = 1.0f + ks;
-#else
-    for (int ks = 0; ks < 64; ++ks) av[ks] = ap[2 * ks];
-#endif
-    __builtin_amdgcn_sched_barrier(0);            // (the scheduler otherwise sinks the reads back between the MFMAs)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    for (int ks = 0; ks < GEMM_AW; ++ks) av[ks] = ap[2 * ks];
 #pragma unroll
-    for (int ks = 0; ks < 64; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks], wreg[ks], acc, 0, 0, 0);
+    for (int ks = 0; ks < 64; ++ks) {
+      if (ks + GEMM_AW < 64) av[ks + GEMM_AW] = ap[2 * (ks + GEMM_AW)];
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks], wreg[ks], acc, 0, 0, 0);
+    }
+    // the order asked of the scheduler (hipcc pairs the reads into ds_read2_b32): the window first, then one read per two
+    // MFMAs; left alone it reads each pair just in time, an LDS round trip in front of every second MFMA
+    __builtin_amdgcn_sched_group_barrier(0x100, GEMM_AW / 2, 0);
+#pragma unroll
+    for (int i = 0; i < 32 - GEMM_AW / 2; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, GEMM_AW, 0);
     // D[m = column][n = output]: lane holds output n, registers = columns (r & 3) + 8 (r >> 2) + 4 kk
     float* dst = cb + ((int64_t)tile * 32) * 128 + 32 * wave + n;
-#ifdef C64V_ABL_NOSTORE      // (timing-only ablation)
-    if (acc[0] == 12345.f)
-#endif
 #pragma unroll
     for (int r = 0; r < 16; ++r) dst[(int64_t)((r & 3) + 8 * (r >> 2) + 4 * kk) * 128] = acc[r];
-#ifndef C64V_ABL_NOFETCH
-    if (nxt < ntiles) commit(buf ^ 1);
-#endif
+    if (nxt < ntiles) commit(buf ^ 1);        // (waits for the fetch, issued before the stores: not for the stores)
     // raw barrier: __syncthreads() would also wait for this tile's 16 global stores per lane (vmcnt(0)) at every tile
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    buf ^= 1;
   }
 }
 
@@ -320,57 +332,108 @@ __global__ __launch_bounds__(256) void c64_ifft_unpack_kernel(const float* __res
 // zero-padded 49-sample blocks of du (two blocks per column: real + imaginary), Z = the forward's input spectra.  Per bin
 // one real [128 x cols]^T [cols x 128] product P[a][b] = sum_col D[col][a] Z[col][b] (a = (re|im, o), b = (re|im, i)):
 //   Re Acc[o][i] = P[(re,o)][(re,i)] + P[(im,o)][(im,i)],   Im Acc[o][i] = P[(re,o)][(im,i)] - P[(im,o)][(re,i)].
-// c64_bin_wgemm_kernel: grid (column chunks, 64 bins), 4 waves; wave w = rows a in [32 w, 32 w + 32), all 128 columns b
-// (four 32 x 32 accumulators); both operands are read straight from global memory - for a fixed column the 32 lanes of a
-// half-wave read 128 consecutive bytes - eight K-steps ahead; the chunk's partial product goes to Pp[chunk][bin].
+// c64_bin_wgemm_kernel: grid (column chunks, 64 bins), 4 waves, one workgroup per CU; wave w = rows a in [32 w, 32 w + 32),
+// all 128 columns b (four 32 x 32 accumulators).  The D and Z slabs of a K-block of WKB columns (2 x 16 KiB, contiguous
+// in global memory) are staged ONCE per workgroup by LDS-DMA (global_load_lds_dwordx4: no VGPR round trip, no ds_write)
+// into a ring of WNST stages; for a fixed column the 32 lanes of a half-wave read 128 consecutive bytes of LDS.  Block
+// kb + WNST - 1 is issued when block kb starts and is waited for when block kb + 1 ends: WNST - 2 blocks of MFMAs
+// (2 x 4096 cycles) cover its latency.  Blocks kb and kb + 1 are both readable during block kb, so the operand reads run
+// WAW K-steps ahead of the MFMAs across the block boundary; one barrier per K-block.  The columns of a chunk are
+// contracted in ascending order and the chunk's partial product goes to Pp[chunk][bin]: the bits of a k-ordered fmaf chain.
 // c64_wfinish_kernel: lane = i, workgroup = o: sums the chunks in order, forms Acc, inverse FFT over the bins, taps 0..15.
-#ifndef C64V_WCH
-#define C64V_WCH 4
-#endif
-#ifndef C64V_PF
-#define C64V_PF 8
-#endif
-#ifndef C64V_GW
-#define C64V_GW 8
-#endif
-constexpr int WCH = C64V_WCH;      // column chunks (split-K) of the weight-gradient GEMM
+constexpr int WCH = 4;             // column chunks (split-K) of the weight-gradient GEMM
+constexpr int WKB = 32;            // columns per K-block: geometry() pads the columns to 128 = WCH x WKB
+constexpr int WNST = 4;            // ring stages of [D slab | Z slab], 32 KiB each
+constexpr int WAW = 4;             // K-steps (2 columns each) the operand reads run ahead
+constexpr int WSTAGE = 2 * WKB * 128 * 4, WDMA = WSTAGE / 1024 / 4;      // bytes per stage, LDS-DMA instructions per wave and stage
+
+template <int N>
+__device__ __forceinline__ void wait_dma() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 __global__ __launch_bounds__(256) void c64_bin_wgemm_kernel(const float* __restrict__ D, const float* __restrict__ Z,
                                                             float* __restrict__ Pp, int ncolp, int cpc) {
-  const int bin = blockIdx.y, chunk = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[WNST * WSTAGE];
+  const int bin = blockIdx.y, chunk = blockIdx.x, lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = lane & 31, kk = lane >> 5;
-  const int c0 = chunk * cpc;                  // cpc: a multiple of 16 columns, all inside the zero-padded buffers
+  const int nkb = cpc / WKB;                   // cpc: a multiple of WKB columns, all inside the zero-padded buffers
   f32x16 acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  const float* dp = D + ((int64_t)bin * ncolp + c0 + kk) * 128 + 32 * wave + n;
-  const float* zp = Z + ((int64_t)bin * ncolp + c0 + kk) * 128 + n;
-  const int nks = cpc >> 1;                    // K-steps of 2 columns: a multiple of PF
-  constexpr int PF = C64V_PF;
-  float ra[PF], rb[PF][4];
+  // ---- staging: the stage image is [D rows of the block | Z rows of the block], 1 KiB pieces; wave w copies pieces
+  // 8 w .. 8 w + 7 (waves 0, 1 the D slab, waves 2, 3 the Z slab), lane l the 16 bytes at 16 l of a piece
+  const int64_t slab0 = ((int64_t)bin * ncolp + (int64_t)chunk * cpc) * 128;
+  const float* src0 = (wave < 2 ? D : Z) + slab0 + (wave & 1) * (WDMA * 256);
+  const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)smem;
+  const unsigned voff = lane * 16;
+  // (the LDS-DMA is issued from inline asm and counted by hand: see gemm_sp.hip; m0 is written in the statement that uses it)
+  auto issue = [&](int kb) {
+    const float* sb = src0 + (int64_t)kb * (WKB * 128);
+    const unsigned dst = lds0 + (kb % WNST) * WSTAGE + wave * (WDMA * 1024);
 #pragma unroll
-  for (int p = 0; p < PF; ++p) {
-    ra[p] = dp[(int64_t)p * 256];
+    for (int i = 0; i < WDMA; ++i)
+      asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sb + i * 256), "s"(dst + i * 1024)
+                   : "memory");
+  };
+  // ---- operands of K-step s (columns 2 s + kk) of a stage: A = D[col][32 wave + n], B_j = Z[col][32 j + n]
+  const float* lds = reinterpret_cast<const float*>(smem);
+  const int aoff = kk * 128 + 32 * wave + n, boff = WKB * 128 + kk * 128 + n;
+  float ra[WAW], rb[WAW][4];
+  auto read_step = [&](int slot, const float* stg, int s) {
+    ra[slot] = stg[aoff + s * 256];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) rb[p][j] = zp[(int64_t)p * 256 + 32 * j];
-  }
-  for (int ks0 = 0; ks0 < nks; ks0 += PF) {
+    for (int j = 0; j < 4; ++j) rb[slot][j] = stg[boff + s * 256 + 32 * j];
+  };
 #pragma unroll
-    for (int p = 0; p < PF; ++p) {
-      const float a = ra[p];
-      const float b0 = rb[p][0], b1 = rb[p][1], b2 = rb[p][2], b3 = rb[p][3];
-      // unconditional reload, clamped to the chunk's last K-step (a branch here made hipcc copy the whole register window)
-#ifndef C64V_ABL_NOLOAD      // (timing-only ablation: the MFMA side alone)
-      const int64_t o = (int64_t)min(ks0 + PF + p, nks - 1) * 256;
-      ra[p] = dp[o];
-      rb[p][0] = zp[o]; rb[p][1] = zp[o + 32]; rb[p][2] = zp[o + 64]; rb[p][3] = zp[o + 96];
-#endif
+  for (int kb = 0; kb < WNST - 1; ++kb)
+    if (kb < nkb) issue(kb);
+  // block 0 landed (a wave's DMA completes in order: all but the WDMA instructions of each younger block)
+  if (nkb >= 3) wait_dma<2 * WDMA>();
+  else if (nkb == 2) wait_dma<WDMA>();
+  else wait_dma<0>();
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int s = 0; s < WAW; ++s) read_step(s, lds, s);
+  constexpr int NS = WKB / 2;                  // K-steps per block
+  for (int kb = 0; kb < nkb; ++kb) {
+    // block kb + 1 landed: this wave's part by count, the other waves' by the barrier - which also says that every wave
+    // has left block kb - 1, whose stage takes block kb + WNST - 1
+    if (kb + 2 < nkb) wait_dma<WDMA>();
+    else wait_dma<0>();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");             // (no operand read of block kb + 1 above the barrier)
+    if (kb + WNST - 1 < nkb) issue(kb + WNST - 1);
+    const float* cur = lds + (kb % WNST) * (WSTAGE / 4);
+    const float* nx = lds + ((kb + 1) % WNST) * (WSTAGE / 4);      // (past the last block: reads of a stale stage, never used)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int slot = s % WAW;
+      const float a = ra[slot];
+      const float b0 = rb[slot][0], b1 = rb[slot][1], b2 = rb[slot][2], b3 = rb[slot][3];
+      if (s + WAW < NS) read_step(slot, cur, s + WAW);
+      else read_step(slot, nx, s + WAW - NS);
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b2, acc[2], 0, 0, 0);
       acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b3, acc[3], 0, 0, 0);
+    }
+    // the order asked of the scheduler: the reads stay WAW K-steps ahead, spread between the MFMAs (hipcc pairs them: 5
+    // ds_read2 per two K-steps); left alone it sinks every read to just in front of the MFMA that uses it
+#pragma unroll
+    for (int i = 0; i < NS / 2; ++i) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
     }
   }
   // D-layout: lane holds column b = 32 j + n, rows a = 32 wave + (r & 3) + 8 (r >> 2) + 4 kk
@@ -446,7 +509,7 @@ extern "C" int eav_conv64_fft_fwd(const float* in, const float* w, float* out, f
   }
   hipLaunchKernelGGL(c64_pack_fft_kernel, dim3(pack_grid(g)), dim3(256), 0, st, in, Z, g, 0);
   EAV_CHECK_LAUNCH("eav_conv64_fft_fwd(fft)");
-  hipLaunchKernelGGL(c64_bin_gemm_kernel, dim3(std::min(C64V_GW, g.ncolp / 32), 64), dim3(256), 0, st, Z, Bm, Y, g.ncolp);
+  hipLaunchKernelGGL(c64_bin_gemm_kernel, dim3(64, std::min(GEMM_GW, g.ncolp / 32)), dim3(256), 0, st, Z, Bm, Y, g.ncolp);
   EAV_CHECK_LAUNCH("eav_conv64_fft_fwd(gemm)");
   hipLaunchKernelGGL(c64_ifft_unpack_kernel, dim3(pack_grid(g)), dim3(256), 0, st, Y, out, stat_part, g);
   EAV_CHECK_LAUNCH("eav_conv64_fft_fwd(ifft)");
@@ -466,7 +529,8 @@ extern "C" int eav_conv64_fft_wgrad(const float* du, float* dW, float* ws, int B
   float* Acc = Pp + (int64_t)WCH * 64 * 128 * 128;
   hipLaunchKernelGGL(c64_pack_fft_kernel, dim3(pack_grid(g)), dim3(256), 0, st, du, D, g, 1);
   EAV_CHECK_LAUNCH("eav_conv64_fft_wgrad(fft)");
-  const int cpc = g.ncolp / WCH;                            // columns per chunk: a multiple of 16
+  static_assert(128 % (WCH * WKB) == 0, "the padded columns split into WCH chunks of whole K-blocks");
+  const int cpc = g.ncolp / WCH;                            // columns per chunk: a multiple of WKB
   hipLaunchKernelGGL(c64_bin_wgemm_kernel, dim3(WCH, 64), dim3(256), 0, st, D, Z, Pp, g.ncolp, cpc);
   EAV_CHECK_LAUNCH("eav_conv64_fft_wgrad(gemm)");
   hipLaunchKernelGGL(c64_wsum_kernel, dim3(64, 64), dim3(64), 0, st, Pp, Acc, WCH);
