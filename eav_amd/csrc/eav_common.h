@@ -72,6 +72,21 @@ __device__ __forceinline__ float elu_f(float v) {
 #endif
 __device__ __forceinline__ float elu_grad_from_out(float v, float a) { return v > 0.f ? 1.f : a + 1.f; }
 
+// One sample of the backward of BatchNorm -> ELU -> AvgPool -> Dropout (pool_bwd_apply_kernel, and the separableConv
+// backward pack that forms du while it loads, eegnet_conv64_fft.hip): v = the BatchNorm input, go = the pooled gradient of
+// its window / P x the dropout multiplier (0 on the dropped tail).  Returns du = scale (g - m1 - uhat m2); g = go ELU'(pre)
+// and uhat leave for the caller's sums.  The contraction is written out - it is the one hipcc chose for the stand-alone
+// kernel - so that every kernel that forms du gives the same bits.
+__device__ __forceinline__ float pool_bwd_du(float v, float go, float mean, float invstd, float sc, float sh, float m1,
+                                             float m2, float& g, float& uhat) {
+#pragma clang fp contract(off)
+  const float pre = __builtin_fmaf(sc, v, sh);
+  const float eg = elu_grad_from_out(pre, elu_f(pre));
+  g = go * eg;
+  uhat = (v - mean) * invstd;
+  return sc * __builtin_fmaf(-m2, uhat, __builtin_fmaf(go, eg, -m1));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -270,12 +270,11 @@ __global__ __launch_bounds__(256) void pool_bwd_apply_kernel(const float* __rest
     ld4(src, t, T, vec, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float pre = sc * v[e] + sh;
-      const float g = go * elu_grad_from_out(pre, elu_f(pre));
-      o[e] = sc * (g - m1 - (v[e] - mean) * invstd * m2);
+      float g, uhat;
+      o[e] = pool_bwd_du(v[e], go, mean, invstd, sc, sh, m1, m2, g, uhat);
       if (t + e < T) {                       // (go = 0 on the dropped tail: it adds nothing, as in pass 1)
         st[0] += g;
-        st[1] += g * ((v[e] - mean) * invstd);
+        st[1] += g * uhat;
       }
     }
     st4(dst, t, T, vec, o);

@@ -11,10 +11,13 @@
 // imaginary): every step - FFT, complex-linear mixing, inverse FFT - keeps them apart (real filters), no unpacking.
 //
 // Three kernels + the filter spectra:
-//   c64_spectra_kernel   BmT[bin][(ri_i, i)][(ri_o, o)] = the transpose of [[Gr, -Gi], [Gi, Gr]], G = conj(W) / 64 (forward), or the
-//                        flipped / transposed filters of the data gradient
+//   c64_spectra_wave     BmT[bin][(ri_i, i)][(ri_o, o)] = the transpose of [[Gr, -Gi], [Gi, Gr]], G = conj(W) / 64 (forward), or the
+//                        flipped / transposed filters of the data gradient - the leading workgroups of the pack launch
 //   c64_pack_fft_kernel  a wave per column (sample b, block pair): coalesced row loads -> LDS transpose -> lane = channel,
 //                        64-point complex FFT entirely in registers (8 x 8, no exchange) -> Z[bin][col][re | im][64 ch]
+//   c64_pack_bwd_kernel  the backward's pack: BOTH spectra of a du block pair from one load (64-sample window of the data
+//                        gradient; its samples 8 .. 56, zero-padded, are the weight gradient's block), du itself optionally
+//                        formed from dp3 / u3 while loading (the backward of separableBN -> ELU -> AvgPool8 -> Dropout)
 //   c64_bin_gemm_kernel  per bin C[cols x 128] = Z[cols x 128] . Bm^T on v_mfma_f32_32x32x2_f32, weight-stationary (a wave
 //                        keeps its 32 outputs x 128 contraction rows of Bm in 64 VGPRs), column tiles through LDS
 //   c64_ifft_unpack_kernel  lane = output channel: inverse FFT in registers, BatchNorm sums per channel (= per lane),
@@ -94,13 +97,11 @@ Geo geometry(int B, int T, int padl) {
 
 // ---------------------------------------------------------------------------------------------------------- filter spectra
 // BmT[bin][k = (ri_i, in)][n = (ri_o, out)] (contraction index major: the GEMM's weight-stationary waves then load their
-// operand registers as whole 128-byte rows).  One workgroup (one wave) per input channel `in`, lane = output channel `out`.
+// operand registers as whole 128-byte rows).  One wave per input channel `in`, lane = output channel `out`.
 // Table 0 (forward): filter (out, in) = w[out][in][:]; table 1 (data gradient: dp2[i] = sum_o w'[i][o] * du[o],
 // w'[i][o][k'] = w[o][i][15 - k']): out = i, in = o.
-__global__ __launch_bounds__(64) void c64_spectra_kernel(const float* __restrict__ w, float* __restrict__ Bm0, int bwd0) {
-  const int in = blockIdx.x, lane = threadIdx.x;
-  const int bwd = bwd0 + blockIdx.y;                      // grid.y = 2: the forward's table, then the data gradient's
-  float* Bm = Bm0 + (int64_t)blockIdx.y * 64 * 128 * 128;
+__device__ __forceinline__ void c64_spectra_wave(const float* __restrict__ w, float* __restrict__ Bm, int in, int bwd,
+                                                 int lane) {
   v2f x[64];
 #pragma unroll
   for (int n = 0; n < 64; ++n) {
@@ -125,15 +126,50 @@ __global__ __launch_bounds__(64) void c64_spectra_kernel(const float* __restrict
 // read back with lane = channel (bank (lane + n) mod 32: conflict-free); block A -> real parts, block B -> imaginary parts.
 constexpr int TS = 65;
 
+// x[ch] = (sample `lane` of block A, of block B) of channel ch  ->  x[n] = sample n of channel `lane`
+__device__ __forceinline__ void pack_transpose(float* tile, v2f (&x)[64], int lane) {
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) tile[ch * TS + lane] = half == 0 ? x[ch].x : x[ch].y;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    float r[64];
+#pragma unroll
+    for (int n = 0; n < 64; ++n) r[n] = tile[lane * TS + n];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int n = 0; n < 64; ++n) {
+      if (half == 0) x[n].x = r[n]; else x[n].y = r[n];
+    }
+  }
+}
+
+__device__ __forceinline__ void pack_store(float* __restrict__ Z, const v2f (&x)[64], int col, int ncolp, int lane) {
+  float* dst = Z + (int64_t)col * 128 + lane;
+#pragma unroll
+  for (int m = 0; m < 64; ++m) {
+    dst[(int64_t)m * ncolp * 128] = x[pos64(m)].x;
+    dst[(int64_t)m * ncolp * 128 + 64] = x[pos64(m)].y;
+  }
+}
+
 // vonly: the block is its 49 valid samples, zero-padded (the du operand of the weight gradient), instead of 64 samples
 // starting padl before the block (forward / data gradient inputs).
+// The first nspec workgroups form the filter spectra instead (a wave per input channel; tables bwd0 .. of Bm0): the per-bin
+// GEMM is the first reader of both, so the tables need no launch - no graph node on the critical path - of their own.
 __global__ __launch_bounds__(256) void c64_pack_fft_kernel(const float* __restrict__ in, float* __restrict__ Z, Geo g,
-                                                           int vonly) {
+                                                           int vonly, const float* __restrict__ w, float* __restrict__ Bm0,
+                                                           int nspec, int bwd0) {
   __shared__ float tiles[4][64 * TS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if ((int)blockIdx.x < nspec) {
+    const int job = blockIdx.x * 4 + wave, table = job >> 6;
+    c64_spectra_wave(w, Bm0 + (int64_t)table * 64 * 128 * 128, job & 63, bwd0 + table, lane);
+    return;
+  }
   float* tile = tiles[wave];
-  const int nwaves = gridDim.x * 4;
-  for (int col = blockIdx.x * 4 + wave; col < g.ncolp; col += nwaves) {
+  const int nwaves = (gridDim.x - nspec) * 4;
+  for (int col = (blockIdx.x - nspec) * 4 + wave; col < g.ncolp; col += nwaves) {
     if (col >= g.ncol) {                       // padding column: zero spectra (the weight gradient contracts over columns)
       float* dz = Z + (int64_t)col * 128 + lane;
 #pragma unroll 8
@@ -159,27 +195,138 @@ __global__ __launch_bounds__(256) void c64_pack_fft_kernel(const float* __restri
         if (half == 0) x[ch].x = v; else x[ch].y = v;
       }
     }
+    pack_transpose(tile, x, lane);
+    fft64<false>(x);
+    pack_store(Z, x, col, g.ncolp, lane);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- backward pack + 2 FFTs
+// The separableConv backward needs two spectra of du: of the 64-sample windows that start 8 samples before each block (data
+// gradient -> Zb) and of the blocks' 49 valid samples, zero-padded (weight gradient -> D).  The second block is samples
+// 8 .. 56 of the first: after the transpose both are compile-time register indices of ONE load of the column.
+// FUSE: du is not read but formed per loaded sample from u3 (separableConv output) and dp3 (gradient of the pooled,
+// dropped-out block-2 output) with pool_bwd_apply_kernel<8>'s arithmetic (pool_bwd_du) - no du tensor in HBM.  The pooled
+// gradient x dropout multiplier of a (channel, pooling window) is formed ONCE per column (a 64-sample window touches at most
+// 9 pooling windows: 576 values per block, 9 per lane) and handed to the 8 lanes of the window through the (still idle) tile.
+struct DuSrc {
+  const float *dp, *u, *bn, *m12;      // dp3 [B,64,T/8], u3 [B,64,T], bn = mean, invstd, scale, shift [64] each, m1 m2 [64] each
+  float drop_p;
+  uint64_t seed;
+  const uint8_t* mask;
+  const uint64_t* seed_dev;
+};
+constexpr int PADB = KT / 2, NPW = 9;      // the data gradient's left padding; pooling windows a 64-sample window can touch
+
+template <bool FUSE>
+__global__ __launch_bounds__(256, 2) void c64_pack_bwd_kernel(const float* __restrict__ du, DuSrc s, float* __restrict__ Zb,
+                                                           float* __restrict__ D, Geo g) {
+  __shared__ float tiles[4][64 * TS];
+  __shared__ __attribute__((aligned(16))) float cst[FUSE ? 64 * 8 : 1];      // per channel: mean, invstd, scale, shift, m1, m2
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* tile = tiles[wave];
+  uint64_t seed = 0;
+  const int To = g.T / 8;
+  if (FUSE) {
+    seed = dropout_seed(s.seed, s.seed_dev);
+    if (threadIdx.x < 64) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) cst[threadIdx.x * 8 + k] = s.bn[k * 64 + threadIdx.x];
+      cst[threadIdx.x * 8 + 4] = s.m12[threadIdx.x];
+      cst[threadIdx.x * 8 + 5] = s.m12[64 + threadIdx.x];
+    }
+    __syncthreads();
+  }
+  const int nwaves = gridDim.x * 4;
+  for (int col = blockIdx.x * 4 + wave; col < g.ncolp; col += nwaves) {
+    if (col >= g.ncol) {                       // padding column: zero spectra in both buffers
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        float* dz = (q ? D : Zb) + (int64_t)col * 128 + lane;
+#pragma unroll 8
+        for (int m = 0; m < 64; ++m) {
+          dz[(int64_t)m * g.ncolp * 128] = 0.f;
+          dz[(int64_t)m * g.ncolp * 128 + 64] = 0.f;
+        }
+      }
+      continue;
+    }
+    const int b = col / g.npair, pr = col - b * g.npair;
+    v2f x[64];
+    const float* in = FUSE ? s.u : du;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
+      const int blk = 2 * pr + half;
+      const int t = blk * LV - PADB + lane;
+      const bool ok = blk < g.nblk && t >= 0 && t < g.T;
+      const float* src = in + (int64_t)b * NCH * g.T + t;
 #pragma unroll
-      for (int ch = 0; ch < NCH; ++ch) tile[ch * TS + lane] = half == 0 ? x[ch].x : x[ch].y;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      float r[64];
-#pragma unroll
-      for (int n = 0; n < 64; ++n) r[n] = tile[lane * TS + n];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int n = 0; n < 64; ++n) {
-        if (half == 0) x[n].x = r[n]; else x[n].y = r[n];
+      for (int ch = 0; ch < NCH; ++ch) {
+        const float v = ok ? src[(int64_t)ch * g.T] : 0.f;
+        if (half == 0) x[ch].x = v; else x[ch].y = v;
       }
     }
-    fft64<false>(x);
-    float* dst = Z + (int64_t)col * 128 + lane;
+    if (FUSE) {
+      // (under the latency of the loads above) go[half][ch][w]: window to0 + w of row (b, ch)
 #pragma unroll
-    for (int m = 0; m < 64; ++m) {
-      dst[(int64_t)m * g.ncolp * 128] = x[pos64(m)].x;
-      dst[(int64_t)m * g.ncolp * 128 + 64] = x[pos64(m)].y;
+      for (int half = 0; half < 2; ++half) {
+        const int blk = 2 * pr + half, to0 = (blk * LV - PADB) >> 3;      // arithmetic shift: floor (block 0 starts at -8)
+#pragma unroll
+        for (int i = 0; i < NCH * NPW / 64; ++i) {
+          const int item = i * 64 + lane, ch = item / NPW, to = to0 + item - ch * NPW;
+          float go = 0.f;
+          if (blk < g.nblk && to >= 0 && to < To) {
+            const uint64_t row = (uint64_t)b * NCH + ch, oi = row * To + to;
+            go = s.dp[oi] * (1.0f / 8) * dropout_mult_row(s.drop_p, seed, s.mask, oi, row);
+          }
+          tile[half * NCH * NPW + item] = go;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      int wofs[2];
+      bool okh[2];
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int blk = 2 * pr + half, t = blk * LV - PADB + lane;
+        okh[half] = blk < g.nblk && t >= 0 && t < g.T;
+        wofs[half] = half * NCH * NPW + (t >> 3) - ((blk * LV - PADB) >> 3);
+      }
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cst + ch * 8);
+        const v2f c1 = *reinterpret_cast<const v2f*>(cst + ch * 8 + 4);
+        float gd, ud;
+        const float o0 = pool_bwd_du(x[ch].x, tile[wofs[0] + ch * NPW], c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, gd, ud);
+        const float o1 = pool_bwd_du(x[ch].y, tile[wofs[1] + ch * NPW], c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, gd, ud);
+        x[ch].x = okh[0] ? o0 : 0.f;
+        x[ch].y = okh[1] ? o1 : 0.f;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
+    pack_transpose(tile, x, lane);
+    // the weight gradient's block waits for the window's FFT: 65 of its 98 values per lane in the tile (idle now; [k][lane]:
+    // a lane re-reads its own words), the rest in registers - all 98 in registers halve the occupancy (256 + 62 registers)
+    constexpr int NPK = TS - LV;               // imaginary parts that still fit into the tile
+    float yk[LV - NPK];
+#pragma unroll
+    for (int n = 0; n < LV; ++n) {
+      tile[n * 64 + lane] = x[PADB + n].x;
+      if (n < NPK) tile[(LV + n) * 64 + lane] = x[PADB + n].y;
+      else yk[n - NPK] = x[PADB + n].y;
+    }
+    fft64<false>(x);
+    pack_store(Zb, x, col, g.ncolp, lane);
+#pragma unroll
+    for (int n = 0; n < 64; ++n) {
+      x[n] = (v2f){0.f, 0.f};
+      if (n < LV) {
+        x[n].x = tile[n * 64 + lane];
+        x[n].y = n < NPK ? tile[(LV + n) * 64 + lane] : yk[n - NPK];
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    fft64<false>(x);
+    pack_store(D, x, col, g.ncolp, lane);
   }
 }
 
@@ -503,11 +650,10 @@ extern "C" int eav_conv64_fft_fwd(const float* in, const float* w, float* out, f
   if (bwd == 2) bwd = 1;
   float* Z = ws + (int64_t)2 * 64 * 128 * 128 + (bwd ? (int64_t)64 * g.ncolp * 128 : 0);
   float* Y = ws + (int64_t)2 * 64 * 128 * 128 + (int64_t)2 * 64 * g.ncolp * 128;
-  if (!prepared) {      // forward: both tables (weights do not change between the forward and the backward of a step)
-    hipLaunchKernelGGL(c64_spectra_kernel, dim3(NCH, bwd ? 1 : 2), dim3(64), 0, st, w, Bm, bwd);
-    EAV_CHECK_LAUNCH("eav_conv64_fft_fwd(spectra)");
-  }
-  hipLaunchKernelGGL(c64_pack_fft_kernel, dim3(pack_grid(g)), dim3(256), 0, st, in, Z, g, 0);
+  // forward: both tables (weights do not change between the forward and the backward of a step), as the leading
+  // workgroups of the pack launch - a wave per (table, input channel)
+  const int nspec = prepared ? 0 : (bwd ? NCH / 4 : 2 * NCH / 4);
+  hipLaunchKernelGGL(c64_pack_fft_kernel, dim3(nspec + pack_grid(g)), dim3(256), 0, st, in, Z, g, 0, w, Bm, nspec, bwd);
   EAV_CHECK_LAUNCH("eav_conv64_fft_fwd(fft)");
   hipLaunchKernelGGL(c64_bin_gemm_kernel, dim3(64, std::min(GEMM_GW, g.ncolp / 32)), dim3(256), 0, st, Z, Bm, Y, g.ncolp);
   EAV_CHECK_LAUNCH("eav_conv64_fft_fwd(gemm)");
@@ -527,7 +673,7 @@ extern "C" int eav_conv64_fft_wgrad(const float* du, float* dW, float* ws, int B
   float* D = Z + (int64_t)2 * 64 * g.ncolp * 128;
   float* Pp = Z + (int64_t)3 * 64 * g.ncolp * 128;
   float* Acc = Pp + (int64_t)WCH * 64 * 128 * 128;
-  hipLaunchKernelGGL(c64_pack_fft_kernel, dim3(pack_grid(g)), dim3(256), 0, st, du, D, g, 1);
+  hipLaunchKernelGGL(c64_pack_fft_kernel, dim3(pack_grid(g)), dim3(256), 0, st, du, D, g, 1, nullptr, nullptr, 0, 0);
   EAV_CHECK_LAUNCH("eav_conv64_fft_wgrad(fft)");
   static_assert(128 % (WCH * WKB) == 0, "the padded columns split into WCH chunks of whole K-blocks");
   const int cpc = g.ncolp / WCH;                            // columns per chunk: a multiple of WKB
@@ -537,5 +683,50 @@ extern "C" int eav_conv64_fft_wgrad(const float* du, float* dW, float* ws, int B
   EAV_CHECK_LAUNCH("eav_conv64_fft_wgrad(sum)");
   hipLaunchKernelGGL(c64_wfinish_kernel, dim3(NCH), dim3(64), 0, st, Acc, dW);
   EAV_CHECK_LAUNCH("eav_conv64_fft_wgrad(finish)");
+  return EAV_OK;
+}
+
+// The whole separableConv backward of a step from ONE pack launch: dx [B,64,T] = d loss / d(conv input) (what
+// eav_conv64_fft_fwd(bwd = 2) gives) and dW [64,64,16] (what eav_conv64_fft_wgrad gives), bit for bit.  ws: the workspace
+// the forward call of this step (eav_conv64_fft_fwd, bwd = 0) left its filter spectra and input spectra in.
+//   du != NULL: du [B,64,T] = d loss / d(conv output) is read;
+//   du == NULL: it is formed while loading, du = eav_bn_elu_pool_bwd_apply(dp, u, bn, m12, P = 8) with the same dropout
+//               arguments (dp [B,64,T/8], u [B,64,T] = the conv output, bn = mean, invstd, scale, shift, m12 = m1, m2) -
+//               that launch and the du tensor disappear.
+// The weight gradient's du spectra and the data gradient's GEMM output share the workspace's third spectra buffer: the
+// weight-gradient GEMM runs first.
+extern "C" int eav_conv64_fft_bwd(const float* du, const float* dp, const float* u, const float* bn, const float* m12,
+                                  float drop_p, uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev, float* dx,
+                                  float* dW, float* ws, int B, int T, void* stream) {
+  EAV_REQUIRE(dx && dW && ws && B > 0 && T > 0, "eav_conv64_fft_bwd: bad arguments");
+  EAV_REQUIRE(du || (dp && u && bn && m12), "eav_conv64_fft_bwd: neither du nor (dp, u, bn, m12)");
+  EAV_REQUIRE(du || T >= 8, "eav_conv64_fft_bwd: T %d < the pooling window", T);
+  EAV_REQUIRE(drop_p > -1.f && drop_p < 1.f, "eav_conv64_fft_bwd: dropout %f outside (-1,1)", drop_p);
+  EAV_REQUIRE(((uintptr_t)ws & 15) == 0, "eav_conv64_fft_bwd: the workspace must be 16-byte aligned");
+  const Geo g = geometry(B, T, PADB);
+  hipStream_t st = (hipStream_t)stream;
+  float* Bm = ws + (int64_t)64 * 128 * 128;                        // the data gradient's table
+  float* Z = ws + (int64_t)2 * 64 * 128 * 128;                     // the forward's input spectra
+  float* Zb = Z + (int64_t)64 * g.ncolp * 128;
+  float* D = Z + (int64_t)2 * 64 * g.ncolp * 128;                  // = Y below
+  float* Pp = Z + (int64_t)3 * 64 * g.ncolp * 128;
+  float* Acc = Pp + (int64_t)WCH * 64 * 128 * 128;
+  const DuSrc src = {dp, u, bn, m12, drop_p, seed, mask, seed_dev};
+  if (du)
+    hipLaunchKernelGGL(c64_pack_bwd_kernel<false>, dim3(pack_grid(g)), dim3(256), 0, st, du, src, Zb, D, g);
+  else
+    hipLaunchKernelGGL(c64_pack_bwd_kernel<true>, dim3(pack_grid(g)), dim3(256), 0, st, du, src, Zb, D, g);
+  EAV_CHECK_LAUNCH("eav_conv64_fft_bwd(fft)");
+  const int cpc = g.ncolp / WCH;
+  hipLaunchKernelGGL(c64_bin_wgemm_kernel, dim3(WCH, 64), dim3(256), 0, st, D, Z, Pp, g.ncolp, cpc);
+  EAV_CHECK_LAUNCH("eav_conv64_fft_bwd(wgemm)");
+  hipLaunchKernelGGL(c64_bin_gemm_kernel, dim3(64, std::min(GEMM_GW, g.ncolp / 32)), dim3(256), 0, st, Zb, Bm, D, g.ncolp);
+  EAV_CHECK_LAUNCH("eav_conv64_fft_bwd(gemm)");
+  hipLaunchKernelGGL(c64_ifft_unpack_kernel, dim3(pack_grid(g)), dim3(256), 0, st, D, dx, nullptr, g);
+  EAV_CHECK_LAUNCH("eav_conv64_fft_bwd(ifft)");
+  hipLaunchKernelGGL(c64_wsum_kernel, dim3(64, 64), dim3(64), 0, st, Pp, Acc, WCH);
+  EAV_CHECK_LAUNCH("eav_conv64_fft_bwd(sum)");
+  hipLaunchKernelGGL(c64_wfinish_kernel, dim3(NCH), dim3(64), 0, st, Acc, dW);
+  EAV_CHECK_LAUNCH("eav_conv64_fft_bwd(finish)");
   return EAV_OK;
 }

@@ -182,6 +182,10 @@ class EEGNet_tor(KernelModule):
         # (the reference's own [B,1,30,500], where one FFT block would be mostly padding).  EAV_FIR_ALGO overrides.
         self.fir_algo = os.environ.get("EAV_FIR_ALGO", "auto")
         self.conv_algo = os.environ.get("EAV_CONV_ALGO", "auto")      # separableConv: see _use_conv_fft
+        # frequency-domain separableConv backward from ONE pack launch that writes the spectra of both gradients and - in a
+        # training step - forms du3 from dp3 / u3 while it loads (eav_conv64_fft_bwd: no eav_bn_elu_pool_bwd_apply launch, no
+        # du3 tensor, one pack launch less); False / EAV_CONV_FUSE=0: the separate launches (bit-identical results)
+        self.conv_fuse = os.environ.get("EAV_CONV_FUSE", "1") != "0"
         self._infer = False                    # set per call: no-grad eval-mode forward
         # forward_batch: (optimiser step counter, labels, idx, targets, batch) - raw pointers for eav_step_begin, taken by the next
         # forward's counter launch (left in place if that forward has none to merge them into)
@@ -488,12 +492,14 @@ class EEGNet_tor(KernelModule):
           P(ws.dp3), B, NF, nb, st)
         # block 2: Dropout <- AvgPool8 <- ELU <- separableBN
         b3 = P(ws.bn3)
+        fuse = bool(self.conv_fuse) and self._use_conv_fft(B)
         if training:
             L("eav_bn_elu_pool_bwd_reduce", P(ws.dp3), P(ws.u3), b3, P(ws.part_pb), B, 64, T2, 8, drop, seed2, m2, cnt, st)
             L("eav_bn_bwd_finalize", P(ws.part_pb), B, 64, float(B * T2), tr, P(g["separableBN.weight"]),
               P(g["separableBN.bias"]), b3 + 4 * 256, b3 + 4 * 320, st)
-            L("eav_bn_elu_pool_bwd_apply", P(ws.dp3), P(ws.u3), b3, b3 + 4 * 256, P(ws.du3), B, 64, T2, 8, drop, seed2, m2,
-              cnt, st)
+            if not fuse:
+                L("eav_bn_elu_pool_bwd_apply", P(ws.dp3), P(ws.u3), b3, b3 + 4 * 256, P(ws.du3), B, 64, T2, 8, drop, seed2,
+                  m2, cnt, st)
         else:
             # eval-mode step (Q4: every epoch after the first): BatchNorm backward is a plain scale, so the gradient and the
             # sums for the BatchNorm weight / bias leave from ONE pass over u3 / dp3
@@ -502,14 +508,17 @@ class EEGNet_tor(KernelModule):
             L("eav_bn_bwd_finalize", P(ws.part_pb), B, 64, float(B * T2), tr, P(g["separableBN.weight"]),
               P(g["separableBN.bias"]), b3 + 4 * 256, b3 + 4 * 320, st)
         # separableConv: data gradient (flipped/transposed taps, pad 8) and weight gradient
-        if self._use_conv_fft(B):
+        if fuse:
+            # one pack launch for both (the filter spectra of the data gradient were prepared by this step's forward call);
+            # training step: du3 = the eav_bn_elu_pool_bwd_apply above is formed inside it and never written
+            L("eav_conv64_fft_bwd", None if training else P(ws.du3), P(ws.dp3), P(ws.u3), b3, b3 + 4 * 256, drop, seed2, m2,
+              cnt, P(ws.dp2), P(g["separableConv.weight"]), P(ws.c64_ws), B, T2, st)
+        elif self._use_conv_fft(B):
             # (bwd = 2: the filter spectra of the data gradient were prepared by this step's forward call)
             L("eav_conv64_fft_fwd", P(ws.du3), P(self.separableConv.weight), P(ws.dp2), None, P(ws.c64_ws), B, T2, 2, st)
-        else:
-            L("eav_conv64_fwd", P(ws.du3), P(ws.wTb), P(ws.dp2), None, B, T2, 8, st)
-        if self._use_conv_fft(B):
             L("eav_conv64_fft_wgrad", P(ws.du3), P(g["separableConv.weight"]), P(ws.c64_ws), B, T2, st)
         else:
+            L("eav_conv64_fwd", P(ws.du3), P(ws.wTb), P(ws.dp2), None, B, T2, 8, st)
             L("eav_conv64_wgrad", P(ws.du3), P(ws.p2), P(ws.part_cw), B, T2, 7, st)
             L("eav_reduce_partials", P(ws.part_cw), ws.np_cw, 65536, 65536, 1.0, P(g["separableConv.weight"]), st)
         # block 1 tail: Dropout <- AvgPool4 <- ELU <- depthwiseBN

@@ -172,6 +172,14 @@ int eav_conv64_fft_fwd(const float* in, const float* w, float* out, float* stat_
 /* dW [64,64,16] = d loss / d separableConv.weight, WRITTEN (replaces eav_conv64_wgrad + eav_reduce_partials); needs the
  * forward input's spectra of the same step in ws (eav_conv64_fft_fwd with bwd = 0 was called on it). */
 int eav_conv64_fft_wgrad(const float* du, float* dW, float* ws, int B, int T, void* stream);
+/* The separableConv backward of a step from ONE pack launch that writes both du spectra: dx = what eav_conv64_fft_fwd(bwd = 2)
+ * gives and dW = what eav_conv64_fft_wgrad gives, bit for bit; ws as for those two (the forward call of the step was made on
+ * it).  du != NULL: du [B,64,T] is read.  du == NULL: du is formed while loading - the backward of separableBN -> ELU ->
+ * AvgPool(1,8) -> Dropout, i.e. eav_bn_elu_pool_bwd_apply(dp, u, bn, m12, ..., P = 8, drop_p, seed, mask, seed_dev) without
+ * that launch and without the du tensor (dp [B,64,T/8], u [B,64,T], bn = mean, invstd, scale, shift, m12 = m1, m2). */
+int eav_conv64_fft_bwd(const float* du, const float* dp, const float* u, const float* bn, const float* m12, float drop_p,
+                       uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev, float* dx, float* dW, float* ws, int B,
+                       int T, void* stream);
 int eav_conv64_wgrad_nparts(int B, int T);
 /* part [nparts][64*64*16]; sum over parts = dL/dW[o,i,k]. */
 int eav_conv64_wgrad(const float* du, const float* in, float* part, int B, int T, int padl, void* stream);
