@@ -37,7 +37,6 @@ __device__ __forceinline__ int kappa(int ks, int kk) { return (ks & 3) + 8 * (ks
 // probability costs one subtract and one native v_exp_f32 instead of the ~12-instruction expf expansion - the VALU
 // work between the MFMA phases was a third of a key-tile iteration.  lse stays in natural-log units at the ABI.
 constexpr float LOG2E = 1.44269504088896340736f, LN2 = 0.69314718055994530942f;
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 struct DropArgs {               // attention-probability dropout (DROP instantiations only)
   float p;

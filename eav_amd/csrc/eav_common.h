@@ -31,14 +31,6 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // ELU(alpha=1) as torch computes it (expm1 for v <= 0) and its derivative (EEGNet_tor.py:53,56,61: nn.ELU()).
 #ifdef EAV_ABL_ELU      // timing-only ablation: the passes without their expm1 (results garbage)
 __device__ __forceinline__ float elu_f(float v) { return v > 0.f ? v : 0.5f * v; }
-#elif defined(EAV_ELU_LIBM)
-// round 5: libm expm1f of the clamped argument, selected (22 instructions per call + clamp + select; `v > 0 ? v :
-// expm1f(v)` compiles to an exec-masked branch around every call - the lanes of a wave diverge on the sign, so nothing is
-// skipped, and the four calls per channel of the depthwise passes sit in four basic blocks that cannot be interleaved)
-__device__ __forceinline__ float elu_f(float v) {
-  const float e = expm1f(fminf(v, 0.f));
-  return v <= 0.f ? e : v;
-}
 #else
 // expm1 on [-17.5, 0] (below, expm1 rounds to -1 in fp32) in 13 branch-free VALU instructions:
 //   t = x log2(e) + 1.5 2^23        the sum's low mantissa bits hold n = rint(x log2 e), no conversion instruction
@@ -92,6 +84,22 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// The same sum as a wave-uniform value by DPP operands only: in-row inclusive scan (row_shr 1, 2, 4, 8), row totals carried
+// by the two row broadcasts, total read from lane 63 - no LDS round trips and no barrier.  (The __shfl_xor butterfly of
+// wave_sum compiles to six DEPENDENT ds_bpermute round trips, ~600 cycles of LDS latency where a kernel waits for it.)
+template <int CTRL, int ROW_MASK, bool BOUND>
+__device__ __forceinline__ float dpp_row(float src) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(src), CTRL, ROW_MASK, 0xf, BOUND));
+}
+__device__ __forceinline__ float wave_total_dpp(float a) {
+  a += dpp_row<0x111, 0xf, true>(a);      // row_shr:1
+  a += dpp_row<0x112, 0xf, true>(a);      // row_shr:2
+  a += dpp_row<0x114, 0xf, true>(a);      // row_shr:4
+  a += dpp_row<0x118, 0xf, true>(a);      // row_shr:8
+  a += dpp_row<0x142, 0xa, false>(a);     // row_bcast:15 into rows 1 and 3
+  a += dpp_row<0x143, 0xc, false>(a);     // row_bcast:31 into rows 2 and 3
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63));
+}
 // sum over the 32 lanes of each wave half (lanes 0-31 / 32-63 reduce separately)
 __device__ __forceinline__ float half_sum(float v) {
 #pragma unroll
@@ -115,6 +123,32 @@ __device__ __forceinline__ void block_sum_256(float (&v)[NV], float* red) {
   }
   __syncthreads();
 }
+
+// 4 consecutive floats p[i .. i + 3] of a row of n: one 16-byte access where the row allows (vec: the row bases are 16-byte
+// aligned) and the four lie inside, element-wise with bounds otherwise (loads give 0 outside)
+__device__ __forceinline__ void ld4(const float* p, int i, int n, bool vec, float (&v)[4]) {
+  if (vec && i + 3 < n) {
+    const float4 a = *reinterpret_cast<const float4*>(p + i);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (i + e < n) ? p[i + e] : 0.f;
+  }
+}
+__device__ __forceinline__ void st4(float* p, int i, int n, bool vec, const float (&v)[4]) {
+  if (vec && i + 3 < n) {
+    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (i + e < n) p[i + e] = v[e];
+  }
+}
+
+// 2^x by the native v_exp_f32 (the base-2 softmax of the attention kernels)
+__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
+// erf-GELU through libm's erff (gemm_sp.hip has its own erfc-fit gelu_erf)
+__device__ __forceinline__ float gelu_erf_libm(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
 // Operand-scale slot of the split-operand kernels (EAV_SP_SLOT floats, include/eav_hip.h): 64 shards of the bits of
 // max|x|, one per 128-byte line (word 32*i) so that the producers' atomicMax traffic spreads over 64 L2 lines / channels
@@ -150,6 +184,15 @@ __device__ __forceinline__ unsigned eav_slot_bits(const float* slot) {
 #pragma unroll 8
   for (int i = 0; i < 64; ++i) bits = max(bits, __float_as_uint(slot[32 * i]));
   return bits;
+}
+
+// sigma = 2^(14 - floor(log2 amax)) from the bits of amax: max|sigma v| in [2^14, 2^15); 1 for an all-zero / non-finite tensor
+__device__ __forceinline__ float sigma_from_bits(unsigned bits) {
+  const int e = (int)((bits >> 23) & 0xff);
+  if (bits == 0u || e == 0xff) return 1.f;
+  int se = 14 - (e - 127);
+  se = max(-126, min(126, se));
+  return __uint_as_float((unsigned)(se + 127) << 23);
 }
 
 // counter-based dropout keep decision: pure function of (seed, element index)

@@ -13,17 +13,8 @@ namespace {
 
 constexpr int F1 = 8, DD = 8, CHMAX = 32;
 
-__device__ __forceinline__ void ld4(const float* p, int i, int n, bool vec, float (&v)[4]) {
-  if (vec && i + 3 < n) {
-    float4 a = *reinterpret_cast<const float4*>(p + i);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (i + e < n) ? p[i + e] : 0.f;
-  }
-}
-// streaming forms: the big activation tensors are touched once per kernel - non-temporal loads / stores keep them from
-// evicting the small reused operands (measured on the float4 copy: +10 % at the same geometry)
+// streaming forms of ld4 / st4: the big activation tensors are touched once per kernel - non-temporal loads / stores keep
+// them from evicting the small reused operands (measured on the float4 copy: +10 % at the same geometry)
 __device__ __forceinline__ void ld4s(const float* p, int i, int n, bool vec, float (&v)[4]) {
   if (vec && i + 3 < n) {
     const f32x4 a = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + i));
@@ -36,15 +27,6 @@ __device__ __forceinline__ void ld4s(const float* p, int i, int n, bool vec, flo
 __device__ __forceinline__ void st4s(float* p, int i, int n, bool vec, const float (&v)[4]) {
   if (vec && i + 3 < n) {
     __builtin_nontemporal_store((f32x4){v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p + i));
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (i + e < n) p[i + e] = v[e];
-  }
-}
-__device__ __forceinline__ void st4(float* p, int i, int n, bool vec, const float (&v)[4]) {
-  if (vec && i + 3 < n) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e)
@@ -299,22 +281,6 @@ __device__ __forceinline__ float dpp_f(float old, float src) {
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, 0xf, BANK_MASK, false));
 }
 
-// Sum of a over the wave, wave-uniform, by DPP only (in-row inclusive scan, the two row broadcasts, lane 63): no LDS round
-// trips and no barrier (eegnet_fir_fft.hip's wave_total)
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ float dpp_row(float src) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(src), CTRL, ROW_MASK, 0xf, BOUND));
-}
-__device__ __forceinline__ float wave_total_dpp(float a) {
-  a += dpp_row<0x111, 0xf, true>(a);      // row_shr:1
-  a += dpp_row<0x112, 0xf, true>(a);      // row_shr:2
-  a += dpp_row<0x114, 0xf, true>(a);      // row_shr:4
-  a += dpp_row<0x118, 0xf, true>(a);      // row_shr:8
-  a += dpp_row<0x142, 0xa, false>(a);     // row_bcast:15 into rows 1 and 3
-  a += dpp_row<0x143, 0xc, false>(a);     // row_bcast:31 into rows 2 and 3
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63));
-}
-
 struct DwFuse {
   const float* z; const float* dp2; const float* bn2;   // bn2: mean, invstd, scale, shift, m1, m2 (64 each)
   float drop_p; uint64_t seed; const uint8_t* mask; const uint64_t* seed_dev;
@@ -343,11 +309,7 @@ __global__ __launch_bounds__(NT, DWB_WPE) void dw_bwd_kernel(const float* __rest
   constexpr int TPG = NT / CG;            // threads per channel group (a multiple of the wave size)
   // samples in DESCENDING order (the FFT weight-gradient kernel behind this one walks them ascending): measured -3 .. -8 us
   // on the step on one box, alternating runs (profiles/r05_eeg_variants.txt); dw_fwd walking backwards costs +5 us
-#ifdef DWB_ASC
-  const int chunk = blockIdx.x, f = blockIdx.y, b = blockIdx.z;
-#else
   const int chunk = blockIdx.x, f = blockIdx.y, b = gridDim.z - 1 - blockIdx.z;
-#endif
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int cg = CG > 1 ? threadIdx.x / TPG : 0, tl = CG > 1 ? threadIdx.x % TPG : threadIdx.x;
   for (int i = threadIdx.x; i < DD * C; i += NT) wsh[i] = w2[f * DD * C + i];
@@ -444,9 +406,6 @@ __global__ __launch_bounds__(NT, DWB_WPE) void dw_bwd_kernel(const float* __rest
       r[d] = __builtin_fmaf(dzv[d][0], a[0], dzv[d][1] * a[1]) + __builtin_fmaf(dzv[d][2], a[2], dzv[d][3] * a[3]);
     // step xor 1: keep 4 values; xor 2: keep 2; xor 4: keep 1; then plain reduce over the rest
     float r4[4], r2[2], r1;
-#ifdef DWB_ABL_NORED      // timing-only ablation (results garbage): the pass without its cross-lane reductions
-    r1 = r[0] + r[1] + r[2] + r[3] + r[4] + r[5] + r[6] + r[7];
-#else
     // (the partner values travel by DPP quad permutations / masked row shifts / v_permlane swaps: the same pairs and the same
     // order of additions as the __shfl_xor butterfly this replaces - ten dependent ds_bpermute round trips per channel)
     {
@@ -479,7 +438,6 @@ __global__ __launch_bounds__(NT, DWB_WPE) void dw_bwd_kernel(const float* __rest
       auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(r1), __float_as_uint(r1), false, false);
       r1 = __uint_as_float(h[0]) + __uint_as_float(h[1]);            // own + lane ^ 32
     }
-#endif
     // lane l (l < 8) now holds the wave total of d = 4*(l&1) + 2*((l>>1)&1) + ((l>>2)&1)
     if (lane < 8) {
       const int d = 4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1);

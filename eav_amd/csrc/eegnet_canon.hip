@@ -181,25 +181,6 @@ __global__ __launch_bounds__(256) void tconv_wgrad_kernel(const float* __restric
 // part[(b,tile)][fd] = sum z, [C2+fd] = sum z^2.   A thread owns 4 consecutive samples (float4 loads and stores).
 constexpr int SPT = 1024;   // samples per block of the spatial kernels
 
-__device__ __forceinline__ void ld4(const float* p, int i, int n, bool vec, float (&v)[4]) {
-  if (vec && i + 3 < n) {
-    const float4 a = *reinterpret_cast<const float4*>(p + i);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (i + e < n) ? p[i + e] : 0.f;
-  }
-}
-__device__ __forceinline__ void st4(float* p, int i, int n, bool vec, const float (&v)[4]) {
-  if (vec && i + 3 < n) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (i + e < n) p[i + e] = v[e];
-  }
-}
-
 __global__ __launch_bounds__(256) void spatial_fwd_kernel(const float* __restrict__ y1, const float* __restrict__ bn1,
                                                           const float* __restrict__ wd, float* __restrict__ z,
                                                           float* __restrict__ part, int C, int S, int F1, int D,

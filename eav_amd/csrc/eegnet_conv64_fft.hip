@@ -31,6 +31,7 @@
 namespace {
 
 constexpr int NCH = 64, KT = 16, NB = 64, LV = NB - KT + 1;      // 49 valid outputs per 64-sample block
+constexpr int PADF = (KT - 1) / 2, PADB = KT / 2;      // left padding of the forward (7) / of the data gradient (8)
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 constexpr float C64[50] = {1.0f, 0.995184727f, 0.98078528f, 0.956940336f, 0.923879533f, 0.881921264f, 0.831469612f, 0.773010453f, 0.707106781f, 0.634393284f, 0.555570233f, 0.471396737f, 0.382683432f, 0.290284677f, 0.195090322f, 0.0980171403f, 0.0f, -0.0980171403f, -0.195090322f, -0.290284677f, -0.382683432f, -0.471396737f, -0.555570233f, -0.634393284f, -0.707106781f, -0.773010453f, -0.831469612f, -0.881921264f, -0.923879533f, -0.956940336f, -0.98078528f, -0.995184727f, -1.0f, -0.995184727f, -0.98078528f, -0.956940336f, -0.923879533f, -0.881921264f, -0.831469612f, -0.773010453f, -0.707106781f, -0.634393284f, -0.555570233f, -0.471396737f, -0.382683432f, -0.290284677f, -0.195090322f, -0.0980171403f, 0.0f, 0.0980171403f};
@@ -216,7 +217,7 @@ struct DuSrc {
   const uint8_t* mask;
   const uint64_t* seed_dev;
 };
-constexpr int PADB = KT / 2, NPW = 9;      // the data gradient's left padding; pooling windows a 64-sample window can touch
+constexpr int NPW = 9;      // pooling windows a 64-sample window can touch
 
 template <bool FUSE>
 __global__ __launch_bounds__(256, 2) void c64_pack_bwd_kernel(const float* __restrict__ du, DuSrc s, float* __restrict__ Zb,
@@ -618,22 +619,28 @@ __global__ __launch_bounds__(64) void c64_wfinish_kernel(const float* __restrict
 
 int pack_grid(const Geo& g) { return std::max(1, std::min(512, cdiv(g.ncolp, 4))); }
 
+// The workspace of eav_conv64_fft_*, in this order: two filter-spectrum tables [64 bins][128][128] (forward BmF, data
+// gradient BmB), three spectra buffers [64 bins][columns][128] (Zf: input of the forward - kept for the weight gradient -,
+// Zb: input of the data gradient, Y: a scratch one - GEMM output / du blocks of the weight gradient), the weight gradient's
+// split-K partial products Pp and their sum Acc.  floats: the end offset = the size (ws NULL: the size alone).
+struct Ws { float *BmF, *BmB, *Zf, *Zb, *Y, *Pp, *Acc; int64_t floats; };
+Ws carve(float* ws, const Geo& g) {
+  const int64_t table = (int64_t)64 * 128 * 128, spectra = (int64_t)64 * g.ncolp * 128;
+  Ws s = {};
+  auto take = [&](int64_t n) { float* p = ws ? ws + s.floats : nullptr; s.floats += n; return p; };
+  s.BmF = take(table), s.BmB = take(table);
+  s.Zf = take(spectra), s.Zb = take(spectra), s.Y = take(spectra);
+  s.Pp = take(WCH * table), s.Acc = take((int64_t)64 * 64 * 64 * 2);
+  return s;
+}
+
 }  // namespace
 
-// floats of the workspace of eav_conv64_fft_*: two filter-spectrum tables (forward, data gradient), three spectra buffers
-// [64 bins][columns][128] (input of the forward - kept for the weight gradient -, input of the data gradient, a scratch one:
-// GEMM output / du blocks of the weight gradient) and the weight gradient's split-K partial products
-extern "C" int64_t eav_conv64_fft_ws_floats(int B, int T) {
-  const Geo g = geometry(B, T, 7);
-  return (int64_t)2 * 64 * 128 * 128 + (int64_t)3 * 64 * g.ncolp * 128 + (int64_t)WCH * 64 * 128 * 128 +
-         (int64_t)64 * 64 * 64 * 2;
-}
+// floats of the workspace of eav_conv64_fft_* (struct Ws)
+extern "C" int64_t eav_conv64_fft_ws_floats(int B, int T) { return carve(nullptr, geometry(B, T, PADF)).floats; }
 
 // rows of stat_part ([rows][128]: 64 sums, 64 sums of squares) eav_conv64_fft_fwd writes
-extern "C" int eav_conv64_fft_nparts(int B, int T) {
-  const Geo g = geometry(B, T, 7);
-  return pack_grid(g) * 4;
-}
+extern "C" int eav_conv64_fft_nparts(int B, int T) { return pack_grid(geometry(B, T, PADF)) * 4; }
 
 // out [B,64,T] = separableConv(in) (bwd = 0, 'same' padding 7 / 8; stat_part as eav_conv64_fwd's, may be NULL) or its data
 // gradient (bwd = 1: in = d loss / d out, out = d loss / d in; bwd = 2: the same, re-using the filter spectra the forward
@@ -642,14 +649,13 @@ extern "C" int eav_conv64_fft_fwd(const float* in, const float* w, float* out, f
                                   int bwd, void* stream) {
   EAV_REQUIRE(in && w && out && ws && B > 0 && T > 0, "eav_conv64_fft_fwd: bad arguments");
   EAV_REQUIRE(((uintptr_t)ws & 15) == 0, "eav_conv64_fft_fwd: the workspace must be 16-byte aligned");
-  const Geo g = geometry(B, T, bwd ? 8 : 7);
+  const Geo g = geometry(B, T, bwd ? PADB : PADF);
   EAV_REQUIRE(bwd >= 0 && bwd <= 2, "eav_conv64_fft_fwd: bwd must be 0, 1 or 2");
   hipStream_t st = (hipStream_t)stream;
-  float* Bm = ws + (bwd ? (int64_t)64 * 128 * 128 : 0);
+  const Ws s = carve(ws, g);
   const bool prepared = bwd == 2;                        // 2: the forward call of this step left the table in ws
   if (bwd == 2) bwd = 1;
-  float* Z = ws + (int64_t)2 * 64 * 128 * 128 + (bwd ? (int64_t)64 * g.ncolp * 128 : 0);
-  float* Y = ws + (int64_t)2 * 64 * 128 * 128 + (int64_t)2 * 64 * g.ncolp * 128;
+  float *Bm = bwd ? s.BmB : s.BmF, *Z = bwd ? s.Zb : s.Zf, *Y = s.Y;
   // forward: both tables (weights do not change between the forward and the backward of a step), as the leading
   // workgroups of the pack launch - a wave per (table, input channel)
   const int nspec = prepared ? 0 : (bwd ? NCH / 4 : 2 * NCH / 4);
@@ -667,12 +673,10 @@ extern "C" int eav_conv64_fft_fwd(const float* in, const float* w, float* out, f
 // same step (a data-gradient call in between does not disturb them).  Bit-reproducible.
 extern "C" int eav_conv64_fft_wgrad(const float* du, float* dW, float* ws, int B, int T, void* stream) {
   EAV_REQUIRE(du && dW && ws && B > 0 && T > 0, "eav_conv64_fft_wgrad: bad arguments");
-  const Geo g = geometry(B, T, 7);
+  const Geo g = geometry(B, T, PADF);
   hipStream_t st = (hipStream_t)stream;
-  float* Z = ws + (int64_t)2 * 64 * 128 * 128;
-  float* D = Z + (int64_t)2 * 64 * g.ncolp * 128;
-  float* Pp = Z + (int64_t)3 * 64 * g.ncolp * 128;
-  float* Acc = Pp + (int64_t)WCH * 64 * 128 * 128;
+  const Ws s = carve(ws, g);
+  float *Z = s.Zf, *D = s.Y, *Pp = s.Pp, *Acc = s.Acc;
   hipLaunchKernelGGL(c64_pack_fft_kernel, dim3(pack_grid(g)), dim3(256), 0, st, du, D, g, 1, nullptr, nullptr, 0, 0);
   EAV_CHECK_LAUNCH("eav_conv64_fft_wgrad(fft)");
   static_assert(128 % (WCH * WKB) == 0, "the padded columns split into WCH chunks of whole K-blocks");
@@ -705,12 +709,8 @@ extern "C" int eav_conv64_fft_bwd(const float* du, const float* dp, const float*
   EAV_REQUIRE(((uintptr_t)ws & 15) == 0, "eav_conv64_fft_bwd: the workspace must be 16-byte aligned");
   const Geo g = geometry(B, T, PADB);
   hipStream_t st = (hipStream_t)stream;
-  float* Bm = ws + (int64_t)64 * 128 * 128;                        // the data gradient's table
-  float* Z = ws + (int64_t)2 * 64 * 128 * 128;                     // the forward's input spectra
-  float* Zb = Z + (int64_t)64 * g.ncolp * 128;
-  float* D = Z + (int64_t)2 * 64 * g.ncolp * 128;                  // = Y below
-  float* Pp = Z + (int64_t)3 * 64 * g.ncolp * 128;
-  float* Acc = Pp + (int64_t)WCH * 64 * 128 * 128;
+  const Ws s = carve(ws, g);
+  float *Bm = s.BmB, *Z = s.Zf, *Zb = s.Zb, *D = s.Y, *Pp = s.Pp, *Acc = s.Acc;      // D: du spectra, then the GEMM output
   const DuSrc src = {dp, u, bn, m12, drop_p, seed, mask, seed_dev};
   if (du)
     hipLaunchKernelGGL(c64_pack_bwd_kernel<false>, dim3(pack_grid(g)), dim3(256), 0, st, du, src, Zb, D, g);

@@ -19,15 +19,17 @@
 //   workgroups in a fixed order and transformed back by a finishing kernel - bit-reproducible run to run.
 //
 // The 1024-point complex FFT runs inside ONE wave, 16 points per lane (element j of lane l = index l + 64 j on input and
-// output), as radix 16 x 16 x 4 with two exchanges through a wave-private LDS buffer:
+// output), as radix 16 x 16 x 4 with one exchange through a wave-private LDS buffer and one between lanes:
 //   n = 64 n1 + 4 n2 + n3,  k = k1 + 16 k2 + 256 k3
 //   (1) radix-16 DFT over n1 in registers (lane = 4 n2 + n3), twiddle W^(lane k1)
-//   (2) exchange: slot 68 k1 + lane  ->  lane' = 4 k1 + n3 reads slots 68 k1 + 4 n2 + n3
-//   (3) radix-16 DFT over n2, twiddle W64^(n3 k2)
-//   (4) exchange: slot k1 + 16 k2 + 260 n3  ->  lane'' reads slots lane'' + 64 m + 260 n3 (m < 4)
-//   (5) radix-4 DFT over n3: X[lane'' + 64 (m + 4 k3)]
-// Every ds_write_b64 / ds_read_b64 of both exchanges is bank-conflict free (pitches 68 and 260 slots - 264 has a 2-way conflict in the 16-lane groups of ds_write_b64; checked offline
-// against the lane groups of MI355X_MICROARCH.md section LDS).  No workgroup barrier inside the transform.
+//   (2) exchange through LDS: slot 66 k1 + lane  ->  lane' = k1 + 16 n3 reads slots 66 k1 + n3 + 4 n2 (n2 < 16)
+//   (3) radix-16 DFT over n2, twiddle W64^(n3 k2): lane' holds k2 = 4 m + r in register 4 m + r
+//   (4) exchange in registers: per m < 4 a 4 x 4 transpose between the lane bits 4-5 (n3) and the register bits 0-1 (r)
+//       by v_permlane32_swap / v_permlane16_swap  ->  lane'' = k1 + 16 r holds n3 in register 4 m + n3
+//   (5) radix-4 DFT over n3: X[lane'' + 64 (m + 4 k3)] in register m + 4 k3
+// Every ds_write_b64 / ds_read_b64 of the LDS exchange is bank-conflict free (pitch 66 slots; checked in
+// tests/test_fir_fft_layout_cpu.py against the lane groups of MI355X_MICROARCH.md section LDS).  No workgroup barrier
+// inside the transform.
 #include <algorithm>
 
 #include "eav_common.h"
@@ -39,59 +41,28 @@ constexpr int F1 = 8;
 constexpr int NF = 1024;        // transform length
 constexpr int LB = 704;         // outputs per block: 11 rows of 64 (2816 B = 22 cache lines, so every block is line aligned)
 constexpr int NROW = LB / 64;   // 11
-#ifdef FFTV_LDSX2
-constexpr int WBUF = 1088;      // float2 slots of a wave's exchange buffer: max(68 x 16, 260 x 3 + 256)
-#else
 constexpr int XP = 66;          // pitch of the exchange rows: reads 66 k1 + n3 (+ 4 n2) cover 32 distinct 8-byte banks
 constexpr int WBUF = 1056;      // float2 slots of a wave's exchange buffer: 66 x 15 + 64, rounded to 128 bytes
-#endif
 constexpr int MAXK = NF - LB + 1;   // 321 taps
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 // y1 / g1 are streamed exactly once by these kernels (614 MB each): non-temporal accesses keep them from evicting the
-// input segments that ARE re-used out of the L2 (-DFFTV_NO_NT: plain accesses, measured 2-4 % slower).
-// FFTV_ABL_NOLOAD / FFTV_ABL_NOFFT: timing-only ablations (results are garbage): the arithmetic side alone / the memory side
-// alone - forward 0.26 / 0.15 ms of 0.28, weight gradient 0.31 / 0.25 ms of 0.39: the transforms, not HBM, are the longer leg.
-#if defined(FFTV_ABL_NOLOAD)
-#define EAV_LDG(p) (1.0f)
-#define EAV_STG(p, v) asm volatile("" ::"v"(v))
-#elif !defined(FFTV_NO_NT)
+// input segments that ARE re-used out of the L2 (plain accesses measured 2-4 % slower).
+// Timing-only ablations (measured once, since removed): the arithmetic side alone (no loads or stores) / the memory side
+// alone (no transforms) - forward 0.26 / 0.15 ms of 0.28, weight gradient 0.31 / 0.25 ms of 0.39: the transforms, not HBM,
+// are the longer leg.
 #define EAV_LDG(p) __builtin_nontemporal_load(p)
 #define EAV_STG(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define EAV_LDG(p) (*(p))
-#define EAV_STG(p, v) (*(p) = (v))
-#endif
 
 __device__ __forceinline__ v2f swp(v2f a) { return __builtin_shufflevector(a, a, 1, 0); }      // (y, x): an op_sel, no move
 __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-// Complex products in forms hipcc maps to v_pk_mul_f32 / v_pk_fma_f32 with op_sel operands only - written as
-// a.xx * b + a.yy * (-b.y, b.x) it builds the swapped / negated pair with a v_xor + v_mov per product (124 of the 454 VALU
-// instructions of one inverse transform + filter product).
-#ifdef FFTV_OLD_ARITH
-__device__ __forceinline__ v2f cmul(v2f a, v2f b) { return a.xx * b + a.yy * (v2f){-b.y, b.x}; }
-__device__ __forceinline__ v2f cmulc(v2f a, v2f b) { return a.xx * (v2f){b.x, -b.y} + a.yy * (v2f){b.y, b.x}; }
-#else
-__device__ __forceinline__ v2f cmul(v2f a, v2f b) {       // a b
-  return fma2(a.yy * (v2f){-1.f, 1.f}, swp(b), a.xx * b);
-}
-__device__ __forceinline__ v2f cmulc(v2f a, v2f b) {      // a conj(b)
-  return fma2(a.yy, swp(b), (a.xx * (v2f){1.f, -1.f}) * b);
-}
-#endif
-#ifndef FFTV_NO_ASM_CMUL
 // Two complex products a0 b0, a1 b1 (CONJ: a conj(b)) in FOUR packed instructions: what hipcc cannot select is one
 // v_pk_fma_f32 with a swapped AND half-negated operand (it builds the pair with a third instruction).  The two products are
 // interleaved so that no packed result is consumed by the next instruction (gfx950 needs one wait state there); the
 // leading s_nop covers a packed producer of an input directly in front of the block, the trailing `s_nop 1` a consumer
 // hipcc schedules directly behind it (the hazard recogniser does not see into inline asm: a v_permlane*_swap of the last
 // result needs two wait states after the VALU write, a packed consumer one).
-#ifdef EAV_FIR_NO_TRAILING_NOP      // (A/B only: round 5's blocks, correct by scheduling luck)
-#define EAV_ASM_TAIL "s_nop 0"
-#else
-#define EAV_ASM_TAIL "s_nop 1"
-#endif
 template <bool CONJ>
 __device__ __forceinline__ void cmul2(v2f a0, v2f b0, v2f a1, v2f b1, v2f& r0, v2f& r1) {
   if (CONJ)
@@ -100,7 +71,7 @@ __device__ __forceinline__ void cmul2(v2f a0, v2f b0, v2f a1, v2f b1, v2f& r0, v
         "v_pk_mul_f32 %1, %4, %5 op_sel_hi:[0,1] neg_hi:[0,1]\n\t"
         "v_pk_fma_f32 %0, %2, %3, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1]\n\t"
         "v_pk_fma_f32 %1, %4, %5, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1]\n\t"
-        EAV_ASM_TAIL
+        "s_nop 1"
         : "=&v"(r0), "=&v"(r1) : "v"(a0), "v"(b0), "v"(a1), "v"(b1));
   else
     asm("s_nop 0\n\t"
@@ -108,7 +79,7 @@ __device__ __forceinline__ void cmul2(v2f a0, v2f b0, v2f a1, v2f b1, v2f& r0, v
         "v_pk_mul_f32 %1, %4, %5 op_sel_hi:[0,1]\n\t"
         "v_pk_fma_f32 %0, %2, %3, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"
         "v_pk_fma_f32 %1, %4, %5, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"
-        EAV_ASM_TAIL
+        "s_nop 1"
         : "=&v"(r0), "=&v"(r1) : "v"(a0), "v"(b0), "v"(a1), "v"(b1));
 }
 // acc0 += a0 conj(b0), acc1 += a1 conj(b1): four packed fmas, the accumulators interleaved for the same reason
@@ -118,40 +89,25 @@ __device__ __forceinline__ void cmacc2_conj(v2f a0, v2f b0, v2f a1, v2f b1, v2f&
       "v_pk_fma_f32 %1, %4, %5, %1 op_sel_hi:[0,1,1] neg_hi:[0,1,0]\n\t"
       "v_pk_fma_f32 %0, %2, %3, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1]\n\t"
       "v_pk_fma_f32 %1, %4, %5, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1]\n\t"
-      EAV_ASM_TAIL
+      "s_nop 1"
       : "+v"(acc0), "+v"(acc1) : "v"(a0), "v"(b0), "v"(a1), "v"(b1));
 }
-#endif
 
-// a w (forward) / a conj(w) (inverse) for a twiddle w: the w-only factors are loop invariants the compiler keeps in
-// registers, which leaves two instructions per product
+// a w (forward) / a conj(w) (inverse) for a twiddle w, in a form hipcc maps to v_pk_mul_f32 / v_pk_fma_f32 with op_sel
+// operands only (written as a.xx * w + a.yy * (-w.y, w.x) it builds the swapped / negated pair with a v_xor + v_mov per
+// product): the w-only factors are loop invariants the compiler keeps in registers, which leaves two instructions per product
 template <bool INV>
 __device__ __forceinline__ v2f twmul(v2f a, v2f w) {
-#ifdef FFTV_OLD_ARITH
-  return INV ? cmulc(a, w) : cmul(a, w);
-#else
   return fma2(w.yy * (INV ? (v2f){1.f, -1.f} : (v2f){-1.f, 1.f}), swp(a), w.xx * a);
-#endif
 }
 // multiply by -i (forward) / +i (inverse)
 template <bool INV>
 __device__ __forceinline__ v2f rot(v2f a) {
-#ifdef FFTV_OLD_ARITH
-  return INV ? (v2f){-a.y, a.x} : (v2f){a.y, -a.x};
-#else
   return swp(a) * (INV ? (v2f){-1.f, 1.f} : (v2f){1.f, -1.f});
-#endif
 }
 
 template <bool INV>
 __device__ __forceinline__ void dft4(v2f& a0, v2f& a1, v2f& a2, v2f& a3) {
-#ifdef FFTV_OLD_ARITH
-  const v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, t3 = rot<INV>(a1 - a3);
-  a0 = t0 + t2;
-  a1 = t1 + t3;
-  a2 = t0 - t2;
-  a3 = t1 - t3;
-#else
   // t1 +- rot(d) = fma(swap(d), (1, -1), t1): the rotation rides on the add (exact: the factors are +-1)
   const v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, d = swp(a1 - a3);
   const v2f c = INV ? (v2f){-1.f, 1.f} : (v2f){1.f, -1.f};
@@ -159,7 +115,6 @@ __device__ __forceinline__ void dft4(v2f& a0, v2f& a1, v2f& a2, v2f& a3) {
   a1 = fma2(d, c, t1);
   a2 = t0 - t2;
   a3 = fma2(d, -c, t1);
-#endif
 }
 
 // 16-point DFT in registers: n = 4 a + b, k = c + 4 d; X[c + 4 d] = sum_b W16^(b c) W4^(b d) sum_a v[4 a + b] W4^(a c)
@@ -190,28 +145,16 @@ __device__ __forceinline__ void dft16(v2f (&v)[16]) {
   for (int k = 0; k < 16; ++k) v[k] = o[k];
 }
 
-// after dft4 over the a index the results sit at v[4 c + b]: the first loop above writes y[b][c] into (v[b], v[4 + b],
-// v[8 + b], v[12 + b]) = positions 4 c + b.  (kept as a comment: the index bookkeeping is the easy thing to get wrong)
-
-// Twiddle tables of a workgroup in LDS (16 KB): t1[k][lane] = W1024^(lane k), t2[k][lane] = W64^((lane & 3) k) - one
+// Twiddle tables of a workgroup in LDS (8.5 KB): t1[k][lane] = W1024^(lane k), t2[k][n3] = W64^(n3 k) - one
 // conflict-free ds_read_b64 per use instead of 64 resident VGPRs (with them the forward kernel spilled 68 registers).
-#ifdef FFTV_LDSX2
-constexpr int TWSZ = 2 * 16 * 64;
-#else
 constexpr int TWSZ = 16 * 64 + 16 * 4;
-#endif
 
 __device__ __forceinline__ void make_twiddles(v2f* __restrict__ twl) {      // 512 threads: one entry each, twice
   for (int i = threadIdx.x; i < TWSZ; i += blockDim.x) {
     float s, c;
-#ifdef FFTV_LDSX2
-    const int which = i >> 10, k = (i >> 6) & 15, lane = i & 63;
-    if (which == 0) sincospif((float)(lane * k) * (1.0f / 512.0f), &s, &c);      // 2 pi m / 1024 = pi (m / 512), m exact
-    else sincospif((float)((lane & 3) * k) * (1.0f / 32.0f), &s, &c);            // 2 pi m / 64
-#else
+    // 2 pi m / 1024 = pi (m / 512), 2 pi m / 64 = pi (m / 32): m exact
     if (i < 1024) sincospif((float)((i & 63) * (i >> 6)) * (1.0f / 512.0f), &s, &c);      // t1[k][lane] = W1024^(lane k)
     else sincospif((float)(((i - 1024) & 3) * ((i - 1024) >> 2)) * (1.0f / 32.0f), &s, &c);      // t2[k][n3] = W64^(n3 k)
-#endif
     twl[i] = (v2f){c, -s};
   }
   __syncthreads();
@@ -220,64 +163,15 @@ __device__ __forceinline__ void make_twiddles(v2f* __restrict__ twl) {      // 5
 // LDS reads as single ds_read_b64 (2 LDS cycles per wave-instruction): left alone, hipcc pairs them into ds_read2_b64 /
 // ds_read2st64_b64, which the LDS serves as two 4 x 16-lane accesses = 8 cycles for the same 16 bytes per lane
 // (MI355X_MICROARCH.md, LDS table).  A volatile access is the one form its load-store optimiser leaves alone.
-#ifdef FFTV_READ2
-__device__ __forceinline__ v2f lds_ld(const v2f* p) { return *p; }
-#else
 typedef const volatile __attribute__((address_space(3))) v2f* lds_cvp;
 __device__ __forceinline__ v2f lds_ld(const v2f* p) { return *(lds_cvp)p; }
-#endif
 
-// The exchanges need no hardware wait between a wave's writes and its own reads: the LDS executes one wave's DS
+// The exchange needs no hardware wait between a wave's writes and its own reads: the LDS executes one wave's DS
 // instructions in issue order, and the transform is private to the wave.  What is needed is that the COMPILER keeps the
 // order (a "memory" clobber); it then places counted lgkmcnt waits in front of the first use of each read by itself, so the
-// butterflies start on the first rows while the last ones are still in flight (-DFFTV_HWWAIT: the round-4 form, a full
-// lgkmcnt(0) drain after the writes and again after the reads).
-#ifdef FFTV_HWWAIT
-#define FFT_ORDER() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
+// butterflies start on the first rows while the last ones are still in flight.
 #define FFT_ORDER() asm volatile("" ::: "memory")
-#endif
 
-// In-wave 1024-point FFT: v[j] = x[lane + 64 j] -> v[j] = X[lane + 64 j].  INV: conjugate twiddles, no 1/N.
-#ifdef FFTV_LDSX2
-template <bool INV>
-__device__ __forceinline__ void fft1024(v2f (&v)[16], v2f* __restrict__ xb, int lane, const v2f* __restrict__ twl) {
-#ifdef FFTV_ABL_NOFFT
-  return;
-#endif
-  const v2f* t1 = twl + lane;
-  const v2f* t2 = twl + 1024 + lane;
-  dft16<INV>(v);
-#pragma unroll
-  for (int k = 1; k < 16; ++k) v[k] = twmul<INV>(v[k], lds_ld(t1 + 64 * k));
-#pragma unroll
-  for (int k = 0; k < 16; ++k) xb[68 * k + lane] = v[k];
-  FFT_ORDER();
-  {
-    const v2f* rp = xb + 68 * (lane >> 2) + (lane & 3);
-#pragma unroll
-    for (int n2 = 0; n2 < 16; ++n2) v[n2] = lds_ld(rp + 4 * n2);
-  }
-  FFT_ORDER();
-  dft16<INV>(v);
-#pragma unroll
-  for (int k = 1; k < 16; ++k) v[k] = twmul<INV>(v[k], lds_ld(t2 + 64 * k));
-  {
-    v2f* wp = xb + (lane >> 2) + 260 * (lane & 3);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) wp[16 * k] = v[k];
-  }
-  FFT_ORDER();
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    v2f u0 = lds_ld(xb + lane + 64 * m), u1 = lds_ld(xb + lane + 64 * m + 260), u2 = lds_ld(xb + lane + 64 * m + 520),
-        u3 = lds_ld(xb + lane + 64 * m + 780);
-    dft4<INV>(u0, u1, u2, u3);
-    v[m] = u0; v[m + 4] = u1; v[m + 8] = u2; v[m + 12] = u3;
-  }
-  FFT_ORDER();
-}
-#else
 // exchange a[lanes 32-63] with b[lanes 0-31] / a[lanes 16-31, 48-63] with b[lanes 0-15, 32-47]: one step of a transpose
 // between a lane bit and a register-index bit, both directions in ONE instruction, no LDS
 __device__ __forceinline__ void swap32(v2f& a, v2f& b) {
@@ -293,22 +187,15 @@ __device__ __forceinline__ void swap16(v2f& a, v2f& b) {
   b = (v2f){__uint_as_float(rx[1]), __uint_as_float(ry[1])};
 }
 
+// In-wave 1024-point FFT: v[j] = x[lane + 64 j] -> v[j] = X[lane + 64 j].  INV: conjugate twiddles, no 1/N.
 template <bool INV>
 __device__ __forceinline__ void fft1024(v2f (&v)[16], v2f* __restrict__ xb, int lane, const v2f* __restrict__ twl) {
-#ifdef FFTV_ABL_NOFFT
-  return;
-#endif
   const v2f* t1 = twl + lane;
   const v2f* t2 = twl + 1024 + (lane >> 4);
   dft16<INV>(v);
-#ifndef FFTV_NO_ASM_CMUL
   v[1] = twmul<INV>(v[1], lds_ld(t1 + 64));
 #pragma unroll
   for (int k = 2; k < 16; k += 2) cmul2<INV>(v[k], lds_ld(t1 + 64 * k), v[k + 1], lds_ld(t1 + 64 * k + 64), v[k], v[k + 1]);
-#else
-#pragma unroll
-  for (int k = 1; k < 16; ++k) v[k] = twmul<INV>(v[k], lds_ld(t1 + 64 * k));
-#endif
 #pragma unroll
   for (int k = 0; k < 16; ++k) xb[XP * k + lane] = v[k];
   FFT_ORDER();
@@ -319,14 +206,9 @@ __device__ __forceinline__ void fft1024(v2f (&v)[16], v2f* __restrict__ xb, int 
   }
   FFT_ORDER();
   dft16<INV>(v);
-#ifndef FFTV_NO_ASM_CMUL
   v[1] = twmul<INV>(v[1], lds_ld(t2 + 4));
 #pragma unroll
   for (int k = 2; k < 16; k += 2) cmul2<INV>(v[k], lds_ld(t2 + 4 * k), v[k + 1], lds_ld(t2 + 4 * k + 4), v[k], v[k + 1]);
-#else
-#pragma unroll
-  for (int k = 1; k < 16; ++k) v[k] = twmul<INV>(v[k], lds_ld(t2 + 4 * k));
-#endif
   // lane 16 n3 + k1 holds k2 = 4 m + r in register 4 m + r; the 4 x 4 transposes put n3 into the register index:
   // lane 16 r + k1, register 4 m + n3
   v2f o[16];
@@ -341,24 +223,6 @@ __device__ __forceinline__ void fft1024(v2f (&v)[16], v2f* __restrict__ xb, int 
   }
 #pragma unroll
   for (int k = 0; k < 16; ++k) v[k] = o[k];
-}
-#endif
-
-// Sum of a over the wave as a wave-uniform value: in-row inclusive scan (row_shr 1, 2, 4, 8), row totals carried by the
-// two row broadcasts, total read from lane 63 - DPP operands only.  (__shfl_xor butterflies compile to six DEPENDENT
-// ds_bpermute round trips, ~600 cycles of LDS latency at the end of every filter iteration of the forward kernel.)
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ float dpp_mov(float src) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(src), CTRL, ROW_MASK, 0xf, BOUND));
-}
-__device__ __forceinline__ float wave_total(float a) {
-  a += dpp_mov<0x111, 0xf, true>(a);      // row_shr:1
-  a += dpp_mov<0x112, 0xf, true>(a);      // row_shr:2
-  a += dpp_mov<0x114, 0xf, true>(a);      // row_shr:4
-  a += dpp_mov<0x118, 0xf, true>(a);      // row_shr:8
-  a += dpp_mov<0x142, 0xa, false>(a);     // row_bcast:15 into rows 1 and 3
-  a += dpp_mov<0x143, 0xc, false>(a);     // row_bcast:31 into rows 2 and 3
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63));
 }
 
 // segment of one electrode pair: v[j] = x[c0][t0 - padl + lane + 64 j] + i x[c0 + 1][...].  Interior segments of a full
@@ -385,11 +249,7 @@ __device__ __forceinline__ void load_segment(v2f (&v)[16], const float* __restri
 // SIMD) share the 8 filter spectra H_f = conj(FFT(w_f)) / 1024, computed by the workgroup itself (wave f < 8 transforms
 // filter f).  The filters are real, so H_f[1024 - k] = conj(H_f[k]): only bins 0 .. 512 are kept (33 KB instead of 64 KB -
 // what makes room for the exchange buffers of 12 waves), rows j >= 8 of a lane read the mirrored bin and conjugate.
-#ifdef FFTV_W8
-constexpr int NWF = 8;
-#else
 constexpr int NWF = 12;
-#endif
 constexpr int HB = 520;         // float2 slots per filter: bins 0 .. 512, padded to a multiple of 64 bytes
 
 template <bool STATS>
@@ -442,18 +302,11 @@ __global__ __launch_bounds__(64 * NWF, 1) void fir_fft_fwd_kernel(const float* _
     for (int f = 0; f < F1; ++f) {
       const v2f* hp = Hs + f * HB + lane;       // bins lane + 64 j, j < 8
       const v2f* hm = Hs + f * HB - lane;       // bins 1024 - (lane + 64 j), j >= 8: the conjugates
-#ifndef FFTV_NO_ASM_CMUL
 #pragma unroll
       for (int j = 0; j < 8; j += 2) cmul2<false>(z[j], lds_ld(hp + 64 * j), z[j + 1], lds_ld(hp + 64 * j + 64), v[j], v[j + 1]);
 #pragma unroll
       for (int j = 8; j < 16; j += 2)
         cmul2<true>(z[j], lds_ld(hm + (NF - 64 * j)), z[j + 1], lds_ld(hm + (NF - 64 * j - 64)), v[j], v[j + 1]);
-#else
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = cmul(z[j], lds_ld(hp + 64 * j));
-#pragma unroll
-      for (int j = 8; j < 16; ++j) v[j] = cmulc(z[j], lds_ld(hm + (NF - 64 * j)));
-#endif
       fft1024<true>(v, xb, lane, tw);
       float* dst = y1 + (((int64_t)b * F1 + f) * C + c0) * S + t0 + lane;
       float a1, a2;
@@ -503,8 +356,8 @@ __global__ __launch_bounds__(64 * NWF, 1) void fir_fft_fwd_kernel(const float* _
           }
         }
       }
-      a1 = wave_total(a1);
-      a2 = wave_total(a2);
+      a1 = wave_total_dpp(a1);
+      a2 = wave_total_dpp(a2);
       if (lane == f) sacc += a1;
       if (lane == 8 + f) sacc += a2;
     }
@@ -624,13 +477,8 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
       for (int j = NROW; j < 16; ++j) v[j] = (v2f){0.f, 0.f};
       fft1024<false>(v, xb, lane, tw);
       const v2f* zp = zb + uu * NF + lane;
-#ifndef FFTV_NO_ASM_CMUL
 #pragma unroll
       for (int j = 0; j < 16; j += 2) cmacc2_conj(lds_ld(zp + 64 * j), v[j], lds_ld(zp + 64 * j + 64), v[j + 1], acc[j], acc[j + 1]);
-#else
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[j] += cmulc(lds_ld(zp + 64 * j), v[j]);
-#endif
 #pragma unroll
       for (int j = 0; j < NROW; ++j) {       // (after the transform: the copy is what waits for the loads)
         cg[j] = ng[j];
@@ -696,9 +544,6 @@ int fft_units(int B, int C, int S, int* npair, int* nblk) {
 // more rounds than 256 workgroups would (14400 units = 1800 rounds-of-8: 225 workgroups x 8 rounds, no partial round)
 int fft_grid(int nunits, int per_wg) {
   const int items = cdiv(nunits, per_wg);
-#ifdef FFTV_G256
-  return std::max(1, std::min(256, items));
-#endif
   if (items <= 256) return std::max(1, items);
   const int rounds = cdiv(items, 256);
   return cdiv(items, rounds);

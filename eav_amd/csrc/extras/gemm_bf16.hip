@@ -26,8 +26,6 @@ struct GemmArgs {
   int gelu, accumulate, ksplit;
 };
 
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // K-contiguous operand (stored [R,K]): 8 consecutive k of row r -> bf16x8
@@ -197,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
         float v = g.alpha * acc[a][b][r] + bias;
         const int64_t o = (int64_t)row * g.ldc + col;
         if (g.pre) g.pre[zb * g.sCb + zh * g.sCh + o] = v;
-        if (g.gelu) v = gelu_erf(v);
+        if (g.gelu) v = gelu_erf_libm(v);
         if (g.resid) v += g.resid[(int64_t)row * g.ldr + col];
         if (g.accumulate) v += C[o];
         C[o] = v;

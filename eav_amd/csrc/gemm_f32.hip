@@ -43,8 +43,6 @@ struct GemmArgs {
   int ksplit;           // > 0: split-K mode - slice z covers k in [z*ksplit, min(K, (z+1)*ksplit)), C[z] = partial
 };
 
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-
 // load a float4 of 4 consecutive elements along the contiguous axis with bounds handling
 __device__ __forceinline__ float4 ld_guard(const float* p, int64_t off, int i, int n, bool rowok) {
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -248,7 +246,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_kernel(GemmArgs g) {
       }
       if (g.gelu) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = gelu_erf(v[r]);
+        for (int r = 0; r < 16; ++r) v[r] = gelu_erf_libm(v[r]);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r)

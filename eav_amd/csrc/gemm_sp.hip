@@ -963,15 +963,6 @@ __global__ __launch_bounds__(256) void sp_absmax_multi_kernel(const PlaneJob* __
   sp_absmax_body(j.src, j.R, j.C >> 2, j.C, reinterpret_cast<unsigned*>(j.slot), blockIdx.z & 3);
 }
 
-// sigma = 2^(14 - floor(log2 amax)): max|sigma v| in [2^14, 2^15); 1 for an all-zero / non-finite tensor
-__device__ __forceinline__ float sigma_from_bits(unsigned bits) {
-  const int e = (int)((bits >> 23) & 0xff);
-  if (bits == 0u || e == 0xff) return 1.f;
-  int se = 14 - (e - 127);
-  se = max(-126, min(126, se));
-  return __uint_as_float((unsigned)(se + 127) << 23);
-}
-
 __device__ __forceinline__ void split8(const float (&tv)[8], uint4& hi, uint4& lo, float lomul) {
   _Float16 h[8], l[8];
 #pragma unroll

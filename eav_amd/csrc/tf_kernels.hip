@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 }
 
 __device__ __forceinline__ float sigma_of_bound(float b) {
-  // the power of two that puts b in [2^14, 2^15) (as sigma_from_bits in gemm_sp.hip); 1 for 0 / non-finite
+  // the power of two that puts b in [2^14, 2^15) (as sigma_from_bits, eav_common.h); 1 for 0 / non-finite
   const unsigned bits = __float_as_uint(b);
   const int e = (int)((bits >> 23) & 0xff);
   if (b <= 0.f || e == 0xff) return 1.f;

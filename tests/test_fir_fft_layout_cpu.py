@@ -1,13 +1,14 @@
 """The index arithmetic of csrc/eegnet_fir_fft.hip, restated in numpy and checked on the CPU: the in-wave 1024-point FFT
-(radix 16 x 16 x 4, 16 points per lane, two exchanges through LDS slots), the bank-conflict freedom of both exchanges under
-the MI355X lane-group rules (ds_write_b64: groups of 16 lanes over 32 banks of 4 B, ds_read_b64: groups of 32 lanes over 64
-banks), and the two frequency-domain identities the kernels rest on (overlap-save correlation for the forward; the
-conjugate-product accumulation for the weight gradient, with two electrodes packed into one complex signal).
+(radix 16 x 16 x 4, 16 points per lane, one exchange through LDS slots and one by v_permlane32_swap / v_permlane16_swap
+transposes between lanes and registers), the bank-conflict freedom of the LDS exchange under the MI355X lane-group rules
+(ds_write_b64: groups of 16 lanes over 32 banks of 4 B, ds_read_b64: groups of 32 lanes over 64 banks), and the two
+frequency-domain identities the kernels rest on (overlap-save correlation for the forward; the conjugate-product
+accumulation for the weight gradient, with two electrodes packed into one complex signal).
 Reference ops: nn.Conv2d(1, 8, (1, 300), padding='same') and its weight gradient - CNN_torch/EEGNet_tor.py:24,51,109."""
 import numpy as np
 
 N, LB, K = 1024, 704, 300
-P1, P2 = 68, 260          # slot pitches of the two exchanges (eegnet_fir_fft.hip: fft1024)
+XP, WBUF = 66, 1056       # slot pitch of the LDS exchange, slots of a wave's buffer (eegnet_fir_fft.hip: fft1024)
 
 
 def W(m):
@@ -35,10 +36,25 @@ def dft16(v, inv):
     return X
 
 
+def swap32(a, b):
+    """v_permlane32_swap on arrays of 64 lanes, in place: a[lanes 32-63] <-> b[lanes 0-31]."""
+    t = a[32:].copy()
+    a[32:] = b[:32]
+    b[:32] = t
+
+
+def swap16(a, b):
+    """v_permlane16_swap, in place: a[lanes 16-31, 48-63] <-> b[lanes 0-15, 32-47]."""
+    for lo in (0, 32):
+        t = a[lo + 16:lo + 32].copy()
+        a[lo + 16:lo + 32] = b[lo:lo + 16]
+        b[lo:lo + 16] = t
+
+
 def fft1024(x, inv=False):
     """Lane l holds x[l + 64 j] in register j on input and X[l + 64 j] on output - the kernel's layout."""
     regs = [[x[lane + 64 * j] for j in range(16)] for lane in range(64)]
-    lds = np.zeros(1088, complex)
+    lds = np.zeros(WBUF, complex)
     for lane in range(64):
         regs[lane] = dft16(regs[lane], inv)
         for k1 in range(16):
@@ -46,23 +62,24 @@ def fft1024(x, inv=False):
             regs[lane][k1] *= np.conj(t) if inv else t
     for lane in range(64):
         for k1 in range(16):
-            lds[P1 * k1 + lane] = regs[lane][k1]
+            lds[XP * k1 + lane] = regs[lane][k1]
     for lane in range(64):
-        regs[lane] = [lds[P1 * (lane >> 2) + 4 * n2 + (lane & 3)] for n2 in range(16)]
+        regs[lane] = [lds[XP * (lane & 15) + (lane >> 4) + 4 * n2] for n2 in range(16)]
     for lane in range(64):
         regs[lane] = dft16(regs[lane], inv)
         for k2 in range(16):
-            t = W(16 * (lane & 3) * k2)
+            t = W(16 * (lane >> 4) * k2)
             regs[lane][k2] *= np.conj(t) if inv else t
-    for lane in range(64):
-        for k2 in range(16):
-            lds[(lane >> 2) + 16 * k2 + P2 * (lane & 3)] = regs[lane][k2]
+    v = [np.array([regs[lane][k] for lane in range(64)]) for k in range(16)]      # v[register][lane]
     X = np.zeros(N, complex)
-    for lane in range(64):
-        for m in range(4):
-            r = dft4([lds[lane + 64 * m + P2 * n3] for n3 in range(4)], inv)
-            for k3 in range(4):
-                X[lane + 64 * (m + 4 * k3)] = r[k3]
+    for m in range(4):
+        swap32(v[4 * m], v[4 * m + 2])
+        swap32(v[4 * m + 1], v[4 * m + 3])
+        swap16(v[4 * m], v[4 * m + 1])
+        swap16(v[4 * m + 2], v[4 * m + 3])
+        r = dft4(v[4 * m:4 * m + 4], inv)
+        for k3 in range(4):                                                       # register m + 4 k3 of every lane
+            X[np.arange(64) + 64 * (m + 4 * k3)] = r[k3]
     return X
 
 
@@ -81,18 +98,12 @@ def _ways(slots, group, banks_in_slots):
     return worst
 
 
-def test_both_exchanges_are_bank_conflict_free():
+def test_lds_exchange_is_bank_conflict_free():
     # 8-byte slots: a ds_write_b64 group of 16 lanes covers 32 banks = 16 slots, a ds_read_b64 group of 32 lanes 64 banks = 32 slots
     for k in range(16):
-        assert _ways([P1 * k + lane for lane in range(64)], 16, 16) == 1
-        assert _ways([P1 * (lane >> 2) + 4 * k + (lane & 3) for lane in range(64)], 32, 32) == 1
-        assert _ways([(lane >> 2) + 16 * k + P2 * (lane & 3) for lane in range(64)], 16, 16) == 1
-    for m in range(4):
-        for n3 in range(4):
-            assert _ways([lane + 64 * m + P2 * n3 for lane in range(64)], 32, 32) == 1
-    assert max(P1 * 15 + 63, 15 + 16 * 15 + P2 * 3) < 1088          # both images fit the wave's exchange buffer
-    # (the first choice of the second pitch, 264, is 2-way conflicted on the writes: the reason for 260)
-    assert max(_ways([(lane >> 2) + 16 * k + 264 * (lane & 3) for lane in range(64)], 16, 16) for k in range(16)) == 2
+        assert _ways([XP * k + lane for lane in range(64)], 16, 16) == 1
+        assert _ways([XP * (lane & 15) + (lane >> 4) + 4 * k for lane in range(64)], 32, 32) == 1
+    assert XP * 15 + 63 < WBUF                                       # the image fits the wave's exchange buffer
 
 
 def test_overlap_save_identities():
