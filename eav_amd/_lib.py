@@ -124,6 +124,7 @@ SIGNATURES = {
     "eav_pair_mean": [_p, _p, _i, _i, _i, _p],
     "eav_ast_fbank": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _d, _f, _f, _p],
     "eav_decimate_fir_f64": [_p, _p, _p, _i, _i64, _i64, _i, _i, _i, _p],
+    "eav_resample_poly_f64": [_p, _p, _p, _i, _i64, _i64, _i, _i, _i, _i, _p],
     "eav_sosfilt_f64": [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _p],
     "eav_resample_sinc_f32": [_p, _p, _p, _i, _i64, _i64, _i, _i, _i, _i, _p],
     "eav_eegnet_block1_infer": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],

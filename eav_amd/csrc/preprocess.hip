@@ -276,6 +276,98 @@ extern "C" int eav_sosfilt_f64(const double* x, double* y, const double* sos, co
 }
 
 // ------------------------------------------------------------------------------------------------
+// Rational-rate EEG resampling: scipy.signal.resample_poly(x, up, down, axis=1) in float64, centred form
+//   y[c][m] = sum_i h[b - i*up] * x[c][i],   b = m*down + center,   over 0 <= i < n_in with 0 <= b - i*up < ntaps
+// (h already carries the factor `up`; scipy's n_pre_pad / n_pre_remove collapse to `center`).  One thread owns one
+// output and walks its inputs in ascending i - one fma chain, no atomics, the same bits on every run.
+// A workgroup of 256 consecutive outputs needs the inputs [i0, i0 + tile), i0 = max(0, ceil((b0 - ntaps + 1) / up)),
+// tile <= (255*down + ntaps - 1)/up + 2; the host stages the tap table in LDS when ntaps <= RP_LDS_DOUBLES and the
+// input tile when it fits what is left of the 64 KiB (loads are clamped into the record, tile slots beyond it
+// hold 0: no padded copy).  What does not fit is read from global memory by the same loop.  Sample and output
+// indices are 64-bit.
+namespace {
+
+constexpr int RP_LDS_DOUBLES = 8192;       // 64 KiB of LDS per workgroup
+
+template <bool TAPS_LDS, bool X_LDS>
+__global__ __launch_bounds__(256) void resample_poly_kernel(const double* __restrict__ x, const double* __restrict__ h,
+                                                            double* __restrict__ y, int64_t n_in, int64_t n_out, int up,
+                                                            int down, int ntaps, int center, int tile) {
+  extern __shared__ __attribute__((aligned(16))) double rp_lds[];
+  double* hl = rp_lds;                                   // [ntaps]  (TAPS_LDS)
+  double* xl = rp_lds + (TAPS_LDS ? ntaps : 0);          // [tile]   (X_LDS)
+  const int tid = threadIdx.x;
+  const double* xr = x + (int64_t)blockIdx.y * n_in;
+  const int64_t m0 = (int64_t)blockIdx.x * 256;
+  const int64_t lo0 = m0 * down + center - (ntaps - 1);
+  const int64_t i0 = lo0 <= 0 ? 0 : (lo0 + up - 1) / up;   // first input any output of this workgroup reads
+  // staging, four loads in flight per thread: the address is clamped into the array, so every load is unconditional and
+  // none waits for the one before it; a tile slot beyond the record is set to 0 (no output reads it: ihi < n_in)
+  if (TAPS_LDS)
+    for (int k0 = tid; k0 < ntaps; k0 += 4 * 256) {
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = h[min(k0 + u * 256, ntaps - 1)];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (k0 + u * 256 < ntaps) hl[k0 + u * 256] = v[u];
+    }
+  if (X_LDS)
+    for (int j0 = tid; j0 < tile; j0 += 4 * 256) {
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = xr[min(i0 + j0 + u * 256, n_in - 1)];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (j0 + u * 256 < tile) xl[j0 + u * 256] = i0 + j0 + u * 256 < n_in ? v[u] : 0.0;
+    }
+  if (TAPS_LDS || X_LDS) __syncthreads();
+  const int64_t m = m0 + tid;
+  if (m >= n_out) return;
+  const int64_t b = m * down + center;
+  const int64_t lo = b - (ntaps - 1);
+  const int64_t ilo = lo <= 0 ? 0 : (lo + up - 1) / up;    // >= i0: lo >= lo0
+  const int64_t ihi = min(n_in - 1, b / up);               // < i0 + tile where it is < n_in
+  auto tap = [&](int k) { if constexpr (TAPS_LDS) return hl[k]; else return h[k]; };
+  auto sample = [&](int64_t i) { if constexpr (X_LDS) return xl[(int)(i - i0)]; else return xr[i]; };
+  int k = (int)(b - ilo * up);                             // <= ntaps - 1: ilo*up >= lo; the last one, b - ihi*up, is >= 0
+  double acc = 0.0;
+  for (int64_t i = ilo; i <= ihi; ++i, k -= up) acc = fma(tap(k), sample(i), acc);
+  y[(int64_t)blockIdx.y * n_out + m] = acc;
+}
+
+}  // namespace
+
+extern "C" int eav_resample_poly_f64(const double* x, const double* h, double* y, int nch, int64_t n_in, int64_t n_out,
+                                     int up, int down, int ntaps, int center, void* stream) {
+  EAV_REQUIRE(x && h && y, "eav_resample_poly_f64: null pointer");
+  EAV_REQUIRE(nch > 0 && nch <= 65535 && n_in > 0 && n_out > 0 && up > 0 && down > 0 && ntaps > 0,
+              "eav_resample_poly_f64: sizes, up and down must be positive (nch <= 65535)");
+  EAV_REQUIRE(center >= 0 && center < ntaps && ntaps <= (1 << 30), "eav_resample_poly_f64: center %d outside the %d taps (at most 2^30)",
+              center, ntaps);
+  EAV_REQUIRE(n_in <= (INT64_MAX / 4) / up && n_out == (n_in * up + down - 1) / down,
+              "eav_resample_poly_f64: n_out %lld is not ceil(n_in * up / down) for n_in %lld", (long long)n_out,
+              (long long)n_in);
+  const int64_t nblk = cdiv64(n_out, 256);
+  EAV_REQUIRE(nblk <= INT32_MAX, "eav_resample_poly_f64: %lld workgroups", (long long)nblk);
+  const bool taps_lds = ntaps <= RP_LDS_DOUBLES;
+  const int64_t tile = (255 * (int64_t)down + ntaps - 1) / up + 2;
+  const bool x_lds = tile <= RP_LDS_DOUBLES - (taps_lds ? ntaps : 0);
+  const size_t lds = ((taps_lds ? (size_t)ntaps : 0) + (x_lds ? (size_t)tile : 0)) * sizeof(double);
+  dim3 grid((unsigned)nblk, nch);
+#define EAV_RP_LAUNCH(T, X)                                                                                             \
+  hipLaunchKernelGGL((resample_poly_kernel<T, X>), grid, dim3(256), lds, (hipStream_t)stream, x, h, y, n_in, n_out, up, \
+                     down, ntaps, center, (int)(x_lds ? tile : 0))
+  if (taps_lds && x_lds) EAV_RP_LAUNCH(true, true);
+  else if (taps_lds) EAV_RP_LAUNCH(true, false);
+  else if (x_lds) EAV_RP_LAUNCH(false, true);
+  else EAV_RP_LAUNCH(false, false);
+#undef EAV_RP_LAUNCH
+  EAV_CHECK_LAUNCH("eav_resample_poly_f64");
+  return EAV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Audio resampling (Dataload_audio.py:40-45 -> torchaudio.transforms.Resample, sinc_interp_hann): a polyphase FIR,
 //   y[f*nw + p] = sum_j taps[p][j] * xp[f*orig + j],   xp = x with `width` zeros in front and width + orig behind.
 // Banded form: tap j of phase p sits at t = ((j - width) / orig - p / nw) * base and the design clamps t to

@@ -1,18 +1,23 @@
 """DataLoadEEG on MI355X - the reference's EEG pre-processing class (Dataload_eeg.py:35-160), same
 constructor, methods and outputs, with the two data-heavy stages on the GPU in float64:
 
-    downsampling()      scipy.signal.resample_poly(x, 1, fs_orig/fs_target)  -> eav_decimate_fir_f64
+    downsampling()      scipy.signal.resample_poly(x, up, down), up/down = fs_target/fs_orig reduced
+                        -> eav_decimate_fir_f64 (up == 1) / eav_resample_poly_f64 (any other ratio)
     bandpass_filter()   butter(5, band, 'bandpass', output='sos') + sosfilt    -> eav_sosfilt_f64
 
-Filter *design* (101-tap Kaiser-windowed sinc; 5th-order Butterworth sections) stays on the host - it is a
+Filter *design* (Kaiser-windowed sinc of 20 max(up, down) + 1 taps; 5th-order Butterworth sections) stays on the host - it is a
 few hundred flops - and follows scipy's published formulas (firwin / resample_poly, butter via scipy itself,
 which is the reference's own dependency, requirements.txt).  `prepare_data()` returns what the reference
 returns: (seg_f_div float64 [N, ch, 500], label_div int64 [N]); labels keep the reference's values
 (argmax over the 10 one-hot rows, i.e. 1,3,5,7,9 - SURVEY Q8); `remap_labels=True` maps them to 0..4.
+`window_seconds` (keyword only) gives the windows in seconds instead of the reference's fixed 500 samples, and
+`feature_dev` keeps the selected windows on the device as float32 [N, ch, win] for the trainers.
 """
 from __future__ import annotations
 
+import math
 import os
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -40,10 +45,13 @@ def read_subject_recording(parent_directory, subject):
 
 
 def resample_poly_design(up, down):
-    """(h float64, center, n_out(n_in)) of scipy.signal.resample_poly(x, up, down) for up == 1:
-    y[m] = sum_j h[j] x[m*down + center - j]  (window ('kaiser', 5.0), half_len = 10*max(up,down))."""
-    if up != 1:
-        raise NotImplementedError("only pure decimation (up == 1) is implemented")
+    """(h float64 already times up, center = half_len) of scipy.signal.resample_poly(x, up, down), up / down reduced by
+    their gcd: y[m] = sum_i h[m*down + center - i*up] x[i]  (window ('kaiser', 5.0), half_len = 10*max(up,down))."""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError(f"resample_poly_design: up {up} and down {down} must be positive")
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
     max_rate = max(up, down)
     half_len = 10 * max_rate
     m = np.arange(-half_len, half_len + 1, dtype=np.float64)
@@ -89,6 +97,34 @@ def decimate(x_dev, down):
     return y
 
 
+def resample(x_dev, up, down):
+    """x_dev float64 device [nch, n] -> [nch, ceil(n*up/down)] (resample_poly(x, up, down, axis=1)); up == down returns
+    the input itself, up == 1 (after the gcd) is `decimate`."""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError(f"resample: up {up} and down {down} must be positive")
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
+    if up == down:
+        return x_dev
+    if up == 1:
+        return decimate(x_dev, down)
+    return resample_kernel(x_dev, up, down)
+
+
+def resample_kernel(x_dev, up, down):
+    """eav_resample_poly_f64 for a reduced up / down (any, up == 1 included - `resample` sends that to `decimate`)."""
+    h, center = resample_poly_design(up, down)
+    nch, n = x_dev.shape
+    n_out = -(-n * up // down)
+    hd = torch.from_numpy(h).to(x_dev.device)
+    y = torch.empty(nch, n_out, dtype=torch.float64, device=x_dev.device)
+    _lib.call("eav_resample_poly_f64", x_dev.data_ptr(), hd.data_ptr(), y.data_ptr(), nch, n, n_out, up, down, len(h), center,
+              _lib.stream_ptr())
+    torch.cuda.current_stream().synchronize()
+    return y
+
+
 def sosfilt(sos, x_dev, chunk=2048):
     """scipy.signal.sosfilt(sos, x, axis=-1) for x float64 device [nch, n]."""
     sos = np.ascontiguousarray(sos, np.float64)
@@ -111,7 +147,7 @@ def sosfilt(sos, x_dev, chunk=2048):
 
 class DataLoadEEG:
     def __init__(self, subject=1, band=[0.3, 50], fs_orig=500, fs_target=100, parent_directory='./Datasets/EAV',
-                 device=None, remap_labels=False):
+                 device=None, remap_labels=False, *, window_seconds=None):
         self.subject = subject
         self.band = band
         self.fs_orig = fs_orig
@@ -119,11 +155,13 @@ class DataLoadEEG:
         self.parent_directory = parent_directory
         self.device = torch.device(device if device else ("cuda" if torch.cuda.is_available() else "cpu"))
         self.remap_labels = remap_labels
+        self.window_seconds = window_seconds
         self.seg = None
         self.label = None
         self.seg_f = None
         self.seg_f_div = None
         self.label_div = None
+        self.feature_dev = None
 
     def _dev(self, a):
         if self.device.type != "cuda":
@@ -142,17 +180,40 @@ class DataLoadEEG:
         self.seg, self.label = found
         print(f'[Info] Loaded EEG data for {tag}')
 
+    def rate_ratio(self):
+        """(up, down) = fs_target / fs_orig in lowest terms; float rates such as 128.0 are accepted."""
+        ratio = Fraction(self.fs_target).limit_denominator(1000) / Fraction(self.fs_orig).limit_denominator(1000)
+        if ratio <= 0:
+            raise ValueError(f"DataLoadEEG: fs_target {self.fs_target} / fs_orig {self.fs_orig} is not a positive rate ratio")
+        return ratio.numerator, ratio.denominator
+
+    def window_length(self, t):
+        """Samples per window for trials of t samples: the reference's 500, or round(window_seconds * fs_target)."""
+        if self.window_seconds is None:
+            return 500
+        win = int(round(self.window_seconds * self.fs_target))
+        if win < 1 or win > t:
+            raise ValueError(f"DataLoadEEG: window_seconds = {self.window_seconds} is {win} samples at {self.fs_target} Hz; "
+                             f"it must be at least one sample and at most a trial ({t} samples)")
+        return win
+
     def downsampling(self):
         # Dataload_eeg.py:85-102
         if self.seg is None:
             return
         ch, t, tri = self.seg.shape
-        factor = self.fs_target / self.fs_orig
-        down_factor = int(self.fs_orig / self.fs_target)
+        up, down = self.rate_ratio()
+        if up != 1 and t * up % down:
+            raise ValueError(f"DataLoadEEG.downsampling: trials of t = {t} samples do not resample to a whole number of "
+                             f"samples at up / down = {up} / {down} (t * up must be a multiple of down)")
         seg = self._dev(self.seg)
         tm = seg.permute(0, 2, 1).reshape(ch, tri * t).contiguous()       # == np.reshape(seg, [ch, t*tri], order='F')
-        tm2 = decimate(tm, down_factor)
-        new_time = int(t * factor)
+        if up == 1:                                                       # the reference's own arithmetic
+            tm2 = decimate(tm, int(self.fs_orig / self.fs_target))
+            new_time = int(t * (self.fs_target / self.fs_orig))
+        else:
+            tm2 = resample(tm, up, down)                                  # tri * t * up / down samples, exactly
+            new_time = t * up // down
         self.seg = tm2.reshape(ch, tri, new_time).permute(0, 2, 1).contiguous()   # order='F' reshape back
 
     def bandpass_filter(self):
@@ -172,7 +233,7 @@ class DataLoadEEG:
         if self.seg_f is None:
             return
         ch, t, tri = self.seg_f.shape
-        win = 500
+        win = self.window_length(t)
         nwin = t // win
         # tm1[c, a, b, d] = seg_f[c, a + win*b, d]; flattened F-order over (b, d): index b + nwin*d
         tm1 = self.seg_f[:, :win * nwin, :].reshape(ch, nwin, win, tri).permute(0, 2, 1, 3)     # [c, a, b, d]
@@ -182,7 +243,9 @@ class DataLoadEEG:
         mask = np.isin(cls, SELECTED_CLASSES)
         idx = torch.from_numpy(np.flatnonzero(mask)).to(seg_div.device)
         data_subset = seg_div.index_select(2, idx)
-        self.seg_f_div = data_subset.permute(2, 0, 1).contiguous().cpu().numpy()
+        selected = data_subset.permute(2, 0, 1).contiguous()
+        self.seg_f_div = selected.cpu().numpy()
+        self.feature_dev = selected.float()                 # == seg_f_div.astype(float32), resident for the trainers
         lab = np.argmax(label_div[:, mask], axis=0)
         self.label_div = (lab - 1) // 2 if self.remap_labels else lab
 

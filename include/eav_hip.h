@@ -593,6 +593,15 @@ int eav_ast_fbank(const float* wav, const double* window400, const double* twidd
  * scipy.signal.resample_poly(x, 1, down): y[c][m] = sum_j h[j] x[c][m*down + center - j], x [nch][n_in]. */
 int eav_decimate_fir_f64(const double* x, const double* h, double* y, int nch, int64_t n_in, int64_t n_out, int down,
                          int ntaps, int center, void* stream);
+/* scipy.signal.resample_poly(x, up, down, axis=1) for any reduced up / down, centred form:
+ * y[c][m] = sum_i h[m*down + center - i*up] x[c][i] over 0 <= i < n_in with the tap index in [0, ntaps);
+ * n_out = ceil(n_in * up / down).  h [ntaps] float64 is the DEVICE table of eav_amd.eeg_data.resample_poly_design
+ * (already times up; center = half_len, ntaps = 2 half_len + 1).  LDS: one budget of 64 KiB = 8192 doubles per workgroup
+ * for taps and input tile TOGETHER - the taps are staged when ntaps <= 8192, the tile ((255 down + ntaps - 1) / up + 2
+ * samples) when it fits what the taps leave; whichever does not fit is read from global memory by the same loop (no ratio
+ * is refused).  One fma chain per output in ascending i (no atomics). */
+int eav_resample_poly_f64(const double* x, const double* h, double* y, int nch, int64_t n_in, int64_t n_out, int up,
+                          int down, int ntaps, int center, void* stream);
 /* scipy.signal.sosfilt(sos, x) along the last axis of x [nch][n] (zero initial state), exact chunk-parallel form:
  * sos [nsec][6]; H [Lc][2 nsec] = cascade output at step k from unit initial state j; AL [2 nsec][2 nsec] = state
  * after Lc zero-input steps; zend / zstart: scratch [nch][ceil(n/Lc)][2 nsec]. */

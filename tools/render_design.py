@@ -173,6 +173,15 @@ if alt:
     v["F4C"] = f"{alt['shallow_transformer']['ms_per_step']:.2f}"
     v["F4CC"] = fmt(alt["shallow_transformer"].get("cpu_oracle", {}).get("samples_per_s", 0))
 
+# the rational-rate EEG resampler (tools/eeg_resample_bench.py)
+if os.path.exists(P("eeg_resample_bench.json")):
+    rp = json.load(open(P("eeg_resample_bench.json")))
+    k = rp["kernel"]
+    v["RP_MS"], v["RP_MIN"], v["RP_MAX"] = f"{k['ms']:.3f}", f"{k['ms_min']:.3f}", f"{k['ms_max']:.3f}"
+    v["RP_TBPS"], v["RP_MB"] = f"{k['gbps'] / 1e3:.2f}", f"{k['algorithmic_bytes'] / 1e6:.0f}"
+    v["RP_FRAC"] = f"{k['frac_of_copy_rate']:.2f}"
+    v["RP_SCIPY"], v["RP_X"] = f"{rp['scipy']['ms']:.0f}", f"{rp['scipy_over_kernel']:.0f}"
+
 src = open(os.path.join(ROOT, "docs", "DESIGN.md.in")).read()
 missing = sorted(set(re.findall(r"@([A-Z0-9_]+)@", src)) - set(v))
 if missing:
