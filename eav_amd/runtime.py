@@ -1,9 +1,9 @@
 """What the kernel-backed models and their trainers share on the host.
 
-    KernelModule     base class of EEGNet_tor, cnn_eeg.EEGNet, ShallowConvNet, AudioModel and VideoModel: flat parameter
-                     storage, the workspace cache, the device checks, the one-outstanding-forward guard, the dropout step
-                     counter, and what GraphStep asks of a model
-    KernelFn         the autograd bridge of all of them (and of transformer.Encoder)
+    KernelModule     base class of EEGNet_tor, cnn_eeg.EEGNet, ShallowConvNet, AudioModel, VideoModel and
+                     transformer.Encoder: flat parameter storage, the workspace cache, the device checks, the
+                     one-outstanding-forward guard, the dropout step counter, and what GraphStep asks of a model
+    KernelFn         the autograd bridge of all of them
     cached_workspace / gather_batch / DeviceLoader / GraphStep / eager_step   the device-resident training loop
 
 Imports _lib and optim only, never a model module.

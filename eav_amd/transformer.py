@@ -24,7 +24,6 @@ the MLP and the attention outputs / log-sum-exps; the fused attention never mate
 """
 from __future__ import annotations
 
-import contextlib
 import json
 import os
 from types import SimpleNamespace
@@ -35,7 +34,8 @@ import torch.nn as nn
 
 from . import _lib
 from .optim import flatten_parameters
-from .runtime import KernelFn
+from .runtime import KernelFn, KernelModule, gather_batch
+from .weight_planes import SLOT, WeightPlanes
 
 
 DEFAULT_PRECISION = "split"
@@ -180,8 +180,7 @@ class _HeadFn(torch.autograd.Function):
         ctx.model, ctx.B = model, feat.shape[0]
         hw = model._head_ws(feat.shape[0], feat.device)
         hw.feat.copy_(feat)
-        model._main = torch.cuda.current_stream()
-        model._st = model._main.cuda_stream
+        model._begin()
         model._head_forward(hw.feat, hw, feat.shape[0])
         hw.token = model._token = model._token + 1
         ctx.token = hw.token
@@ -193,20 +192,14 @@ class _HeadFn(torch.autograd.Function):
         hw = model._head_ws(ctx.B, dlogits.device)
         if hw.token != ctx.token:
             raise _lib.EavError("Encoder.head backward: activations were overwritten by a later head forward")
-        model._main = torch.cuda.current_stream()
-        model._st = model._main.cuda_stream
+        model._begin()
         model._head_backward(dlogits.contiguous(), hw.feat, hw, ctx.B, False)
-        offs, gflat = model._flat[2], model._flat[1]
-        out = []
-        for k in model._names:
-            p = model._pmap[k]
-            trained = p.requires_grad and k.startswith("classifier.")
-            out.append(gflat[offs[k][0]:offs[k][0] + offs[k][1]].view(p.shape) if trained else None)
-        return (None, None, *out)
+        return (None, None, *model._grad_views(False))
 
 
-class Encoder(nn.Module):
-    """ASTForAudioClassification / ViTForImageClassification (5-class head) on the HIP kernels."""
+class Encoder(KernelModule):
+    """ASTForAudioClassification / ViTForImageClassification (5-class head) on the HIP kernels.  The flat parameter
+    layout is the param_shapes order (q, k, v weights adjacent), not the named_parameters() order."""
 
     def __init__(self, cfg, weights=None):
         super().__init__()
@@ -223,20 +216,14 @@ class Encoder(nn.Module):
                 v = torch.randn(shp) * 0.02          # HF initializer_range
             _set_param(self, k, v)
         self._names = list(shapes)
-        self._ws = None
-        self._ws_cache = {}           # batch size -> workspace (a ragged last batch must not evict the full-batch one)
         self._hws = {}                # batch size -> head-only workspace (Encoder.head)
-        self._flat = None
-        self._token = 0
-        self._saved = None
         self.kernel_events = None
         # Dropout (cfg.hidden_dropout / cfg.attention_dropout, training mode only): every keep decision is a hash of
         # (dropout_seed, site, device-resident forward counter, element index) - no mask is stored, the backward
         # regenerates it, and a captured step draws fresh masks on every replay.  The default seed follows
-        # torch.manual_seed; set_dropout_masks (tests) replaces the generator by explicit masks.
+        # torch.manual_seed; set_dropout_masks (tests) replaces the generator by explicit masks, keyed and shaped as in
+        # dropout_sites(B).
         self.dropout_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._fwd_counter = None
-        self._dropout_masks = None
         # GEMM / attention operand precision: "split" (default: fp32-grade on the fp16 matrix cores - every operand as
         # fp16 hi + lo planes, three MFMAs per product, csrc/gemm_sp.hip + attention_sp.hip; measured against float64
         # it is not worse than the exact-fp32 kernels and it passes the same parity bounds), "fp32" (exact-fp32 MFMA),
@@ -286,10 +273,10 @@ class Encoder(nn.Module):
         # planes as well (scale from a rigorous bound, eav_layernorm_bwd_bound) and leave the bias-gradient partials of the
         # linear layer that consumes it - two conversion passes per layer disappear (EAV_FUSED_DH=0 for A/B runs)
         self.fused_dh = os.environ.get("EAV_FUSED_DH", "1") != "0"
-        self._side, self._aux, self._wgrad_done, self._wready, self._wnorm_ready = None, None, {}, {}, None
+        self._main = self._st = None  # the stream of the current launch sequence and its handle (_begin)
+        self._side, self._aux, self._wgrad_done = None, None, {}
         self._part_busy, self._ring_pos = {}, {}
-        self._wplanes = None          # split mode: {weight key: (planes, planes of the transpose, slot index)}
-        self._wplanes_key = None
+        self._wplanes = None          # split mode: the WeightPlanes of the GEMM weights
         self._phase = "fwd"
         self._scales_all = False
         # multi-GPU: called as hook(lo, hi) from inside the backward whenever flat_grad[lo:hi] is final
@@ -329,7 +316,7 @@ class Encoder(nn.Module):
         self.cfg.num_labels = head.weight.shape[0]
         self._flat = None
         self._ws = None
-        self._ws_cache, self._hws = {}, {}
+        self._wss, self._hws = {}, {}
 
     def head_parameters(self):
         return list(self.classifier.parameters())
@@ -339,17 +326,17 @@ class Encoder(nn.Module):
     def invalidate_weight_planes(self):
         """Call after writing parameters in a way torch cannot see (`p.data.mul_(...)`, raw-pointer kernels): `.data`
         writes move neither the parameter's nor the flat buffer's version counter."""
-        self._wplanes_key = None
+        if self._wplanes is not None:
+            self._wplanes.invalidate()
 
     def load_state_dict(self, *args, **kwargs):
-        self._wplanes_key = None
+        self.invalidate_weight_planes()
         return super().load_state_dict(*args, **kwargs)
 
     def _apply(self, fn, *args, **kwargs):
-        self._wplanes_key = None
         self._wplanes = None
         self._ws = None
-        self._ws_cache, self._hws = {}, {}
+        self._wss, self._hws = {}, {}
         return super()._apply(fn, *args, **kwargs)
 
     def head_grad_ranges(self):
@@ -368,14 +355,9 @@ class Encoder(nn.Module):
             self._flat = flatten_parameters(self, order=self._names)
             self._pmap = dict(self.named_parameters())
 
-    def _forward_output(self):          # what KernelFn hands to autograd
-        return self._ws.logits.clone()
-
     def forward(self, x=None, labels=None, pixel_values=None, input_values=None):
         x = x if x is not None else (pixel_values if pixel_values is not None else input_values)
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise _lib.EavError("eav_amd encoders run on an MI355X only (no CPU fallback): move model and input to "
-                                "the ROCm device")
+        self._require_gpu(x)
         c = self.cfg
         want = (c.W, c.H) if c.kind == "ast" else (c.C, c.H, c.W)
         if tuple(x.shape[1:]) != want:
@@ -390,6 +372,10 @@ class Encoder(nn.Module):
             from .optim import CrossEntropyLoss
             loss = CrossEntropyLoss()(logits, labels)
         return _Out(logits, loss)
+
+    def forward_batch(self, xs, ys, idx, optimizer):
+        data, targets = gather_batch(xs, ys, idx)
+        return self(data).logits, targets
 
     # ------------------------------------------------------------------ kernel schedule
     def _call(self, name, *args):
@@ -438,12 +424,6 @@ class Encoder(nn.Module):
     def _site_seed(self, site_id):
         return (int(self.dropout_seed) + ((site_id + 1) << 40)) & 0xFFFFFFFFFFFFFFFF
 
-    def set_dropout_masks(self, masks):
-        """Testing hook (the convention of KernelModule.set_dropout_masks): a dict of contiguous uint8 keep-masks on the
-        model's device, keyed and shaped as in dropout_sites(B), used instead of the generator by every training forward
-        (and its backward) until None restores the generator."""
-        self._dropout_masks = masks
-
     def mix_dropout_rank(self, rank):
         """Data parallelism: give replica `rank` its own dropout stream (rank_dropout_seed)."""
         self.dropout_seed = rank_dropout_seed(self.dropout_seed, rank)
@@ -486,10 +466,8 @@ class Encoder(nn.Module):
                             and tuple(m.shape) == shape and m.is_contiguous()):
                         raise _lib.EavError(f"set_dropout_masks: site {name!r} needs a contiguous uint8 mask {shape} on {dev}")
             else:
-                if self._fwd_counter is None or self._fwd_counter.device != dev:
-                    self._fwd_counter = torch.zeros((), dtype=torch.int64, device=dev)
-                self._call("eav_counter_inc", self._fwd_counter.data_ptr(), self._st)
-                d.cnt = self._fwd_counter.data_ptr()
+                d.cnt = self._counter(dev).data_ptr()
+                self._call("eav_counter_inc", d.cnt, self._st)
         d.mk = (lambda name: d.masks[name].data_ptr()) if d.masks is not None else (lambda name: None)
         ws.drop = d
         return d
@@ -564,7 +542,6 @@ class Encoder(nn.Module):
         return ws
 
     # ------------------------------------------------------------------ split-operand (fp16 hi/lo planes) plumbing
-    SLOT = 4128   # floats per scale slot (include/eav_hip.h EAV_SP_SLOT)
     FS, BS = 5, 8   # slots per layer: forward y1, qkv, ao, y2, act; backward dh(fc2), dact, dh(o), dao, dS, dqkv, dy(fc1), dy(qkv)
 
     def _alloc_split(self, ws, dev, nsave):
@@ -583,9 +560,7 @@ class Encoder(nn.Module):
         ws.aop = [h(M, D) for _ in range(nsave)]
         ws.y2p = [h(M, D) for _ in range(nsave)]
         ws.actp = [h(M, FF) for _ in range(nsave)]
-        ws.fslots = torch.zeros(1 + self.FS * Lr, self.SLOT, dtype=torch.float32, device=dev)
-        H, N = c.heads, c.ntok
-        Npad = _lib.plain("eav_attn_sp_npad", N)
+        ws.fslots, ws.fslot = self._slots(1 + self.FS * Lr, dev)
         if ws.fused:   # attention operands: row planes of qkv and per-head transposed planes (csrc/attention_sp.hip)
             ws.qkvrow = [torch.empty(M, 6 * D, dtype=torch.float16, device=dev) for _ in range(nsave)]
         if full:
@@ -599,11 +574,17 @@ class Encoder(nn.Module):
             ws.part_cs2_pool = [ws.part_cs2] + [torch.empty_like(ws.part_cs2) for _ in range(3)]
             ws.np_attn = ws.B * ((c.ntok + 31) // 32)          # bias-gradient partials of the attention backward: one row per 32-token tile
             ws.part_attn_pool = [torch.zeros(ws.np_attn, 3 * D, dtype=torch.float32, device=dev) for _ in range(4)]
-            ws.bslots = torch.zeros(2 + self.BS * Lr, self.SLOT, dtype=torch.float32, device=dev)
+            ws.bslots, ws.bslot = self._slots(2 + self.BS * Lr, dev)
             if c.hidden_dropout > 0.0:        # measured scales of the two gated gradients of every layer
-                ws.dslots = torch.zeros(2 * Lr, self.SLOT, dtype=torch.float32, device=dev)
+                ws.dslots, ws.dslot = self._slots(2 * Lr, dev)
             if ws.fused:
                 ws.dorow = torch.empty(M, 2 * D, dtype=torch.float16, device=dev)
+
+    @staticmethod
+    def _slots(n, dev):
+        """n zeroed scale slots ([n, SLOT] floats) and the device address of each."""
+        table = torch.zeros(n, SLOT, dtype=torch.float32, device=dev)
+        return table, [table.data_ptr() + 4 * SLOT * k for k in range(n)]
 
     def _weight_keys(self):
         """[(cache key, parameter name of the [out, in] matrix, out, in)] of every GEMM weight."""
@@ -621,7 +602,13 @@ class Encoder(nn.Module):
         """(Re)build the fp16 hi/lo planes of the GEMM weights (and of their transposes, for the data-gradient
         products) that changed: FusedAdam records the byte ranges it updated (`_eav_dirty`), any torch in-place write
         to the flat buffer (load_state_dict, .copy_) bumps its version and invalidates everything."""
-        flat = self._flat[0]
+        flat, offs = self._flat[0], self._flat[2]
+        keys = self._weight_keys()
+        wp = self._wplanes
+        if wp is None or wp.dev != dev or (need_T and not wp.T):
+            wp = self._wplanes = WeightPlanes([(k, 4 * offs[pn][0], out, inn) for k, pn, out, inn in keys],
+                                              self.cfg.layers, dev, need_T)
+            wp.main = self._main
         # Invalidation key: flatten_parameters rebinds p.data to views of the flat buffer, and a rebound .data has its
         # OWN version counter - load_state_dict, p.copy_/add_ under no_grad and torch.optim optimisers bump the
         # parameters' versions, never the flat buffer's.  So the key is the sum of the GEMM weights' versions (host-side,
@@ -630,123 +617,12 @@ class Encoder(nn.Module):
         # moves): it reports the byte ranges it updated instead (`_eav_dirty`, recorded only because this model asked
         # for it through `_eav_track_dirty`).
         flat._eav_track_dirty = True
-        key = (flat.data_ptr(), flat._version, sum(self._pmap[pn]._version for _, pn, _, _ in self._weight_keys()))
-        dirty = getattr(flat, "_eav_dirty", [])
-        flat._eav_dirty = []
-        have_T = self._wplanes is not None and self._wplanes["_T"]
-        keys = self._weight_keys()
-        kp = lambda k: _lib.plain("eav_sp_kpad", k)  # noqa: E731
-        everything = self._wplanes is None or self._wplanes["_dev"] != dev or (need_T and not have_T) \
-            or self._wplanes_key != key
-        if everything and (self._wplanes is None or self._wplanes["_dev"] != dev or (need_T and not have_T)):
-            wp = {"_T": need_T, "_dev": dev,
-                  "_slots": torch.zeros(len(keys), self.SLOT, dtype=torch.float32, device=dev),
-                  # max_n ||W1_n||_2 per layer: input of the a-priori scale of the MLP activation (eav_tf_forward_scales)
-                  "_wnorm_fc1": torch.zeros(self.cfg.layers, dtype=torch.float32, device=dev),
-                  # max_n ||Wqkv_n||_2 per layer: bound of the fused q/k/v projection's output
-                  "_wnorm_qkv": torch.zeros(self.cfg.layers, dtype=torch.float32, device=dev),
-                  # max_j ||W2[:, j]||_2 per layer: bound of the MLP hidden-state gradient (eav_sp_bound_scale)
-                  "_wcolnorm_fc2": torch.zeros(self.cfg.layers, dtype=torch.float32, device=dev)}
-            for n, (k, _, out, inn) in enumerate(keys):
-                wp[k] = (torch.empty(out, 2 * kp(inn), dtype=torch.float16, device=dev),
-                         torch.empty(inn, 2 * kp(out), dtype=torch.float16, device=dev) if need_T else None, n)
-            self._wplanes = wp
-        wp = self._wplanes
-        stale = []
-        for k, pname, out, inn in keys:
-            src = _lib.ptr(self._pmap[pname])
-            if everything or any(lo < src + 4 * out * inn and src < hi for lo, hi in dirty):
-                stale.append((k, src, out, inn))
-        # After an optimiser step every matrix is stale: ~100 small launches (max|w| + conversion per matrix).  They go to
-        # the side stream - idle during the forward - in layer order, one event per matrix; the main stream waits for a
-        # matrix's event right before the first GEMM that reads its planes (_wp), so only the patch projection's
-        # conversion is ever on the critical path.
+        versions = (flat._version, sum(self._pmap[pn]._version for _, pn, _, _ in keys))
+        dirty, flat._eav_dirty = getattr(flat, "_eav_dirty", []), []
+        stale = wp.stale(flat.data_ptr(), versions, dirty, need_T)
+        # (the refresh goes to the side stream - idle during the forward - when this step runs on two streams)
         side = self._side_stream(dev) if (stale and self._two_streams() and self.kernel_events is None) else None
-        self._wready = {}
-        self._wnorm_ready = None
-        if side is not None:
-            start = torch.cuda.Event()
-            start.record()                      # the weights are final (the optimiser ran on this stream)
-            side.wait_event(start)
-        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            st = _lib.stream_ptr()
-            if len(stale) == len(keys):
-                wp["_slots"].zero_()
-                wp["_wnorm_fc1"].zero_()
-                wp["_wcolnorm_fc2"].zero_()
-                wp["_wnorm_qkv"].zero_()
-                # everything is stale (the state after an optimiser step): the whole table in two launches
-                jobs = wp.get("_jobs")
-                if jobs is None or wp["_jobs_key"] != key[0]:
-                    rows = []
-                    for k, src, out, inn in stale:
-                        pl, plT, n = wp[k]
-                        rows.append([src, _lib.ptr(pl), _lib.ptr(plT) or 0,
-                                     wp["_slots"].data_ptr() + 4 * self.SLOT * n, out | (inn << 32)])     # EavPlaneJob
-                    jobs = wp["_jobs"] = torch.tensor(rows, dtype=torch.int64).to(dev)
-                    wp["_jobs_key"] = key[0]
-                # the row / column norms behind the a-priori scales FIRST (their own event: the forward's scales wait for
-                # nothing else) and in one launch for the whole table (36 launches of ~10 us stood between the optimiser step
-                # and the first scales of the next forward)
-                njobs = wp.get("_njobs")
-                if njobs is None or wp["_njobs_key"] != (key[0], wp["_T"]):
-                    rows, mb = [], 1
-                    for k, src, out, inn in stale:
-                        if k.startswith("fc1"):
-                            rows.append([src, inn, wp["_wnorm_fc1"].data_ptr() + 4 * int(k[3:]), out | (inn << 32), 0])
-                            mb = max(mb, min((out + 3) // 4, 128))
-                        elif k.startswith("fc2") and wp["_T"]:
-                            # (keyed on the planes HAVING transposes, not on this call's need_T: a no_grad forward right after
-                            # an optimiser step refreshes everything with need_T = False, and the next training step finds
-                            # nothing stale - its backward must still see the norms of the CURRENT weights)
-                            rows.append([src, inn, wp["_wcolnorm_fc2"].data_ptr() + 4 * int(k[3:]), out | (inn << 32), 1])
-                            mb = max(mb, (inn + 63) // 64)
-                        elif k.startswith("qkv"):
-                            rows.append([src, inn, wp["_wnorm_qkv"].data_ptr() + 4 * int(k[3:]), out | (inn << 32), 0])
-                            mb = max(mb, min((out + 3) // 4, 128))
-                    njobs = wp["_njobs"] = (torch.tensor(rows, dtype=torch.int64).to(dev), len(rows), mb)
-                    wp["_njobs_key"] = (key[0], wp["_T"])
-                if njobs[1]:
-                    _lib.call("eav_norm_max_multi", _lib.ptr(njobs[0]), njobs[1], njobs[2], st)
-                if side is not None:
-                    self._wnorm_ready = torch.cuda.Event()
-                    self._wnorm_ready.record(side)
-                _lib.call("eav_sp_refresh_planes", _lib.ptr(jobs), len(stale), max(o for _, _, o, _ in stale),
-                          max(i for _, _, _, i in stale), st)
-                if side is not None:
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                    self._wready = {k: ev for k, _, _, _ in stale}
-                stale = []
-            # some matrices are stale (a partial update): the row / column norms first - the a-priori scales of EVERY layer
-            # are computed by one launch before layer 0 and wait for ONE event (`_wnorm_ready`), not for the conversions -
-            # then max|w| + conversion per matrix with one event each (the main stream waits for a matrix's planes right
-            # before the first GEMM that reads them: _wp)
-            for k, src, out, inn in stale:
-                li = int(k[3:]) if k[:3] in ("fc1", "fc2", "qkv") else -1
-                if k.startswith("fc1"):
-                    wp["_wnorm_fc1"][li].zero_()
-                    _lib.call("eav_rownorm_max", src, out, inn, inn, wp["_wnorm_fc1"].data_ptr() + 4 * li, st)
-                elif k.startswith("fc2") and wp["_T"]:
-                    wp["_wcolnorm_fc2"][li].zero_()
-                    _lib.call("eav_colnorm_max", src, out, inn, inn, wp["_wcolnorm_fc2"].data_ptr() + 4 * li, st)
-                elif k.startswith("qkv"):
-                    wp["_wnorm_qkv"][li].zero_()
-                    _lib.call("eav_rownorm_max", src, out, inn, inn, wp["_wnorm_qkv"].data_ptr() + 4 * li, st)
-            if stale and side is not None:
-                self._wnorm_ready = torch.cuda.Event()
-                self._wnorm_ready.record(side)
-            for k, src, out, inn in stale:
-                pl, plT, n = wp[k]
-                wp["_slots"][n].zero_()
-                slot = wp["_slots"].data_ptr() + 4 * self.SLOT * n
-                _lib.call("eav_sp_absmax", src, out, inn, inn, slot, st)
-                _lib.call("eav_sp_convert", src, out, inn, inn, slot, _lib.ptr(pl), _lib.ptr(plT), st)
-                if side is not None:
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                    self._wready[k] = ev
-        self._wplanes_key = key
+        wp.refresh(stale, flat.data_ptr(), versions, side)
 
     def _terms(self, kind):
         """MFMA terms of the backward products of `kind` ("dgrad" | "wgrad"): 3 = fp32-grade, 1 = hi.hi only; wgrad also 2 =
@@ -764,22 +640,17 @@ class Encoder(nn.Module):
         """Whether this step runs its weight gradients / final reductions beside the main stream (overlap_wgrad)."""
         o = self.overlap_wgrad
         if o == "auto":
-            ws = getattr(self, "_ws", None)
-            return ws is not None and ws.B * self.cfg.ntok >= 8192
+            return self._ws is not None and self._ws.B * self.cfg.ntok >= 8192
         return bool(o)
 
-    def _cur_stream(self):
-        """The stream the current launch sequence runs on (cached by _launch_forward / _launch_backward / the head functions:
-        torch.cuda.current_stream() costs tens of microseconds per call, and the step waits on ~50 events)."""
-        m = getattr(self, "_main", None)
-        return m if m is not None else torch.cuda.current_stream()
-
-    def _wp(self, key, transposed=False):
-        ev = self._wready.pop(key, None)
-        if ev is not None:
-            self._cur_stream().wait_event(ev)
-        pl, plT, n = self._wplanes[key]
-        return _lib.ptr(plT if transposed else pl), self._wplanes["_slots"].data_ptr() + 4 * self.SLOT * n
+    def _begin(self):
+        """Head of every launch sequence (forward, backward, the head functions): look the current stream up once -
+        torch.cuda.current_stream() costs tens of microseconds per call, and the step waits on ~50 events."""
+        self._main = torch.cuda.current_stream()
+        self._st = self._main.cuda_stream
+        if self._wplanes is not None:
+            self._wplanes.main = self._main
+        return self._st
 
     def _to_planes(self, src, R, C, ld, slot, dst, amax_done=False):
         """fp32 [R, C] -> row planes (one set serves the products that contract over columns AND those over rows)."""
@@ -797,7 +668,7 @@ class Encoder(nn.Module):
         self._ring_pos[pool] = i = i % len(ring)
         ev = self._part_busy.pop(ring[i].data_ptr(), None)
         if ev is not None:
-            self._cur_stream().wait_event(ev)
+            self._main.wait_event(ev)
         return ring[i]
 
     def _reduce_async(self, buf, off_bytes, nparts, stride, n, out):
@@ -873,14 +744,14 @@ class Encoder(nn.Module):
         finished before the next conversion overwrites it."""
         ev = self._wgrad_done.pop(buf.data_ptr(), None) if buf is not None else None
         if ev is not None:
-            self._cur_stream().wait_event(ev)
+            self._main.wait_event(ev)
 
     def _join_wgrads(self):
         if self._side is not None and self._wgrad_done:
-            self._cur_stream().wait_stream(self._side)
+            self._main.wait_stream(self._side)
             self._wgrad_done.clear()
         if self._aux is not None and self._part_busy:
-            self._cur_stream().wait_stream(self._aux)
+            self._main.wait_stream(self._aux)
             self._part_busy.clear()
 
     # ------------------------------------------------------------------ classification head (shared by the full path
@@ -914,9 +785,8 @@ class Encoder(nn.Module):
             sh = P(hw.sth)
             L("eav_layernorm_bwd", P(hw.dhl), P(feat), w("classifier.layernorm.weight"), sh, sh + 4 * B,
               P(hw.dpooled), 0, P(hw.part_lnr), B, D, st)
-            npb = _lib.plain("eav_layernorm_bwd_nparts", B)
-            self._reduce(hw.part_lnr, npb, 2 * D, D, gp("classifier.layernorm.weight"))
-            L("eav_reduce_partials", P(hw.part_lnr) + 4 * D, npb, 2 * D, D, 1.0, gp("classifier.layernorm.bias"), st)
+            self._reduce_gamma_beta(hw.part_lnr, _lib.plain("eav_layernorm_bwd_nparts", B),
+                                    gp("classifier.layernorm.weight"), gp("classifier.layernorm.bias"))
         else:
             L("eav_dense_softmax_bwd", P(dlogits), None, P(feat), w("classifier.weight"), gp("classifier.weight"),
               gp("classifier.bias"), P(hw.dseqr), B, D, c.num_labels, st)
@@ -947,48 +817,48 @@ class Encoder(nn.Module):
         self._ensure_flat()
         return _Out(_HeadFn.apply(feat.contiguous().float(), self, *[self._pmap[k] for k in self._names]))
 
+    def _workspace_for(self, B, dev, full):
+        """The workspace of a batch of B.  Three replaceable ones are kept (the full batch, a ragged last batch, an
+        evaluation batch): the 5000 % 128 = 8 frames at the end of every vision epoch must not free and re-zero the 19 GB
+        of the B = 128 one.  One allocated for a full backward also serves the no_grad forwards of its batch size; one
+        without the backward's buffers is replaced when a full backward comes."""
+        key = (B, str(dev), self._fused_attention(), self.precision == "split")
+        old = self._wss.get(key)
+        if old is not None and full and not old.full:
+            del self._wss[key]
+            if getattr(old, "pinned", False):       # a captured graph still writes to it
+                self._wss[key + ("head only",)] = old
+
+        def make():
+            if not torch.cuda.is_current_stream_capturing():
+                torch.cuda.empty_cache()            # hand an evicted workspace's blocks back before taking new ones
+            return self._alloc(B, dev, full)
+        return self._workspace(key, make, keep_unpinned=3)
+
     def _launch_forward(self, x):
         c = self.cfg
         P, L = _lib.ptr, self._call
-        self._main = torch.cuda.current_stream()      # (looked up once per launch sequence: ~50 event waits per step use it)
-        self._st = st = self._main.cuda_stream
+        st = self._begin()
         self._phase = "fwd"
         B = x.shape[0]
-        D, FF, N, H = c.hidden, c.ff, c.ntok, c.heads
-        hd = D // H
-        pm = self._pmap
+        D, N = c.hidden, c.ntok
         full = self._want_full
-        ws = self._ws
-        sp = self.precision == "split"
-        ok = lambda v: (v is not None and v.B == B and v.hs[0].device == x.device and (v.full or not full)  # noqa: E731
-                        and v.fused == self._fused_attention() and v.sp == sp)
-        if not ok(ws):
-            # one workspace per batch size (at most three: the full batch, a ragged last batch, an evaluation batch) - the
-            # 5000 % 128 = 8 frames at the end of every vision epoch must not free and re-zero the 19 GB of the B = 128 one
-            ws = self._ws_cache.get(B)
-            if not ok(ws):
-                if len(self._ws_cache) >= 3:
-                    self._ws_cache.pop(next(k for k in self._ws_cache if k != B))
-                    torch.cuda.empty_cache()
-                ws = self._ws_cache[B] = self._alloc(B, x.device, full)
-            self._ws = ws
+        ws = self._workspace_for(B, x.device, full)
+        sp = ws.sp
         drop = self._begin_dropout(ws, B, x.device)
         if sp:
             self._refresh_weight_planes(x.device, full)
             ws.fslots.zero_()
-            fslot = lambda n: ws.fslots.data_ptr() + 4 * self.SLOT * n  # noqa: E731
-            kpb = lambda k: 4 * _lib.plain("eav_sp_kpad", k)            # noqa: E731  plane row stride in bytes
-        M, ldn = ws.M, ws.ldn
         pre = c.prefix
-        w = lambda k: P(pm[k])  # noqa: E731
+        w = lambda k: P(self._pmap[k])  # noqa: E731
         # patch embedding: im2col rows x projection weight -> token rows [nextra:], then cls/dist + positions
         L("eav_im2col", P(x), P(ws.col), B, c.C, c.H, c.W, c.patch, c.sy, c.sx, c.transposed, st)
         h0 = ws.hs[0]
         if sp:
-            self._to_planes(P(ws.col), B * c.npatch, c.kp, c.kp, fslot(0), ws.colp)
-            wpl, wsl = self._wp("patch")
-            self._gemm_sp(P(ws.colp), fslot(0), wpl, wsl, P(h0) + 4 * c.nextra * D, c.npatch, D, c.kp, D, batch=B,
-                          sA=c.npatch * kpb(c.kp), sC=N * D,
+            self._to_planes(P(ws.col), B * c.npatch, c.kp, c.kp, ws.fslot[0], ws.colp)
+            wpl, wsl = self._wplanes.get("patch")
+            self._gemm_sp(P(ws.colp), ws.fslot[0], wpl, wsl, P(h0) + 4 * c.nextra * D, c.npatch, D, c.kp, D, batch=B,
+                          sA=c.npatch * 4 * _lib.plain("eav_sp_kpad", c.kp), sC=N * D,      # (plane row stride in bytes)
                           bias=w(f"{pre}.embeddings.patch_embeddings.projection.bias"))
         else:
             self._gemm(P(ws.col), w(f"{pre}.embeddings.patch_embeddings.projection.weight"),
@@ -999,51 +869,16 @@ class Encoder(nn.Module):
           w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None,
           w(f"{pre}.embeddings.position_embeddings"), B, N, D, c.nextra, st)
         if drop.ph > 0.0:
-            self._drop_add(P(h0), None, P(h0), M * D, drop.ph, 0, "emb")
-        scale = hd ** -0.5
+            self._drop_add(P(h0), None, P(h0), ws.M * D, drop.ph, 0, "emb")
+        scale = (D // c.heads) ** -0.5
+        if sp and c.layers:
+            self._forward_scales()
+        layer = self._layer_forward_split if sp else self._layer_forward_f32
         for i in range(c.layers):
             j = i if ws.full else 0
             hin = ws.hs[i] if ws.full else ws.hs[i & 1]
             hout = ws.hs[i + 1] if ws.full else ws.hs[(i + 1) & 1]
-            Lk = f"{pre}.layers.{i}"
-            stp = P(ws.st[j])
-            if sp:
-                if i == 0:
-                    self._forward_scales(fslot)
-                self._layer_forward_split(i, j, hin, hout, Lk, stp, fslot, scale)
-                continue
-            L("eav_layernorm_fwd", P(hin), w(f"{Lk}.layernorm_before.weight"), w(f"{Lk}.layernorm_before.bias"),
-              P(ws.y1[j]), stp, stp + 4 * M, M, D, c.eps, st)
-            qkv = P(ws.qkv[j])
-            self._gemm(P(ws.y1[j]), w(f"{Lk}.attention.q_proj.weight"), qkv, M, 3 * D, D, D, D, 3 * D,
-                       bias=w(f"{Lk}.attention.q_proj.bias"))
-            if ws.fused and drop.pa > 0.0:
-                L("eav_attn_fwd_dropout", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, drop.pa,
-                  self._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
-            elif ws.fused:
-                L("eav_attn_fwd", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, st)
-            else:
-                Pm = P(ws.P[j])
-                self._gemm(qkv, qkv + 4 * D, Pm, N, N, hd, 3 * D, 3 * D, ldn, batch=B * H, heads=H,
-                           sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(H * N * ldn, N * ldn), alpha=scale)
-                Pv = self._softmax_forward(i, Pm, B * H * N, N, ldn)
-                self._gemm(Pv, qkv + 8 * D, P(ws.ao[j]), N, hd, N, ldn, 3 * D, D, tB=1, batch=B * H, heads=H,
-                           sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
-            # (hidden dropout sits between the bias and the residual add: the product leaves without the residual and one
-            # element-wise pass forms resid + Dropout(product))
-            hd_on = drop.ph > 0.0
-            self._gemm(P(ws.ao[j]), w(f"{Lk}.attention.o_proj.weight"), P(ws.hmid[j]), M, D, D, D, D, D,
-                       bias=w(f"{Lk}.attention.o_proj.bias"), resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
-            if hd_on:
-                self._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
-            L("eav_layernorm_fwd", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"), w(f"{Lk}.layernorm_after.bias"),
-              P(ws.y2[j]), stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
-            self._gemm(P(ws.y2[j]), w(f"{Lk}.mlp.fc1.weight"), P(ws.act[j]), M, FF, D, D, D, FF,
-                       bias=w(f"{Lk}.mlp.fc1.bias"), gelu=1, pre=P(ws.pre[j]))
-            self._gemm(P(ws.act[j]), w(f"{Lk}.mlp.fc2.weight"), P(hout), M, D, FF, FF, FF, D,
-                       bias=w(f"{Lk}.mlp.fc2.bias"), resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
-            if hd_on:
-                self._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+            layer(i, j, hin, hout, f"{pre}.layers.{i}", P(ws.st[j]), scale)
         hlast = ws.hs[c.layers] if ws.full else ws.hs[c.layers & 1]
         R = B * c.nextra
         L("eav_token_rows", P(hlast), P(ws.rows), B, N, D, c.nextra, 0, st)
@@ -1054,8 +889,49 @@ class Encoder(nn.Module):
             L("eav_pair_mean", P(ws.seqr), P(ws.pooled), B, D, 0, st)
         self._head_forward(ws.pooled if c.kind == "ast" else ws.seqr, ws, B)
         self._token += 1
-        self._saved = (self._token, x, full, None)
+        self._saved = (self._token, x, full)
         return self._token
+
+    def _layer_forward_f32(self, i, j, hin, hout, Lk, stp, scale):
+        """One encoder layer on the exact-fp32 GEMM and attention kernels (precision "fp32"; _gemm_name: also bf16)."""
+        c, ws = self.cfg, self._ws
+        P, L, st = _lib.ptr, self._call, self._st
+        D, FF, N, H, M, B, ldn = c.hidden, c.ff, c.ntok, c.heads, ws.M, ws.B, ws.ldn
+        hd = D // H
+        drop = ws.drop
+        w = lambda k: P(self._pmap[k])  # noqa: E731
+        L("eav_layernorm_fwd", P(hin), w(f"{Lk}.layernorm_before.weight"), w(f"{Lk}.layernorm_before.bias"),
+          P(ws.y1[j]), stp, stp + 4 * M, M, D, c.eps, st)
+        qkv = P(ws.qkv[j])
+        self._gemm(P(ws.y1[j]), w(f"{Lk}.attention.q_proj.weight"), qkv, M, 3 * D, D, D, D, 3 * D,
+                   bias=w(f"{Lk}.attention.q_proj.bias"))
+        if ws.fused and drop.pa > 0.0:
+            L("eav_attn_fwd_dropout", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, drop.pa,
+              self._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
+        elif ws.fused:
+            L("eav_attn_fwd", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, st)
+        else:
+            Pm = P(ws.P[j])
+            self._gemm(qkv, qkv + 4 * D, Pm, N, N, hd, 3 * D, 3 * D, ldn, batch=B * H, heads=H,
+                       sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(H * N * ldn, N * ldn), alpha=scale)
+            Pv = self._softmax_forward(i, Pm, B * H * N, N, ldn)
+            self._gemm(Pv, qkv + 8 * D, P(ws.ao[j]), N, hd, N, ldn, 3 * D, D, tB=1, batch=B * H, heads=H,
+                       sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
+        # (hidden dropout sits between the bias and the residual add: the product leaves without the residual and one
+        # element-wise pass forms resid + Dropout(product))
+        hd_on = drop.ph > 0.0
+        self._gemm(P(ws.ao[j]), w(f"{Lk}.attention.o_proj.weight"), P(ws.hmid[j]), M, D, D, D, D, D,
+                   bias=w(f"{Lk}.attention.o_proj.bias"), resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
+        if hd_on:
+            self._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+        L("eav_layernorm_fwd", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"), w(f"{Lk}.layernorm_after.bias"),
+          P(ws.y2[j]), stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
+        self._gemm(P(ws.y2[j]), w(f"{Lk}.mlp.fc1.weight"), P(ws.act[j]), M, FF, D, D, D, FF,
+                   bias=w(f"{Lk}.mlp.fc1.bias"), gelu=1, pre=P(ws.pre[j]))
+        self._gemm(P(ws.act[j]), w(f"{Lk}.mlp.fc2.weight"), P(hout), M, D, FF, FF, FF, D,
+                   bias=w(f"{Lk}.mlp.fc2.bias"), resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
+        if hd_on:
+            self._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
 
     def _softmax_forward(self, i, Pm, rows, N, ldn):
         """Materialised-score path: softmax in place over the scores of layer i; returns the operand of the P.V product -
@@ -1092,33 +968,36 @@ class Encoder(nn.Module):
         g(dP, qkv, dqkv + 4 * D, N, hd, N, ldn, 3 * D, 3 * D, tA=1, tB=1, batch=B * H, heads=H, sA=sP, sB=sQ, sC=sQ,
           alpha=scale)
 
-    def _forward_scales(self, fslot):
+    _SCALE_PARAMS = ("layernorm_before.weight", "layernorm_before.bias", "layernorm_after.weight", "layernorm_after.bias",
+                     "mlp.fc1.bias", "attention.q_proj.bias")
+
+    def _scale_offsets(self, i):
+        """(offset of layer i's first parameter in the flat buffer, the offsets relative to it of the parameters
+        eav_tf_forward_scales_qkv reads, in its argument order)."""
+        offs, Lk = self._flat[2], f"{self.cfg.prefix}.layers.{i}"
+        first = offs[f"{Lk}.attention.q_proj.weight"][0]
+        return first, tuple(offs[f"{Lk}.{n}"][0] - first for n in self._SCALE_PARAMS)
+
+    def _forward_scales(self):
         """A-priori operand scales (rigorous bounds: eav_tf_forward_scales_qkv) of y1, qkv, y2, act of EVERY layer in one
         launch - the flat parameter buffer lays the layers out identically.  Falls back to one launch per layer (inside
         _layer_forward_split) if it does not."""
-        c, ws = self.cfg, self._ws
+        c, ws, wp = self.cfg, self._ws, self._wplanes
         self._scales_all = False
         if not (self.fused_planes and c.hidden % 8 == 0 and c.ff % 8 == 0):
             return
-        offs, pre = self._flat[2], c.prefix
-        first = lambda i: offs[f"{pre}.layers.{i}.attention.q_proj.weight"][0]  # noqa: E731
-        names = ("layernorm_before.weight", "layernorm_before.bias", "layernorm_after.weight", "layernorm_after.bias",
-                 "mlp.fc1.bias", "attention.q_proj.bias")
-        rel = [tuple(offs[f"{pre}.layers.{i}.{n}"][0] - first(i) for n in names) for i in range(c.layers)]
-        stride = first(1) - first(0) if c.layers > 1 else 0
-        if any(r != rel[0] for r in rel) or any(first(i) - first(0) != i * stride for i in range(c.layers)):
+        first, rel = zip(*(self._scale_offsets(i) for i in range(c.layers)))
+        stride = first[1] - first[0] if c.layers > 1 else 0
+        if any(r != rel[0] for r in rel) or any(first[i] - first[0] != i * stride for i in range(c.layers)):
             return
-        if self._wnorm_ready is not None:              # the row norms come from the side-stream weight refresh
-            self._cur_stream().wait_event(self._wnorm_ready)
-        o = rel[0]
-        qkvp = self.fused_qkv and ws.fused
-        self._call("eav_tf_forward_scales_qkv", _lib.ptr(self._flat[0]) + 4 * first(0), stride, c.layers, o[0], o[1], o[2],
-                   o[3], o[4], o[5], c.hidden, c.ff, self._wplanes["_wnorm_fc1"].data_ptr(),
-                   self._wplanes["_wnorm_qkv"].data_ptr(), fslot(1), self.FS * self.SLOT, 0, 3, 4, 1 if qkvp else -1,
-                   self._st)
+        if wp.norm_ready is not None:              # the row norms come from the side-stream weight refresh
+            self._main.wait_event(wp.norm_ready)
+        self._call("eav_tf_forward_scales_qkv", _lib.ptr(self._flat[0]) + 4 * first[0], stride, c.layers, *rel[0],
+                   c.hidden, c.ff, wp.wnorm_fc1.data_ptr(), wp.wnorm_qkv.data_ptr(), ws.fslot[1], self.FS * SLOT, 0, 3, 4,
+                   1 if (self.fused_qkv and ws.fused) else -1, self._st)
         self._scales_all = True
 
-    def _layer_forward_split(self, i, j, hin, hout, Lk, stp, fslot, scale):
+    def _layer_forward_split(self, i, j, hin, hout, Lk, stp, scale):
         """One encoder layer with every projection on the split-operand GEMM; the attention core stays on the fp32
         kernels.  LayerNorm / attention / GELU outputs are converted to planes once (plus the transposed planes when
         a backward will follow); only the planes are kept per layer."""
@@ -1127,23 +1006,19 @@ class Encoder(nn.Module):
         D, FF, N, H, M = c.hidden, c.ff, c.ntok, c.heads, ws.M
         hd = D // H
         w = lambda k: P(self._pmap[k])  # noqa: E731
-        s_y1, s_qkv, s_ao, s_y2, s_act = (fslot(1 + self.FS * i + k) for k in range(5))
+        s_y1, s_qkv, s_ao, s_y2, s_act = ws.fslot[1 + self.FS * i:1 + self.FS * (i + 1)]
         y, ao, act = ws.y1[0], ws.ao[j], ws.act[0]
         # Producers write the operand planes themselves where a rigorous bound of the tensor exists BEFORE it is computed
         # (LayerNorm outputs, the MLP's GELU output: eav_tf_forward_scales) - no fp32 copy, no measured maximum, no
         # conversion pass for y1, y2, act.  The attention output keeps the measured scale (its kernel emits max|O|).
         fusedp = self.fused_planes and D % 8 == 0 and FF % 8 == 0
         if fusedp:
-            self._wp(f"fc1{i}")        # (waits for the side-stream refresh of this layer's fc1 planes / row norms)
-            offs = self._flat[2]
-            base = offs[f"{Lk}.attention.q_proj.weight"][0]
-            o = lambda k: offs[f"{Lk}.{k}"][0] - base  # noqa: E731
-            qkvp = self.fused_qkv and ws.fused
+            self._wplanes.get(f"fc1{i}")        # (waits for the side-stream refresh of this layer's fc1 planes / row norms)
             if not self._scales_all:
-                L("eav_tf_forward_scales_qkv", P(self._flat[0]) + 4 * base, 0, 1, o("layernorm_before.weight"),
-                  o("layernorm_before.bias"), o("layernorm_after.weight"), o("layernorm_after.bias"), o("mlp.fc1.bias"),
-                  o("attention.q_proj.bias"), D, FF, self._wplanes["_wnorm_fc1"].data_ptr() + 4 * i,
-                  self._wplanes["_wnorm_qkv"].data_ptr() + 4 * i, s_y1, 0, 0, 3, 4, 1 if qkvp else -1, st)
+                first, rel = self._scale_offsets(i)
+                L("eav_tf_forward_scales_qkv", P(self._flat[0]) + 4 * first, 0, 1, *rel, D, FF,
+                  self._wplanes.wnorm_fc1.data_ptr() + 4 * i, self._wplanes.wnorm_qkv.data_ptr() + 4 * i, s_y1, 0, 0, 3, 4,
+                  1 if (self.fused_qkv and ws.fused) else -1, st)
             L("eav_layernorm_fwd_planes", P(hin), w(f"{Lk}.layernorm_before.weight"), w(f"{Lk}.layernorm_before.bias"),
               None, P(ws.y1p[j]), s_y1, stp, stp + 4 * M, M, D, c.eps, st)
         else:
@@ -1151,7 +1026,7 @@ class Encoder(nn.Module):
               P(y), stp, stp + 4 * M, M, D, c.eps, s_y1, st)
             self._to_planes(P(y), M, D, D, s_y1, ws.y1p[j], amax_done=True)
         qkv = P(ws.qkv[0 if ws.fused else j])
-        wpl, wsl = self._wp(f"qkv{i}")
+        wpl, wsl = self._wplanes.get(f"qkv{i}")
         qkvp = fusedp and self.fused_qkv and ws.fused
         if qkvp:
             # the projection writes the row planes of Q | K | V itself (lo without the 2^11 lift: the attention kernels' format,
@@ -1198,7 +1073,7 @@ class Encoder(nn.Module):
                            sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
         if not (ws.fused and fusedp and self.fused_ao) or (ws.fused and ws.drop.pa > 0.0):
             self._to_planes(P(ao), M, D, D, s_ao, ws.aop[j], amax_done=ws.fused)
-        wpl, wsl = self._wp(f"o{i}")
+        wpl, wsl = self._wplanes.get(f"o{i}")
         # (hidden dropout: the product leaves without the residual, one element-wise pass forms resid + Dropout(product) - the
         # split GEMM's epilogue stays as it is)
         drop = ws.drop
@@ -1207,11 +1082,10 @@ class Encoder(nn.Module):
                       resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
         if hd_on:
             self._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
-        wpl, wsl = None, None
         if fusedp:
             L("eav_layernorm_fwd_planes", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"),
               w(f"{Lk}.layernorm_after.bias"), None, P(ws.y2p[j]), s_y2, stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
-            wpl, wsl = self._wp(f"fc1{i}")
+            wpl, wsl = self._wplanes.get(f"fc1{i}")
             # fc1: bias + erf-GELU in the epilogue; the pre-activation is kept (fp32) for the backward only, the
             # activation leaves as planes - it never exists in fp32
             self._call("eav_gemm_sp_ex", P(ws.y2p[j]), wpl, None, s_y2, wsl, M, FF, D, FF, 1, 0, 0, 1.0,
@@ -1221,14 +1095,14 @@ class Encoder(nn.Module):
             L("eav_layernorm_fwd_amax", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"),
               w(f"{Lk}.layernorm_after.bias"), P(y), stp + 8 * M, stp + 12 * M, M, D, c.eps, s_y2, st)
             self._to_planes(P(y), M, D, D, s_y2, ws.y2p[j], amax_done=True)
-            wpl, wsl = self._wp(f"fc1{i}")
+            wpl, wsl = self._wplanes.get(f"fc1{i}")
             # fc1 stores the PRE-activation only (kept per layer for the backward; a scratch buffer in the frozen phase)
             # and max|GELU|; the conversion applies the GELU while it splits - the activation never exists in fp32
             pre = P(ws.pre[j]) if ws.full else P(act)
             self._gemm_sp(P(ws.y2p[j]), s_y2, wpl, wsl, pre, M, FF, D, FF, bias=w(f"{Lk}.mlp.fc1.bias"), gelu=3,
                           amax=s_act)
             self._call("eav_sp_convert_gelu", pre, M, FF, FF, s_act, P(ws.actp[j]), None, self._st)
-        wpl, wsl = self._wp(f"fc2{i}")
+        wpl, wsl = self._wplanes.get(f"fc2{i}")
         self._gemm_sp(P(ws.actp[j]), s_act, wpl, wsl, P(hout), M, D, FF, D, bias=w(f"{Lk}.mlp.fc2.bias"),
                       resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
         if hd_on:
@@ -1239,7 +1113,7 @@ class Encoder(nn.Module):
         self._call("eav_gemm_f32", A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch, heads, sA[0], sA[1], sB[0], sB[1],
                    sC[0], sC[1], float(alpha), None, 0, None, None, 0, 0, self._st)
 
-    def _layer_backward_split(self, i, Lk, stp, gp, bslot, fslot, scale):
+    def _layer_backward_split(self, i, Lk, stp, gp, scale):
         """Backward of one layer: dh (gradient w.r.t. the layer output, fp32) in ws.dh on entry, gradient w.r.t. the
         layer input on exit.  Every weight gradient is a split-K GEMM over the transposed planes; data gradients use
         the planes of the transposed weights."""
@@ -1249,8 +1123,9 @@ class Encoder(nn.Module):
         hd = D // H
         w = lambda k: P(self._pmap[k])  # noqa: E731
         dh, dy, dao, dact, dqkv = P(ws.dh), P(ws.dy), P(ws.dao), P(ws.dact), P(ws.dqkv)
-        s_y1, s_qkv, s_ao, s_y2, s_act = (fslot(1 + self.FS * i + k) for k in range(5))
-        b_dh2, b_dact, b_dh1, b_dao, b_ds, b_dqkv, b_dy2, b_dy1 = (bslot(1 + self.BS * i + k) for k in range(8))
+        s_y1, s_qkv, s_ao, s_y2, s_act = ws.fslot[1 + self.FS * i:1 + self.FS * (i + 1)]
+        b_dh2, b_dact, b_dh1, b_dao, b_ds, b_dqkv, b_dy2, b_dy1 = ws.bslot[1 + self.BS * i:1 + self.BS * (i + 1)]
+        b_below = ws.bslot[1 + self.BS * (i - 1)] if i > 0 else ws.bslot[0]     # max|dh| of the layer below (the embedding's)
         fdh = self.fused_dh and self._bwd_three_terms()      # (hi.hi-only gradient products need the tight measured scales)
         # Hidden dropout: the gradient entering the fc2 / o_proj products is dh o M / (1 - p) (the residual branch keeps dh).
         # The gate is a pass of its own into ws.dhd; the gated tensor gets its own MEASURED scale slot (s_dh2 / s_dh1) - the
@@ -1261,8 +1136,7 @@ class Encoder(nn.Module):
         fdh = fdh and not hd_on
         s_dh2, s_dh1, g_dh = b_dh2, b_dh1, dh
         if hd_on:
-            dslot = lambda n: ws.dslots.data_ptr() + 4 * self.SLOT * n  # noqa: E731
-            s_dh2, s_dh1, g_dh = dslot(2 * i), dslot(2 * i + 1), P(ws.dhd)
+            s_dh2, s_dh1, g_dh = ws.dslot[2 * i], ws.dslot[2 * i + 1], P(ws.dhd)
             self._drop_add(dh, None, g_dh, M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
             L("eav_sp_absmax", g_dh, M, D, D, s_dh2, st)
         # fc2: h_out = h_mid + act.W2^T + b2.  max|dh| is already in b_dh2 (left there by the producer of dh); every
@@ -1271,12 +1145,12 @@ class Encoder(nn.Module):
         if not (fdh and i < c.layers - 1):
             self._to_planes_bias(g_dh, M, D, s_dh2, ws.dhp, gp(f"{Lk}.mlp.fc2.bias"))
         self._wgrad_sp(ws.dhp, s_dh2, ws.actp[i], s_act, gp(f"{Lk}.mlp.fc2.weight"), D, FF, M)
-        wpl, wsl = self._wp(f"fc2{i}", transposed=True)
+        wpl, wsl = self._wplanes.get(f"fc2{i}", transposed=True)
         if self.fused_dact and FF % 8 == 0:
             # data gradient through fc2 and the GELU in one pass, result straight into the planes of dact: its scale comes
             # from |dact| = |(dh W2) gelu'(pre)| <= 1.13 sqrt(D) max|dh| max_j ||W2[:, j]||_2 (max|dh| is in b_dh2, the column
             # norms are refreshed with the weight planes); the epilogue also leaves fc1's bias-gradient partials
-            L("eav_sp_bound_scale", b_dact, s_dh2, self._wplanes["_wcolnorm_fc2"].data_ptr() + 4 * i,
+            L("eav_sp_bound_scale", b_dact, s_dh2, self._wplanes.wcolnorm_fc2.data_ptr() + 4 * i,
               1.13 * float(np.sqrt(D)), st)
             self._before_overwrite(ws.dactp)
             part = self._part_buf("part_cs2_pool")
@@ -1290,7 +1164,7 @@ class Encoder(nn.Module):
             self._to_planes_bias(dact, M, FF, b_dact, ws.dactp, gp(f"{Lk}.mlp.fc1.bias"))
         # fc1
         self._wgrad_sp(ws.dactp, b_dact, ws.y2p[i], s_y2, gp(f"{Lk}.mlp.fc1.weight"), FF, D, M)
-        wpl, wsl = self._wp(f"fc1{i}", transposed=True)
+        wpl, wsl = self._wplanes.get(f"fc1{i}", transposed=True)
         if fdh:
             self._gemm_sp(P(ws.dactp), b_dact, wpl, wsl, dy, M, D, FF, D, amax=b_dy2, blockmax=False)
             self._ln_bwd_planes(dy, P(ws.hmid[i]), w(f"{Lk}.layernorm_after.weight"), stp + 8 * M, stp + 12 * M, dh, b_dh1,
@@ -1308,7 +1182,7 @@ class Encoder(nn.Module):
                 L("eav_sp_absmax", g_dh, M, D, D, s_dh1, st)
             self._to_planes_bias(g_dh, M, D, s_dh1, ws.dhp2, gp(f"{Lk}.attention.o_proj.bias"))
         self._wgrad_sp(ws.dhp2, s_dh1, ws.aop[i], s_ao, gp(f"{Lk}.attention.o_proj.weight"), D, D, M)
-        wpl, wsl = self._wp(f"o{i}", transposed=True)
+        wpl, wsl = self._wplanes.get(f"o{i}", transposed=True)
         # (dao goes to the attention operand preparation: one scale per tensor, no row-block maxima needed)
         self._gemm_sp(P(ws.dhp2), s_dh1, wpl, wsl, dao, M, D, D, D, amax=b_dao if ws.fused else None, blockmax=False)
         # attention core
@@ -1343,19 +1217,19 @@ class Encoder(nn.Module):
         if not (ws.fused and fused_bwd):
             self._to_planes_bias(dqkv, M, 3 * D, b_dqkv, ws.dqkvp, gp(f"{Lk}.attention.q_proj.bias"))
         self._wgrad_sp(ws.dqkvp, b_dqkv, ws.y1p[i], s_y1, gp(f"{Lk}.attention.q_proj.weight"), 3 * D, D, M)
-        wpl, wsl = self._wp(f"qkv{i}", transposed=True)
+        wpl, wsl = self._wplanes.get(f"qkv{i}", transposed=True)
         # the gradient w.r.t. this layer's input is the next (lower) layer's dh: leave its max in that layer's slot
         if fdh and i > 0:
             self._gemm_sp(P(ws.dqkvp), b_dqkv, wpl, wsl, dy, M, D, 3 * D, D, amax=b_dy1, blockmax=False)
             below = Lk.rsplit(".", 1)[0] + f".{i - 1}"
             self._ln_bwd_planes(dy, P(ws.hs[i]), w(f"{Lk}.layernorm_before.weight"), stp, stp + 4 * M, dh,
-                                bslot(1 + self.BS * (i - 1)), b_dh1, b_dy1, ws.dhp, gp(f"{Lk}.layernorm_before.weight"),
+                                b_below, b_dh1, b_dy1, ws.dhp, gp(f"{Lk}.layernorm_before.weight"),
                                 gp(f"{Lk}.layernorm_before.bias"), gp(f"{below}.mlp.fc2.bias"), s_y1)
         else:
             self._gemm_sp(P(ws.dqkvp), b_dqkv, wpl, wsl, dy, M, D, 3 * D, D)
             part = self._part_buf("part_ln_pool")
             L("eav_layernorm_bwd_amax", dy, P(ws.hs[i]), w(f"{Lk}.layernorm_before.weight"), stp, stp + 4 * M, dh, 1,
-              P(part), M, D, bslot(1 + self.BS * (i - 1)) if i > 0 else bslot(0), st)
+              P(part), M, D, b_below, st)
             self._reduce_ln(part, gp(f"{Lk}.layernorm_before.weight"), gp(f"{Lk}.layernorm_before.bias"))
 
     def _ln_bwd_planes(self, dy, x, gamma, mean, rstd, dh, slot_out, slot_old, slot_dy, planes, g_gamma, g_beta, g_bias,
@@ -1380,6 +1254,12 @@ class Encoder(nn.Module):
         """C[M,N] = A^T.B for A stored [K,M], B stored [K,N] (weight gradient: contraction over tokens)."""
         self._call(self._gemm_name() + "_splitk", A, B, C, _lib.ptr(self._ws.splitk), M, N, K, lda, ldb, 1, 1, self._st)
 
+    def _reduce_gamma_beta(self, part, nparts, g_gamma, g_beta):
+        """LayerNorm weight / bias gradients from `part` ([nparts][2 D]: dgamma | dbeta partials), one launch each."""
+        D = self.cfg.hidden
+        self._call("eav_reduce_partials", _lib.ptr(part), nparts, 2 * D, D, 1.0, g_gamma, self._st)
+        self._call("eav_reduce_partials", _lib.ptr(part) + 4 * D, nparts, 2 * D, D, 1.0, g_beta, self._st)
+
     def _reduce_ln(self, part, gw, gb):
         """LayerNorm weight / bias gradients from `part` ([np_ln][2 D]: dgamma | dbeta partials): one launch when the
         two gradients are neighbours in the flat buffer (they are: weight, then bias, D floats each)."""
@@ -1387,34 +1267,86 @@ class Encoder(nn.Module):
         if gb == gw + 4 * D:
             self._reduce_async(part, 0, ws.np_ln, 2 * D, 2 * D, gw)
         else:
-            self._reduce(part, ws.np_ln, 2 * D, D, gw)
-            self._call("eav_reduce_partials", _lib.ptr(part) + 4 * D, ws.np_ln, 2 * D, D, 1.0, gb, self._st)
-
-    def _reduce(self, part, nparts, stride, n, out):
-        self._call("eav_reduce_partials", _lib.ptr(part), nparts, stride, n, 1.0, out, self._st)
+            self._reduce_gamma_beta(part, ws.np_ln, gw, gb)
 
     def _bias_grad(self, dy_ptr, M, N, ld, out):
         ws = self._ws
         self._call("eav_colsum", dy_ptr, _lib.ptr(ws.part_cs), M, N, ld, self._st)
         self._call("eav_reduce_partials", _lib.ptr(ws.part_cs), ws.np_cs, N, N, 1.0, out, self._st)
 
+    def _layer_backward_f32(self, i, Lk, stp, gp, scale):
+        """Backward of one layer on the exact-fp32 kernels: ws.dh holds the gradient w.r.t. the layer output on entry, the
+        gradient w.r.t. the layer input on exit."""
+        c, ws = self.cfg, self._ws
+        P, L, st = _lib.ptr, self._call, self._st
+        D, FF, N, H, M, B = c.hidden, c.ff, c.ntok, c.heads, ws.M, ws.B
+        hd = D // H
+        drop = ws.drop
+        w = lambda k: P(self._pmap[k])  # noqa: E731
+        dh, dy, dao, dact, dqkv = P(ws.dh), P(ws.dy), P(ws.dao), P(ws.dact), P(ws.dqkv)
+        # fc2: h_out = h_mid + Dropout(act.W2^T + b2): the products see dh o M / (1 - p), the residual branch dh
+        g_dh = dh
+        if drop.ph > 0.0:
+            g_dh = P(ws.dhd)
+            self._drop_add(dh, None, g_dh, M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+        self._wgrad(g_dh, P(ws.act[i]), gp(f"{Lk}.mlp.fc2.weight"), D, FF, M, D, FF)
+        self._bias_grad(g_dh, M, D, D, gp(f"{Lk}.mlp.fc2.bias"))
+        self._gemm(g_dh, w(f"{Lk}.mlp.fc2.weight"), dact, M, FF, D, D, FF, FF, tB=1)
+        L("eav_gelu_bwd", dact, P(ws.pre[i]), M * FF, st)
+        # fc1
+        self._wgrad(dact, P(ws.y2[i]), gp(f"{Lk}.mlp.fc1.weight"), FF, D, M, FF, D)
+        self._bias_grad(dact, M, FF, FF, gp(f"{Lk}.mlp.fc1.bias"))
+        self._gemm(dact, w(f"{Lk}.mlp.fc1.weight"), dy, M, D, FF, FF, D, D, tB=1)
+        # layernorm_after: dh (now gradient w.r.t. h_mid) += LN backward
+        L("eav_layernorm_bwd", dy, P(ws.hmid[i]), w(f"{Lk}.layernorm_after.weight"), stp + 8 * M,
+          stp + 12 * M, dh, 1, P(ws.part_ln), M, D, st)
+        self._reduce_gamma_beta(ws.part_ln, ws.np_ln, gp(f"{Lk}.layernorm_after.weight"), gp(f"{Lk}.layernorm_after.bias"))
+        # o_proj
+        if drop.ph > 0.0:
+            self._drop_add(dh, None, g_dh, M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+        self._wgrad(g_dh, P(ws.ao[i]), gp(f"{Lk}.attention.o_proj.weight"), D, D, M, D, D)
+        self._bias_grad(g_dh, M, D, D, gp(f"{Lk}.attention.o_proj.bias"))
+        self._gemm(g_dh, w(f"{Lk}.attention.o_proj.weight"), dao, M, D, D, D, D, D, tB=1)
+        # attention core
+        qkv = P(ws.qkv[i])
+        if ws.fused and drop.pa > 0.0:
+            L("eav_attn_bwd_dropout", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale,
+              drop.pa, self._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
+        elif ws.fused:
+            L("eav_attn_bwd", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale, st)
+        else:     # materialised scores, batched over (image, head)
+            self._attention_backward_scores(self._gemm, i, qkv, dao, dqkv, scale)
+        # fused q/k/v projection
+        self._wgrad(dqkv, P(ws.y1[i]), gp(f"{Lk}.attention.q_proj.weight"), 3 * D, D, M, 3 * D, D)
+        self._bias_grad(dqkv, M, 3 * D, 3 * D, gp(f"{Lk}.attention.q_proj.bias"))
+        self._gemm(dqkv, w(f"{Lk}.attention.q_proj.weight"), dy, M, D, 3 * D, 3 * D, D, D, tB=1)
+        L("eav_layernorm_bwd", dy, P(ws.hs[i]), w(f"{Lk}.layernorm_before.weight"), stp, stp + 4 * M, dh, 1,
+          P(ws.part_ln), M, D, st)
+        self._reduce_gamma_beta(ws.part_ln, ws.np_ln, gp(f"{Lk}.layernorm_before.weight"), gp(f"{Lk}.layernorm_before.bias"))
+
+    def _grad_views(self, full):
+        """What a backward hands to autograd, in the order of the parameters the forward took: views of the flat
+        gradient buffer for the trained parameters (the classifier alone unless `full`), None for the others."""
+        gflat, offs, pm = self._flat[1], self._flat[2], self._pmap
+        out = []
+        for k in self._names:
+            p = pm[k]
+            trained = p.requires_grad and (full or k.startswith("classifier."))
+            out.append(gflat[offs[k][0]:offs[k][0] + offs[k][1]].view(p.shape) if trained else None)
+        return out
+
     def _launch_backward(self, dlogits, token):
-        if self._saved is None or self._saved[0] != token:
-            raise _lib.EavError("Encoder.backward: activations were overwritten by a later forward")
+        self._check_token(token)
         c = self.cfg
         P, L = _lib.ptr, self._call
-        self._main = torch.cuda.current_stream()
-        st = self._st = self._main.cuda_stream
+        st = self._begin()
         self._phase = "bwd"
-        _, x, full, _ = self._saved
+        full = self._saved[2]
         ws = self._ws
-        B, M, ldn = ws.B, ws.M, ws.ldn
-        D, FF, N, H = c.hidden, c.ff, c.ntok, c.heads
-        hd = D // H
-        pm = self._pmap
-        flat, gflat, offs = self._flat
+        B, M, sp = ws.B, ws.M, ws.sp
+        D, N = c.hidden, c.ntok
+        _, gflat, offs = self._flat
         gp = lambda k: gflat.data_ptr() + 4 * offs[k][0]  # noqa: E731
-        w = lambda k: P(pm[k])  # noqa: E731
         pre = c.prefix
         R = B * c.nextra
         # ---- head
@@ -1423,84 +1355,31 @@ class Encoder(nn.Module):
             L("eav_pair_mean", P(ws.dseqr), P(ws.dpooled), B, D, 1, st)
         if full:
             sf = P(ws.stf)
-            L("eav_layernorm_bwd", P(ws.dseqr), P(ws.rows), w(f"{pre}.layernorm.weight"), sf, sf + 4 * R,
+            L("eav_layernorm_bwd", P(ws.dseqr), P(ws.rows), P(self._pmap[f"{pre}.layernorm.weight"]), sf, sf + 4 * R,
               P(ws.drows), 0, P(ws.part_lnr), R, D, st)
-            self._reduce(ws.part_lnr, ws.np_lnr, 2 * D, D, gp(f"{pre}.layernorm.weight"))
-            L("eav_reduce_partials", P(ws.part_lnr) + 4 * D, ws.np_lnr, 2 * D, D, 1.0, gp(f"{pre}.layernorm.bias"), st)
+            self._reduce_gamma_beta(ws.part_lnr, ws.np_lnr, gp(f"{pre}.layernorm.weight"), gp(f"{pre}.layernorm.bias"))
             ws.dh.zero_()
             L("eav_token_rows", P(ws.dh), P(ws.drows), B, N, D, c.nextra, 1, st)
-            scale = hd ** -0.5
-            dh, dy, dao, dact, dqkv = P(ws.dh), P(ws.dy), P(ws.dao), P(ws.dact), P(ws.dqkv)
-            sp = ws.sp
+            scale = (D // c.heads) ** -0.5
+            dh = P(ws.dh)
             drop = ws.drop
             if sp and drop.ph > 0.0:
                 ws.dslots.zero_()
             if sp:
                 ws.bslots.zero_()
-                bslot = lambda n: ws.bslots.data_ptr() + 4 * self.SLOT * n  # noqa: E731
-                fslot = lambda n: ws.fslots.data_ptr() + 4 * self.SLOT * n  # noqa: E731
                 # dh of the top layer comes from the head (token-row scatter): one pass for its maximum; every other dh
                 # gets its maximum from the LayerNorm backward that produces it
-                self._call("eav_sp_absmax", P(ws.dh), M, D, D, bslot(1 + self.BS * (c.layers - 1)), st)
+                self._call("eav_sp_absmax", dh, M, D, D, ws.bslot[1 + self.BS * (c.layers - 1)], st)
+            # ---- layers
+            layer = self._layer_backward_split if sp else self._layer_backward_f32
             for i in reversed(range(c.layers)):
                 Lk = f"{pre}.layers.{i}"
-                stp = P(ws.st[i])
-                if sp:
-                    self._layer_backward_split(i, Lk, stp, gp, bslot, fslot, scale)
-                    if self.grad_ready_hook is not None:
-                        self._join_wgrads()         # the layer's weight gradients must be complete before they travel
-                        lo = offs[f"{Lk}.attention.q_proj.weight"][0]
-                        hi = offs[f"{Lk}.mlp.fc2.bias"][0] + offs[f"{Lk}.mlp.fc2.bias"][1]
-                        self.grad_ready_hook(lo, hi)
-                    continue
-                # fc2: h_out = h_mid + Dropout(act.W2^T + b2): the products see dh o M / (1 - p), the residual branch dh
-                g_dh = dh
-                if drop.ph > 0.0:
-                    g_dh = P(ws.dhd)
-                    self._drop_add(dh, None, g_dh, M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
-                self._wgrad(g_dh, P(ws.act[i]), gp(f"{Lk}.mlp.fc2.weight"), D, FF, M, D, FF)
-                self._bias_grad(g_dh, M, D, D, gp(f"{Lk}.mlp.fc2.bias"))
-                self._gemm(g_dh, w(f"{Lk}.mlp.fc2.weight"), dact, M, FF, D, D, FF, FF, tB=1)
-                L("eav_gelu_bwd", dact, P(ws.pre[i]), M * FF, st)
-                # fc1
-                self._wgrad(dact, P(ws.y2[i]), gp(f"{Lk}.mlp.fc1.weight"), FF, D, M, FF, D)
-                self._bias_grad(dact, M, FF, FF, gp(f"{Lk}.mlp.fc1.bias"))
-                self._gemm(dact, w(f"{Lk}.mlp.fc1.weight"), dy, M, D, FF, FF, D, D, tB=1)
-                # layernorm_after: dh (now gradient w.r.t. h_mid) += LN backward
-                L("eav_layernorm_bwd", dy, P(ws.hmid[i]), w(f"{Lk}.layernorm_after.weight"), stp + 8 * M,
-                  stp + 12 * M, dh, 1, P(ws.part_ln), M, D, st)
-                self._reduce(ws.part_ln, ws.np_ln, 2 * D, D, gp(f"{Lk}.layernorm_after.weight"))
-                L("eav_reduce_partials", P(ws.part_ln) + 4 * D, ws.np_ln, 2 * D, D, 1.0,
-                  gp(f"{Lk}.layernorm_after.bias"), st)
-                # o_proj
-                if drop.ph > 0.0:
-                    self._drop_add(dh, None, g_dh, M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
-                self._wgrad(g_dh, P(ws.ao[i]), gp(f"{Lk}.attention.o_proj.weight"), D, D, M, D, D)
-                self._bias_grad(g_dh, M, D, D, gp(f"{Lk}.attention.o_proj.bias"))
-                self._gemm(g_dh, w(f"{Lk}.attention.o_proj.weight"), dao, M, D, D, D, D, D, tB=1)
-                # attention core
-                qkv = P(ws.qkv[i])
-                if ws.fused and drop.pa > 0.0:
-                    L("eav_attn_bwd_dropout", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale,
-                      drop.pa, self._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
-                elif ws.fused:
-                    L("eav_attn_bwd", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale, st)
-                else:     # materialised scores, batched over (image, head)
-                    self._attention_backward_scores(self._gemm, i, qkv, dao, dqkv, scale)
-                # fused q/k/v projection
-                self._wgrad(dqkv, P(ws.y1[i]), gp(f"{Lk}.attention.q_proj.weight"), 3 * D, D, M, 3 * D, D)
-                self._bias_grad(dqkv, M, 3 * D, 3 * D, gp(f"{Lk}.attention.q_proj.bias"))
-                self._gemm(dqkv, w(f"{Lk}.attention.q_proj.weight"), dy, M, D, 3 * D, 3 * D, D, D, tB=1)
-                L("eav_layernorm_bwd", dy, P(ws.hs[i]), w(f"{Lk}.layernorm_before.weight"), stp, stp + 4 * M, dh, 1,
-                  P(ws.part_ln), M, D, st)
-                self._reduce(ws.part_ln, ws.np_ln, 2 * D, D, gp(f"{Lk}.layernorm_before.weight"))
-                L("eav_reduce_partials", P(ws.part_ln) + 4 * D, ws.np_ln, 2 * D, D, 1.0,
-                  gp(f"{Lk}.layernorm_before.bias"), st)
+                layer(i, Lk, P(ws.st[i]), gp, scale)
                 if self.grad_ready_hook is not None:   # layer i's parameters are one contiguous slice
-                    lo = offs[f"{Lk}.attention.q_proj.weight"][0]
-                    hi = offs[f"{Lk}.mlp.fc2.bias"][0] + offs[f"{Lk}.mlp.fc2.bias"][1]
-                    self.grad_ready_hook(lo, hi)
-            # embeddings ("emb" dropout: dh is final here, so its gate runs in place)
+                    self._join_wgrads()         # the layer's weight gradients must be complete before they travel
+                    last = offs[f"{Lk}.mlp.fc2.bias"]
+                    self.grad_ready_hook(offs[f"{Lk}.attention.q_proj.weight"][0], last[0] + last[1])
+            # ---- embeddings ("emb" dropout: dh is final here, so its gate runs in place)
             if drop.ph > 0.0:
                 self._drop_add(dh, None, dh, M * D, drop.ph, 0, "emb")
             L("eav_embed_bwd", dh, gp(f"{pre}.embeddings.position_embeddings"), P(ws.demb), B, N, D, c.nextra, st)
@@ -1513,9 +1392,9 @@ class Encoder(nn.Module):
                 # demb (the patch rows of dh) gets its own maximum pass: the slot layer 0's LayerNorm backward filled is
                 # indexed by the rows of dh (cls / distillation rows included), and the per-row-block maxima must be the
                 # converted tensor's own
-                s_demb = bslot(1 + self.BS * c.layers)
+                s_demb = ws.bslot[1 + self.BS * c.layers]
                 self._to_planes(P(ws.demb), MP, D, D, s_demb, ws.dembp)
-                self._wgrad_sp(ws.dembp, s_demb, ws.colp, fslot(0),
+                self._wgrad_sp(ws.dembp, s_demb, ws.colp, ws.fslot[0],
                                gp(f"{pre}.embeddings.patch_embeddings.projection.weight"), D, c.kp, MP)
             else:
                 self._wgrad(P(ws.demb), P(ws.col), gp(f"{pre}.embeddings.patch_embeddings.projection.weight"), D, c.kp,
@@ -1524,12 +1403,7 @@ class Encoder(nn.Module):
             self._call("eav_reduce_partials", P(ws.part_cs), _lib.plain("eav_colsum_nparts", MP), D, D, 1.0,
                        gp(f"{pre}.embeddings.patch_embeddings.projection.bias"), st)
         self._join_wgrads()          # side-stream weight gradients complete before autograd / the optimiser see them
-        out = []
-        for k in self._names:
-            p = pm[k]
-            trained = p.requires_grad and (full or k.startswith("classifier."))
-            out.append(gflat[offs[k][0]:offs[k][0] + offs[k][1]].view(p.shape) if trained else None)
-        return out
+        return self._grad_views(full)
 
 
 def ASTForAudioClassification(cfg=None, weights=None):

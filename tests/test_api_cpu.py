@@ -360,12 +360,12 @@ def test_bench_subject_job_record_and_multi_gpu_headline():
 
 def test_runtime_module_is_shared_by_the_models_and_reexported_by_eegnet():
     """eav_amd.runtime holds the training runtime and the models' base class: it imports no model module, eegnet keeps the
-    old import path alive with the same objects, the five models derive from KernelModule, and GraphStep refuses
-    anything else."""
+    old import path alive with the same objects, the models (the AST / ViT Encoder among them) derive from KernelModule,
+    and GraphStep refuses anything else."""
     import copy
     import eav_amd.eegnet as eg
     import eav_amd.runtime as rt
-    from eav_amd import _lib
+    from eav_amd import _lib, transformer as T
     from eav_amd.cnn_audio import AudioModel
     from eav_amd.cnn_eeg import EEGNet
     from eav_amd.optim import FusedAdam
@@ -374,7 +374,8 @@ def test_runtime_module_is_shared_by_the_models_and_reexported_by_eegnet():
     assert sorted(set(re.findall(r"^from \.(\w*) import", src, flags=re.M))) == ["", "optim"] and "\nimport eav_amd" not in src
     for name in ("cached_workspace", "gather_batch", "GraphStep", "DeviceLoader"):
         assert getattr(eg, name) is getattr(rt, name) and getattr(rt, name).__module__ == "eav_amd.runtime"
-    for model in (eg.EEGNet_tor(5), EEGNet(5), ShallowConvNet(5, num_layers=1), AudioModel()):
+    for model in (eg.EEGNet_tor(5), EEGNet(5), ShallowConvNet(5, num_layers=1), AudioModel(),
+                  T.Encoder(T.make_config("vit", hidden=32, layers=1, heads=2, ff=64, image=32))):
         assert isinstance(model, rt.KernelModule) and model._wss == {} and model._flat is None
         twin = copy.deepcopy(model)
         assert list(twin.state_dict()) == list(model.state_dict()) and twin._wss is not model._wss
@@ -385,6 +386,57 @@ def test_runtime_module_is_shared_by_the_models_and_reexported_by_eegnet():
     lin = torch.nn.Linear(2, 2)
     with pytest.raises(_lib.EavError, match="KernelModule"):
         rt.GraphStep(lin, FusedAdam(lin.parameters(), capturable=True), None, torch.zeros(4, 2), torch.zeros(4), 2)
+
+
+@pytest.mark.parametrize("kind", ["ast", "vit"])
+def test_encoder_flat_layout_is_the_param_shapes_order(kind):
+    """The Encoder's flat buffer follows param_shapes (q, k, v weights adjacent, then their biases - the fused q/k/v GEMM,
+    _forward_scales, head_grad_ranges and grad_ready_hook rely on it), every tensor rounded up to 4 floats; that is not the
+    named_parameters() order."""
+    from eav_amd import transformer as T
+    cfg = T.make_config(kind, hidden=32, layers=1, heads=2, ff=64, image=32)
+    model = T.Encoder(cfg)
+    model._ensure_flat()
+    want, total = {}, 0
+    for k, shp in T.param_shapes(cfg).items():
+        want[k] = (total, int(np.prod(shp)))
+        total += (want[k][1] + 3) // 4 * 4
+    assert model._flat[2] == want and list(model._flat[2]) == list(want) and model._flat[0].numel() == total
+    assert model._names == list(want) and model._names != [n for n, _ in model.named_parameters()]
+    for k, p in model.named_parameters():
+        assert p.data_ptr() == model._flat[0].data_ptr() + 4 * want[k][0], k
+
+
+def test_weight_planes_staleness_is_decided_without_a_launch():
+    """WeightPlanes.stale: which matrices' planes must be rebuilt, from the flat buffer's address, the version counters,
+    the byte ranges the optimiser reported and whether transposes are needed - host arithmetic only."""
+    from eav_amd import transformer as T
+    from eav_amd.weight_planes import WeightPlanes
+    cfg = T.make_config("vit", hidden=32, layers=2, heads=2, ff=64, image=32)
+    model = T.Encoder(cfg)
+    model._ensure_flat()
+    offs = model._flat[2]
+    mats = [(k, 4 * offs[pn][0], out, inn) for k, pn, out, inn in model._weight_keys()]
+    every = [k for k, _, _, _ in mats]
+    assert every == ["patch", "qkv0", "o0", "fc10", "fc20", "qkv1", "o1", "fc11", "fc21"]
+    wp = WeightPlanes(mats, cfg.layers, torch.device("cpu"), False)
+    base, versions = 1 << 20, (0, 7)
+    assert wp.stale(base, versions, [], False) == every            # never refreshed
+    wp.key = (base, versions)                                      # (what refresh() leaves behind)
+    assert wp.stale(base, versions, [], False) == []
+    at = {k: (base + off, base + off + 4 * out * inn) for k, off, out, inn in mats}
+    lo, hi = at["fc11"]
+    assert wp.stale(base, versions, [(lo + 8, lo + 12)], False) == ["fc11"]
+    assert wp.stale(base, versions, [(hi - 4, hi)], False) == ["fc11"] and wp.stale(base, versions, [(hi, hi + 4)], False) == []
+    assert wp.stale(base, versions, [(at["o1"][1] - 4, lo + 4)], False) == ["o1", "fc11"]     # a range over two matrices
+    assert wp.stale(base, versions, [(at["qkv0"][0], at["qkv0"][0] + 4), (at["fc21"][1] - 4, at["fc21"][1])],
+                    False) == ["qkv0", "fc21"]
+    assert wp.stale(base, (0, 8), [], False) == every              # a parameter's version moved
+    assert wp.stale(base, (1, 7), [], False) == every              # the flat buffer's version moved
+    assert wp.stale(base + 64, versions, [], False) == every       # the flat buffer was rebuilt
+    assert wp.stale(base, versions, [], True) == every             # transposes needed, none held
+    wp.invalidate()
+    assert wp.stale(base, versions, [], False) == every
 
 
 def test_split_gemm_instantiations_are_scratch_free():

@@ -246,7 +246,7 @@ def test_replayed_captured_step_draws_a_fresh_mask_every_replay(precision):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         static_logits = step()
-    model._ws.pinned = True
+    model._pin_workspace()
     seen = []
     for k in range(3):
         graph.replay()

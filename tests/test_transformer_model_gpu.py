@@ -374,7 +374,7 @@ def test_training_step_after_an_evaluation_forward_keeps_the_weight_norms(kind):
         opt.zero_grad()
         CrossEntropyLoss()(model(xd).logits, yd).backward()
         torch.cuda.synchronize()
-        norms = model._wplanes["_wcolnorm_fc2"].clone()
+        norms = model._wplanes.wcolnorm_fc2.clone()
         return {k: p.grad.clone() for k, p in model.named_parameters()}, norms
 
     g1, norms = run(True)
@@ -435,3 +435,95 @@ def test_ab_switches_keep_the_attention_backward_consistent(switch):
             continue
         rel = float((grads["split"][k] - ref).norm() / ref.norm().clamp_min(1e-30))
         assert rel < 1e-3, (k, rel)
+
+
+# ============================================================================================ KernelModule plumbing
+_STEP_IDX = [[0, 1], [2, 3], [4, 5], [1, 4], [5, 0], [3, 2]]
+
+
+def _small_vit(precision):
+    """ViT with head_dim 64 (the fused-attention path), 5 tokens, no dropout, one stream; (model, its configuration)."""
+    from eav_amd import transformer as T
+    torch.manual_seed(11)
+    cfg = T.make_config("vit", hidden=128, heads=2, ff=256, layers=2, image=32)
+    model = T.Encoder(cfg)
+    model.precision, model.overlap_wgrad = precision, False
+    return model, cfg
+
+
+def _graph_and_twin(precision):
+    """A GraphStep over an Encoder after five run() calls (two eager, the capture, two replays) and a twin driven by
+    eager_step over the same index batches: (graph step, model, twin's step function, losses of both)."""
+    import copy
+    from eav_amd.optim import CrossEntropyLoss, FusedAdam
+    from eav_amd.runtime import GraphStep, eager_step, gather_batch
+    model, cfg = _small_vit(precision)
+    twin = copy.deepcopy(model)
+    model, twin = model.cuda().train(), twin.cuda().train()
+    x, y = synth.frame_batch(21, 6, cfg.H)
+    xs, ys = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    crit = CrossEntropyLoss()
+    opt = FusedAdam(model.parameters(), lr=1e-3, weight_decay=0.01, decoupled=True, capturable=True)
+    topt = FusedAdam(twin.parameters(), lr=1e-3, weight_decay=0.01, decoupled=True, capturable=True)
+    gs = GraphStep(model, opt, crit, xs, ys, 2)
+
+    def twin_step(idx):
+        data, targets = gather_batch(xs, ys, torch.as_tensor(idx, dtype=torch.long, device=xs.device))
+        return eager_step(lambda d: twin(d).logits, topt, crit, data, targets)[1].clone()
+
+    got = [gs.run(idx)[1].clone() for idx in _STEP_IDX[:5]]
+    want = [twin_step(idx) for idx in _STEP_IDX[:5]]
+    torch.cuda.synchronize()
+    return gs, model, twin, twin_step, got, want
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_graph_step_takes_an_encoder(precision):
+    """GraphStep accepts the Encoder (a KernelModule): eager, captured and replayed steps give the losses and the final
+    parameters of a twin stepped eagerly, bit for bit."""
+    gs, model, twin, _, got, want = _graph_and_twin(precision)
+    assert gs.graph is not None
+    for s, (a, b) in enumerate(zip(got, want)):
+        assert torch.equal(a, b), (s, float(a), float(b))
+    assert torch.equal(model._flat[0], twin._flat[0])
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_captured_encoder_workspace_survives_eviction(precision):
+    """The workspace a hipGraph was captured with is pinned: forwards at four other batch sizes evict each other, never it,
+    and the next replay still computes the twin's next step."""
+    gs, model, twin, twin_step, _, _ = _graph_and_twin(precision)
+    captured = model._ws
+    assert captured.pinned and captured.B == 2
+    x = torch.from_numpy(synth.frame_batch(22, 5, model.cfg.H)[0]).cuda()
+    with torch.no_grad():
+        for B in (1, 3, 4, 5):
+            model(x[:B])
+    assert model._ws.B == 5 and any(w is captured for w in model._wss.values()) and captured.pinned
+    assert sum(1 for w in model._wss.values() if not getattr(w, "pinned", False)) <= 3
+    loss = gs.run(_STEP_IDX[5])[1].clone()
+    assert torch.equal(loss, twin_step(_STEP_IDX[5]))
+    assert torch.equal(model._flat[0], twin._flat[0])
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_encoder_workspace_is_reused_and_replaced_not_duplicated(precision):
+    """One workspace per (batch size, device, attention path, precision): the training one also serves a no_grad forward of
+    the same batch size, and one allocated by a no_grad forward is replaced when a training step comes."""
+    from eav_amd.optim import CrossEntropyLoss
+    x, y = synth.frame_batch(23, 2, 32)
+    x, y = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    model = _small_vit(precision)[0].cuda().train()
+    CrossEntropyLoss()(model(x).logits, y).backward()
+    ws = model._ws
+    assert ws.full and len(model._wss) == 1
+    with torch.no_grad():
+        model(x)
+    assert model._ws is ws and len(model._wss) == 1
+    fresh = _small_vit(precision)[0].cuda().train()
+    with torch.no_grad():
+        fresh(x)
+    first = fresh._ws
+    assert not first.full and len(fresh._wss) == 1
+    CrossEntropyLoss()(fresh(x).logits, y).backward()
+    assert fresh._ws is not first and fresh._ws.full and len(fresh._wss) == 1

@@ -63,8 +63,7 @@ def main():
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         loss = sg()
-    if getattr(mg, "_ws", None) is not None:
-        mg._ws.pinned = True
+    mg._pin_workspace()
 
     def replay():
         g.replay()
