@@ -2,8 +2,10 @@
 
 API of Transformer_torch/Transformer_Audio.py:9-103:
     AudioModelTrainer(DATA, model_path, sub='', num_classes=5, weight_decay=1e-5, lr=0.001, batch_size=128)
-        .train(epochs=20, lr=None, freeze=True)      attribute: outputs_test  (float32 [N_test, 5])
+        .train(epochs=20, lr=None, freeze=True)      attribute: outputs_test  (float32 [N_test, num_classes])
 The model is eav_amd.transformer.Encoder (HIP kernels) instead of the Hugging Face ASTForAudioClassification;
+`model_path` may be the stock download (ast-finetuned-audioset: a 527-label head, loaded and then replaced, as
+Transformer_Audio.py:22-24 does) and `num_classes` anything up to transformer.HEAD_MAX_CLASSES;
 equal-length clips go through the HIP log-mel front-end, ragged ones through the reference's own host call of
 ASTFeatureExtractor.  Kept quirks: `weight_decay` is accepted and ignored (Q10); one optimiser spans both phases
 (Q11); outputs_test only after the last unfrozen epoch (Q15); one line per epoch appended to

@@ -29,6 +29,9 @@ class FineTuneBase:
     """Owns model, optimiser, loaders; subclasses provide the reference-specific reporting."""
 
     def _build(self, model_path, n_classes, lr, device):
+        """The reference's order (Transformer_Audio.py:22-24, Transformer_Vision.py:29-30): load the checkpoint with the
+        head its config.json describes - 527 AudioSet or 1000 ImageNet classes for the stock downloads - then replace
+        that head by a fresh Linear(hidden, n_classes); 1 <= n_classes <= transformer.HEAD_MAX_CLASSES."""
         self.device = device
         self.model = Encoder.from_pretrained(model_path)
         in_features = self.model.cfg.hidden

@@ -14,6 +14,8 @@ unfrozen fine-tuning phases give the head and the backbone different counts
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import _lib
@@ -173,13 +175,12 @@ class FusedAdam(torch.optim.Optimizer):
 
 class _CEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, scores, targets, flag):
+    def forward(ctx, scores, targets, flag, scratch=None):
         B, NC = scores.shape
         loss = torch.empty((), dtype=torch.float32, device=scores.device)
         need_grad = ctx.needs_input_grad[0]
         dsc = torch.empty_like(scores) if need_grad else None      # no gradient buffer under no_grad (validate())
-        _lib.call("eav_ce_fwd_bwd", scores.data_ptr(), targets.data_ptr(), loss.data_ptr(), _lib.ptr(dsc), None,
-                  flag.data_ptr(), B, NC, _lib.stream_ptr())
+        _ce_launch(scratch, scores, targets, loss, dsc, None, flag)
         ctx.dsc = dsc
         return loss
 
@@ -194,8 +195,24 @@ class _CEFn(torch.autograd.Function):
             out = ctx.dsc.clone()
             _lib.call("eav_scale_by_scalar", out.data_ptr(), gout.contiguous().data_ptr(), out.numel(),
                       _lib.stream_ptr())
-            return out, None, None
-        return ctx.dsc, None, None
+            return out, None, None, None
+        return ctx.dsc, None, None, None
+
+
+# classes the narrow head kernels are meant for (eav_dense_softmax_* keeps them in registers, eav_ce_fwd_bwd walks a row
+# with one thread); Encoder.head_algo and CrossEntropyLoss.head_algo switch to the wide kernels above it
+HEAD_NARROW_CLASSES = 16
+
+
+def _ce_launch(scratch, scores, targets, loss, dsc, ncorrect, flag):
+    """eav_ce_fwd_bwd (scratch None), or eav_ce_wide_fwd_bwd (one wave per row) with its per-row scratch."""
+    B, NC = scores.shape
+    if scratch is not None:
+        _lib.call("eav_ce_wide_fwd_bwd", scores.data_ptr(), targets.data_ptr(), loss.data_ptr(), _lib.ptr(dsc),
+                  _lib.ptr(ncorrect), flag.data_ptr(), scratch.data_ptr(), B, NC, _lib.stream_ptr())
+    else:
+        _lib.call("eav_ce_fwd_bwd", scores.data_ptr(), targets.data_ptr(), loss.data_ptr(), _lib.ptr(dsc),
+                  _lib.ptr(ncorrect), flag.data_ptr(), B, NC, _lib.stream_ptr())
 
 
 _UNIT = {}
@@ -219,10 +236,34 @@ class CrossEntropyLoss:
     any other class index outside [0, classes) is rejected: the kernel never indexes with such a label (the row
     contributes nothing to the loss and receives a zero gradient) and records it in a device flag; ``check()`` reads the flag (one host synchronisation) and
     raises.  The trainers call it once per epoch - a per-step check would serialise host and GPU; code that drives the
-    criterion directly calls ``check()`` whenever it synchronises anyway."""
+    criterion directly calls ``check()`` whenever it synchronises anyway.
+
+    ``head_algo`` routes by the class count like ``Encoder.head_algo``: "auto" (default; EAV_HEAD_ALGO overrides) takes
+    eav_ce_wide_fwd_bwd above 16 classes and eav_ce_fwd_bwd up to there, "wide" forces the former at any width and
+    "narrow" the latter, which raises above 16 classes as the Encoder's does.  The wide kernel's per-row scratch is kept
+    on the criterion, one buffer per (batch, device): nothing is allocated for it in the launch path."""
 
     def __init__(self):
         self._flag = None
+        self._scratch = {}
+        self.head_algo = os.environ.get("EAV_HEAD_ALGO", "auto")
+
+    def _wide(self, classes):
+        if self.head_algo not in ("auto", "wide", "narrow"):
+            raise ValueError(f"head_algo {self.head_algo!r}: expected 'auto', 'wide' or 'narrow'")
+        if self.head_algo == "narrow" and classes > HEAD_NARROW_CLASSES:
+            raise NotImplementedError(f"head_algo 'narrow' takes at most {HEAD_NARROW_CLASSES} classes, the scores have {classes}")
+        return self.head_algo == "wide" or (self.head_algo == "auto" and classes > HEAD_NARROW_CLASSES)
+
+    def _scratch_for(self, scores):
+        """The wide kernel's row terms for this batch size (None: the narrow kernel runs)."""
+        B, NC = scores.shape
+        if not self._wide(NC):
+            return None
+        key = (B, scores.device)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(_lib.plain("eav_ce_wide_ws_floats", B), dtype=torch.float32, device=scores.device)
+        return self._scratch[key]
 
     def check(self):
         if self._flag is not None:
@@ -253,8 +294,7 @@ class CrossEntropyLoss:
             targets = targets.long()
         if self._flag is None or self._flag.device != scores.device:
             self._flag = torch.zeros((), dtype=torch.int32, device=scores.device)
-        _lib.call("eav_ce_fwd_bwd", scores.data_ptr(), targets.contiguous().data_ptr(), loss_out.data_ptr(), None,
-                  ncorrect.data_ptr(), self._flag.data_ptr(), scores.shape[0], scores.shape[1], _lib.stream_ptr())
+        _ce_launch(self._scratch_for(scores), scores, targets.contiguous(), loss_out, None, ncorrect, self._flag)
 
     def __call__(self, scores, targets):
         if not isinstance(scores, torch.Tensor) or not scores.is_cuda or not targets.is_cuda:
@@ -268,4 +308,4 @@ class CrossEntropyLoss:
             targets = targets.long()
         if self._flag is None or self._flag.device != scores.device:
             self._flag = torch.zeros((), dtype=torch.int32, device=scores.device)
-        return _CEFn.apply(scores, targets.contiguous(), self._flag)
+        return _CEFn.apply(scores, targets.contiguous(), self._flag, self._scratch_for(scores))

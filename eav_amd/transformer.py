@@ -33,16 +33,21 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .optim import flatten_parameters
+from .optim import HEAD_NARROW_CLASSES, flatten_parameters
 from .runtime import KernelFn, KernelModule, gather_batch
 from .weight_planes import SLOT, WeightPlanes
 
 
 DEFAULT_PRECISION = "split"
+# Classes the classification head takes: up to HEAD_NARROW_CLASSES (16, optim.py) on eav_dense_softmax_* (the classes in
+# registers), beyond that on eav_dense_wide_* (csrc/head_wide.hip; EAV_HEAD_MAX_CLASSES of include/eav_hip.h) - AudioSet's
+# 527, ImageNet's 1000, ImageNet-21k's 21 843.
+HEAD_MAX_CLASSES = 32768
 
 # ----------------------------------------------------------------------------- configuration
 def make_config(kind, hidden=768, layers=12, heads=12, ff=3072, eps=1e-12, num_labels=5, patch=16, mel=128,
-                frames=1024, fstride=10, tstride=10, image=224, channels=3, hidden_dropout=0.0, attention_dropout=0.0):
+                frames=1024, fstride=10, tstride=10, image=224, channels=3, hidden_dropout=0.0, attention_dropout=0.0,
+                id2label=None):
     """hidden_dropout / attention_dropout: HF hidden_dropout_prob / attention_probs_dropout_prob, applied in training mode
     at the four sites of Encoder.dropout_sites; 0 <= p < 1 (0: the site does not exist)."""
     for name, p in (("hidden_dropout", hidden_dropout), ("attention_dropout", attention_dropout)):
@@ -61,17 +66,21 @@ def make_config(kind, hidden=768, layers=12, heads=12, ff=3072, eps=1e-12, num_l
     return SimpleNamespace(kind=kind, hidden=hidden, layers=layers, heads=heads, ff=ff, eps=eps,
                            num_labels=num_labels, patch=patch, ny=ny, nx=nx, npatch=ny * nx, nextra=nextra,
                            ntok=ny * nx + nextra, prefix=prefix, kp=geo["C"] * patch * patch,
-                           hidden_dropout=float(hidden_dropout), attention_dropout=float(attention_dropout), **geo)
+                           hidden_dropout=float(hidden_dropout), attention_dropout=float(attention_dropout),
+                           id2label=id2label, **geo)
 
 
 def config_from_hf(cfg_json: dict):
+    """cfg.id2label: the label names of the checkpoint's config.json as a list ordered by class index (None without them)."""
     mt = cfg_json.get("model_type", "")
+    names = cfg_json.get("id2label")
     common = dict(hidden=cfg_json.get("hidden_size", 768), layers=cfg_json.get("num_hidden_layers", 12),
                   heads=cfg_json.get("num_attention_heads", 12), ff=cfg_json.get("intermediate_size", 3072),
                   eps=cfg_json.get("layer_norm_eps", 1e-12), patch=cfg_json.get("patch_size", 16),
                   num_labels=len(cfg_json["id2label"]) if "id2label" in cfg_json else cfg_json.get("num_labels", 2),
                   hidden_dropout=cfg_json.get("hidden_dropout_prob", 0.0),
-                  attention_dropout=cfg_json.get("attention_probs_dropout_prob", 0.0))
+                  attention_dropout=cfg_json.get("attention_probs_dropout_prob", 0.0),
+                  id2label=[names[k] for k in sorted(names, key=int)] if names else None)
     if cfg_json.get("hidden_act", "gelu") != "gelu":
         raise NotImplementedError("only the exact erf GELU is implemented")
     if mt == "audio-spectrogram-transformer":
@@ -198,7 +207,8 @@ class _HeadFn(torch.autograd.Function):
 
 
 class Encoder(KernelModule):
-    """ASTForAudioClassification / ViTForImageClassification (5-class head) on the HIP kernels.  The flat parameter
+    """ASTForAudioClassification / ViTForImageClassification on the HIP kernels, with a head of 1 .. HEAD_MAX_CLASSES
+    classes (the reference's 5, or the 527 / 1000 of the stock checkpoints it starts from).  The flat parameter
     layout is the param_shapes order (q, k, v weights adjacent), not the named_parameters() order."""
 
     def __init__(self, cfg, weights=None):
@@ -230,6 +240,10 @@ class Encoder(KernelModule):
         # "bf16" (bf16 MFMA operands everywhere, fp32 accumulate: ~5e-3 logit drift) or "bf16_bwd" (fp32 forward -
         # logits unchanged - and bf16 operands for the backward products only).  EAV_ENCODER_PRECISION overrides.
         self.precision = os.environ.get("EAV_ENCODER_PRECISION", DEFAULT_PRECISION)
+        # classification Linear: "auto" (default) takes eav_dense_wide_* above HEAD_NARROW_CLASSES classes and
+        # eav_dense_softmax_* up to there, "wide" forces the former at any width (tests), "narrow" the latter - it raises
+        # above HEAD_NARROW_CLASSES.  EAV_HEAD_ALGO overrides.
+        self.head_algo = os.environ.get("EAV_HEAD_ALGO", "auto")
         # split mode: weight-gradient GEMMs on a side stream (see _wgrad_sp).  "auto" (default): two streams from 8192 token
         # rows per step on, one stream below - at the per-rank batches of a data-parallel group (ViT B = 16: 3152 rows) the
         # ~100 events / waits of the two-stream schedule cost more host time than the overlap returns (20.1 -> 13.1 ms;
@@ -283,8 +297,11 @@ class Encoder(KernelModule):
         self.grad_ready_hook = None
         if cfg.hidden % cfg.heads or (cfg.hidden // cfg.heads) % 4 or cfg.hidden % 4 or cfg.hidden > 1024:
             raise NotImplementedError("hidden size must be <= 1024, a multiple of 4, head_dim a multiple of 4")
-        if cfg.ntok > 2048 or cfg.num_labels > 16:
-            raise NotImplementedError("at most 2048 tokens and 16 classes")
+        if cfg.ntok > 2048:
+            raise NotImplementedError("at most 2048 tokens")
+        if not 1 <= cfg.num_labels <= HEAD_MAX_CLASSES:
+            raise NotImplementedError(f"the classification head takes 1 .. HEAD_MAX_CLASSES = {HEAD_MAX_CLASSES} classes, "
+                                      f"not {cfg.num_labels}")
 
     # ------------------------------------------------------------------ loading
     @classmethod
@@ -311,9 +328,14 @@ class Encoder(KernelModule):
         Transformer_Audio.py:24 / `classifier = nn.Linear(...)`, Transformer_Vision.py:30)."""
         head = self.classifier.dense if self.cfg.kind == "ast" else self.classifier
         dev = head.weight.device
-        head.weight = nn.Parameter(torch.as_tensor(weight, dtype=torch.float32).clone().to(dev))
+        weight = torch.as_tensor(weight, dtype=torch.float32)
+        if not 1 <= weight.shape[0] <= HEAD_MAX_CLASSES:      # refused before anything is replaced
+            raise NotImplementedError(f"the classification head takes 1 .. HEAD_MAX_CLASSES = {HEAD_MAX_CLASSES} classes, "
+                                      f"not {weight.shape[0]}")
+        head.weight = nn.Parameter(weight.clone().to(dev))
         head.bias = nn.Parameter(torch.as_tensor(bias, dtype=torch.float32).clone().to(dev))
         self.cfg.num_labels = head.weight.shape[0]
+        self.cfg.id2label = None            # the checkpoint's names belonged to the head that just left
         self._flat = None
         self._ws = None
         self._wss, self._hws = {}, {}
@@ -518,6 +540,7 @@ class Encoder(KernelModule):
         ws.rows, ws.seqr, ws.stf = f(R, D), f(R, D), f(2, R)
         ws.pooled, ws.hl, ws.sth = f(B, D), f(B, D), f(2, B)
         ws.logits = f(B, c.num_labels)
+        ws.head_ws = self._head_scratch(B, f)
         if full_backward:
             ws.dh, ws.dy, ws.dao = f(M, D), f(M, D), f(M, D)
             ws.dact, ws.dqkv = f(M, FF), f(M, 3 * D)
@@ -756,6 +779,37 @@ class Encoder(KernelModule):
 
     # ------------------------------------------------------------------ classification head (shared by the full path
     # and by Encoder.head on cached features: same kernels, same arguments, hence bit-equal logits and gradients)
+    def _head_wide(self):
+        """Whether the classification Linear runs on eav_dense_wide_* (head_algo)."""
+        algo, n = self.head_algo, self.cfg.num_labels
+        if algo not in ("auto", "wide", "narrow"):
+            raise ValueError(f"head_algo {algo!r}: expected 'auto', 'wide' or 'narrow'")
+        if algo == "narrow" and n > HEAD_NARROW_CLASSES:
+            raise NotImplementedError(f"head_algo 'narrow' takes at most {HEAD_NARROW_CLASSES} classes, the head has {n}")
+        return algo == "wide" or (algo == "auto" and n > HEAD_NARROW_CLASSES)
+
+    def _head_scratch(self, B, f):
+        """The wide backward's class slices of d loss / d feat (None where the head kernels need no scratch)."""
+        n = _lib.plain("eav_dense_wide_bwd_ws_floats", B, self.cfg.hidden, self.cfg.num_labels) if self._head_wide() else 0
+        return f(n) if n else None
+
+    def _dense_forward(self, feat, weight, bias, hw, B):
+        c, P = self.cfg, _lib.ptr
+        if self._head_wide():
+            self._call("eav_dense_wide_fwd", P(feat), weight, bias, P(hw.logits), B, c.hidden, c.num_labels, self._st)
+        else:
+            self._call("eav_dense_softmax_fwd", P(feat), weight, bias, P(hw.logits), None, B, c.hidden, c.num_labels,
+                       self._st)
+
+    def _dense_backward(self, dlogits, feat, weight, dweight, dbias, dfeat, hw, B):
+        c, P = self.cfg, _lib.ptr
+        if self._head_wide():
+            self._call("eav_dense_wide_bwd", P(dlogits), P(feat), weight, dweight, dbias, P(dfeat), P(hw.head_ws), B,
+                       c.hidden, c.num_labels, self._st)
+        else:
+            self._call("eav_dense_softmax_bwd", P(dlogits), None, P(feat), weight, dweight, dbias, P(dfeat), B, c.hidden,
+                       c.num_labels, self._st)
+
     def _head_forward(self, feat, hw, B):
         """feat [B, D] = the classifier's input (AST: mean of the cls / distillation rows after the final LayerNorm,
         HF modeling_audio_spectrogram_transformer.py ASTMLPHead; ViT: the cls row after the final LayerNorm)."""
@@ -766,11 +820,9 @@ class Encoder(KernelModule):
             sh = P(hw.sth)
             L("eav_layernorm_fwd", P(feat), w("classifier.layernorm.weight"), w("classifier.layernorm.bias"),
               P(hw.hl), sh, sh + 4 * B, B, D, c.eps, st)
-            L("eav_dense_softmax_fwd", P(hw.hl), w("classifier.dense.weight"), w("classifier.dense.bias"),
-              P(hw.logits), None, B, D, c.num_labels, st)
+            self._dense_forward(hw.hl, w("classifier.dense.weight"), w("classifier.dense.bias"), hw, B)
         else:
-            L("eav_dense_softmax_fwd", P(feat), w("classifier.weight"), w("classifier.bias"), P(hw.logits), None,
-              B, D, c.num_labels, st)
+            self._dense_forward(feat, w("classifier.weight"), w("classifier.bias"), hw, B)
 
     def _head_backward(self, dlogits, feat, hw, B, need_dfeat):
         """Head gradients into the flat gradient buffer; d loss / d feat into hw.dpooled (AST) / hw.dseqr (ViT)."""
@@ -780,25 +832,27 @@ class Encoder(KernelModule):
         gp = lambda k: gflat.data_ptr() + 4 * offs[k][0]  # noqa: E731
         w = lambda k: P(self._pmap[k])  # noqa: E731
         if c.kind == "ast":
-            L("eav_dense_softmax_bwd", P(dlogits), None, P(hw.hl), w("classifier.dense.weight"),
-              gp("classifier.dense.weight"), gp("classifier.dense.bias"), P(hw.dhl), B, D, c.num_labels, st)
+            self._dense_backward(dlogits, hw.hl, w("classifier.dense.weight"), gp("classifier.dense.weight"),
+                                 gp("classifier.dense.bias"), hw.dhl, hw, B)
             sh = P(hw.sth)
             L("eav_layernorm_bwd", P(hw.dhl), P(feat), w("classifier.layernorm.weight"), sh, sh + 4 * B,
               P(hw.dpooled), 0, P(hw.part_lnr), B, D, st)
             self._reduce_gamma_beta(hw.part_lnr, _lib.plain("eav_layernorm_bwd_nparts", B),
                                     gp("classifier.layernorm.weight"), gp("classifier.layernorm.bias"))
         else:
-            L("eav_dense_softmax_bwd", P(dlogits), None, P(feat), w("classifier.weight"), gp("classifier.weight"),
-              gp("classifier.bias"), P(hw.dseqr), B, D, c.num_labels, st)
+            self._dense_backward(dlogits, feat, w("classifier.weight"), gp("classifier.weight"), gp("classifier.bias"),
+                                 hw.dseqr, hw, B)
 
     def _head_ws(self, B, dev):
         hw = self._hws.get(B)
-        if hw is None or hw.feat.device != dev or hw.logits.shape[1] != self.cfg.num_labels:
+        if hw is None or hw.feat.device != dev or hw.logits.shape[1] != self.cfg.num_labels \
+                or hw.wide != self._head_wide():
             c, D = self.cfg, self.cfg.hidden
             f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
             hw = self._hws[B] = SimpleNamespace(
                 feat=f(B, D), hl=f(B, D), sth=f(2, B), logits=f(B, c.num_labels), dhl=f(B, D), dpooled=f(B, D),
-                dseqr=f(B, D), part_lnr=f(_lib.plain("eav_layernorm_bwd_nparts", B * c.nextra), 2 * D), token=-1)
+                dseqr=f(B, D), part_lnr=f(_lib.plain("eav_layernorm_bwd_nparts", B * c.nextra), 2 * D), token=-1,
+                head_ws=self._head_scratch(B, f), wide=self._head_wide())
         return hw
 
     def last_features(self):
@@ -822,7 +876,7 @@ class Encoder(KernelModule):
         evaluation batch): the 5000 % 128 = 8 frames at the end of every vision epoch must not free and re-zero the 19 GB
         of the B = 128 one.  One allocated for a full backward also serves the no_grad forwards of its batch size; one
         without the backward's buffers is replaced when a full backward comes."""
-        key = (B, str(dev), self._fused_attention(), self.precision == "split")
+        key = (B, str(dev), self._fused_attention(), self.precision == "split", self._head_wide())
         old = self._wss.get(key)
         if old is not None and full and not old.full:
             del self._wss[key]

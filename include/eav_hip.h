@@ -245,6 +245,22 @@ int eav_dense_softmax_bwd(const float* dout, const float* probs, const float* in
  * label+1 for label >= 0, the label itself if negative) - torch raises at this point, the Python wrapper does too. */
 int eav_ce_fwd_bwd(const float* in, const int64_t* y, float* loss, float* din, int* ncorrect, int* bad_label, int B,
                    int NC, void* stream);
+/* The wide head (csrc/head_wide.hip): the same Linear and loss for more than 16 classes, exact fp32, no atomics - the
+ * summation order is fixed by the shape, two runs give the same bits.  NF a multiple of 4 up to 1024, 1 <= NC <=
+ * EAV_HEAD_MAX_CLASSES.  logits = in . w^T + bias. */
+#define EAV_HEAD_MAX_CLASSES 32768
+int eav_dense_wide_fwd(const float* in, const float* w, const float* bias, float* logits, int B, int NF, int NC,
+                       void* stream);
+/* dw = dlogits^T . in, dbias = column sums of dlogits, din = dlogits . w (din may be NULL: not computed).  ws: device
+ * scratch of eav_dense_wide_bwd_ws_floats(B, NF, NC) floats (the class slices of din; may be NULL when that is 0). */
+int64_t eav_dense_wide_bwd_ws_floats(int B, int NF, int NC);
+int eav_dense_wide_bwd(const float* dlogits, const float* in, const float* w, float* dw, float* dbias, float* din,
+                       float* ws, int B, int NF, int NC, void* stream);
+/* eav_ce_fwd_bwd's contract (ignore_index -100, bad_label encoding, *ncorrect += hits with the first maximum winning a
+ * tie, NaN when every row is ignored) with one wave per row; ws: eav_ce_wide_ws_floats(B) floats of device scratch. */
+int64_t eav_ce_wide_ws_floats(int B);
+int eav_ce_wide_fwd_bwd(const float* in, const int64_t* y, float* loss, float* din, int* ncorrect, int* bad_label,
+                        float* ws, int B, int NC, void* stream);
 /* v[i] *= *scalar (device scalar): the upstream gradient applied to the stored d loss / d scores. */
 int eav_scale_by_scalar(float* v, const float* scalar, int64_t n, void* stream);
 /* torch.optim.Adam (decoupled=0) / AdamW (decoupled=1) update of one flat tensor; step >= 1.

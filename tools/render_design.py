@@ -182,6 +182,21 @@ if os.path.exists(P("eeg_resample_bench.json")):
     v["RP_FRAC"] = f"{k['frac_of_copy_rate']:.2f}"
     v["RP_SCIPY"], v["RP_X"] = f"{rp['scipy']['ms']:.0f}", f"{rp['scipy_over_kernel']:.0f}"
 
+# the wide classification head (tools/head_wide_bench.py)
+if os.path.exists(P("head_wide_bench.json")):
+    rows = ["| B, hidden, classes | dense products: wide / composition (classes) | ratio | loss: wide / old kernel | "
+            "whole head step: wide / composition | w read + dw written over the step | share of a 2-layer unfrozen step |",
+            "|---|---|---|---|---|---|---|"]
+    for h in json.load(open(P("head_wide_bench.json")))["shapes"]:
+        dn, ls = h["dense_only"], h["loss_only"]
+        rows.append(f"| {h['B']}, {h['hidden']}, {h['classes']} | {dn['wide']['ms'] * 1e3:.1f} / "
+                    f"{dn['composition']['ms'] * 1e3:.1f} µs ({h['composition_classes']}) | {dn['wide_over_composition']:.2f} | "
+                    f"{ls['wide']['ms'] * 1e3:.1f} / {ls['composition']['ms'] * 1e3:.1f} µs | "
+                    f"{h['wide']['ms'] * 1e3:.1f} / {h['composition']['ms'] * 1e3:.1f} µs | "
+                    f"{h['w_read_plus_dw_written_bytes'] / 1e6:.1f} MB, {h['gbps']:.0f} GB/s | "
+                    f"{100 * h['head_share_of_step']:.1f} % of {h['unfrozen_step']['ms']:.2f} ms ({h['unfrozen_step']['model']}) |")
+    v["HEAD_WIDE_TABLE"] = "\n".join(rows)
+
 src = open(os.path.join(ROOT, "docs", "DESIGN.md.in")).read()
 missing = sorted(set(re.findall(r"@([A-Z0-9_]+)@", src)) - set(v))
 if missing:
