@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import _lib
 from .optim import CrossEntropyLoss, FusedAdam
-from .runtime import DeviceLoader, GraphStep, KernelFn, KernelModule, eager_step
+from .runtime import DeviceLoader, KernelFn, KernelModule, train_step
 
 _PARAM_ORDER = ["features.0.weight", "features.0.bias", "features.2.weight", "features.2.bias", "features.6.weight",
                 "features.6.bias", "features.8.weight", "features.8.bias", "classifier.weight", "classifier.bias"]
@@ -110,22 +110,21 @@ class AudioModel(KernelModule):
         ws = self._workspace((B, T, str(x.device)), lambda: _Workspace(self, B, T, x.device), keep_unpinned=3)
         w1, b1, w2, b2, w3, b3, w4, b4, wc, bc = [P(p) for p in self._params()]
         d1, d2 = self._drop()
-        masks = self._dropout_masks if self.training else None
-        if masks is not None:
+
+        def check(masks):
             if tuple(masks[0].shape) != (B, 128, T) or tuple(masks[1].shape) != (B, 128, POOLED) \
                     or masks[0].dtype != torch.uint8 or masks[1].dtype != torch.uint8 \
                     or masks[0].device != x.device or masks[1].device != x.device:
                 raise _lib.EavError(f"set_dropout_masks: expected uint8 device masks [{B},128,{T}] and "
                                     f"[{B},128,{POOLED}]")
-            masks = (masks[0].contiguous(), masks[1].contiguous())
+            return masks[0].contiguous(), masks[1].contiguous()
+
+        cnt, mk = self._dropout(x.device, d1 > 0.0 or d2 > 0.0, check)
         self._token += 1
         seed1, seed2 = self.dropout_seed, self.dropout_seed + 1
-        cnt = None
-        if (d1 > 0.0 or d2 > 0.0) and masks is None:   # device-resident dropout counter: graph replays draw fresh masks
-            cnt = P(self._counter(x.device))
+        if cnt is not None:                 # device-resident dropout counter: graph replays draw fresh masks
             L("eav_counter_inc", cnt, st)
-        m1 = P(masks[0]) if masks is not None else None
-        m2 = P(masks[1]) if masks is not None else None
+        m1, m2 = mk(0), mk(1)
         L("eav_audio_conv5_fwd", P(x), w1, b1, P(ws.a1), None, B, 1, 256, T, T, 0, 0.0, 0, None, None, st)
         L("eav_audio_conv5_fwd", P(ws.a1), w2, b2, P(ws.p2), P(ws.idx2), B, 256, 128, T, 8 * POOLED, 1, d1, seed1,
           m1, cnt, st)
@@ -134,19 +133,16 @@ class AudioModel(KernelModule):
         L("eav_audio_conv5_fwd", P(ws.a3), w4, b4, P(ws.a4), None, B, 128, 128, POOLED, POOLED, 0, d2, seed2, m2, cnt,
           st)
         L("eav_dense_softmax_fwd", P(ws.a4), wc, bc, P(ws.logits), None, B, 128 * POOLED, self.num_classes, st)
-        self._saved = (self._token, x, d1, d2, masks, ws)
+        self._saved = (self._token, x, d1, d2, mk, ws)      # (mk keeps explicit masks alive)
         return self._token
 
     def _launch_backward(self, dlogits, token):
         self._check_token(token)
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
-        _, x, d1, d2, masks, ws = self._saved
+        _, x, d1, d2, _, ws = self._saved
         B, T = x.shape
-        flat, gflat, offs = self._flat
-        g = {k: gflat[offs[k][0]:offs[k][0] + offs[k][1]] for k in _PARAM_ORDER}
-        named = dict(self.named_parameters())
-        w2, w3, w4, wc = (P(named[k]) for k in ("features.2.weight", "features.6.weight", "features.8.weight",
-                                                "classifier.weight"))
+        g = self._grad_views()
+        _, _, w2, _, w3, _, w4, _, wc, _ = [P(p) for p in self._params()]
         s1, s2 = 1.0 / (1.0 - d1), 1.0 / (1.0 - d2)
         Pn = POOLED
 
@@ -171,7 +167,7 @@ class AudioModel(KernelModule):
           st)
         wgrad(2, ws.dz2, None, 1.0, ws.a1, 256, 128, T, 8 * Pn, "features.2.weight")
         wgrad(1, ws.da1, None, 1.0, x, 1, 256, T, T, "features.0.weight")
-        return [g[k].view(named[k].shape) if named[k].requires_grad else None for k in _PARAM_ORDER]
+        return self._grads_out(g)
 
 
 def create_dataloader(x, y, batch_size=64, shuffle=True):
@@ -235,7 +231,7 @@ def train_model(model, train_loader, val_loader, epochs=100, lr=1e-3, save_dir="
     optimizer = FusedAdam(model.parameters(), lr=lr, capturable=True)
     activation_saver = ActivationSaver(model, val_loader, save_dir)
     grad_sync = None
-    graph = None
+    graphs = {}
 
     for epoch in range(epochs):
         model.train()
@@ -245,14 +241,10 @@ def train_model(model, train_loader, val_loader, epochs=100, lr=1e-3, save_dir="
         total = 0
 
         for k, idx in enumerate(batches):
-            if len(idx) == train_loader.batch_size:
-                if graph is None:
-                    graph = GraphStep(model, optimizer, criterion, train_loader.x, train_loader.y, len(idx), grad_sync)
-                out, loss = graph.run(idx)
+            out, loss, y = train_step(graphs, model, optimizer, criterion, train_loader, idx, True, grad_sync,
+                                      eager_input=lambda x: x.permute(0, 2, 1))
+            if y is None:       # a replayed step: its labels were gathered inside the graph
                 y = train_loader.gather_labels(idx)
-            else:
-                x, y = train_loader.gather(idx)
-                out, loss = eager_step(model, optimizer, criterion, x.permute(0, 2, 1), y, grad_sync)
             losses[k].copy_(loss)
             correct += (out.argmax(dim=1) == y).sum()
             total += len(idx)

@@ -278,11 +278,7 @@ class VideoModel(KernelModule):
         npart = _lib.plain("eav_video_bn_nparts", u.M)
         if training:
             L("eav_video_bn_stats", P(c), P(ws.stat), u.M, C, st)
-        b = u.bn
-        base = bn.data_ptr()
-        L("eav_bn_finalize", P(ws.stat) if training else None, npart if training else 0, C, float(u.M),
-          P(b.weight), P(b.bias), P(b.running_mean), P(b.running_var), int(training), float(b.momentum), float(b.eps),
-          base, base + 4 * C, base + 8 * C, base + 12 * C, st)
+        self._bn_finalize(u.bn, ws.stat if training else None, npart if training else 0, u.M, bn, training)
 
     def _bn_apply(self, u, dst, relu=1, res=None, ures=None):
         L, P, st, ws = _lib.call, _lib.ptr, _lib.stream_ptr(), self._ws
@@ -433,10 +429,7 @@ class VideoModel(KernelModule):
             L("eav_video_maxpool_bwd", P(cur), P(ws.pidx), P(ws.Sda), B, stem.OH, stem.OW, 64, ws.PH, ws.PW, 3, 2, 1, st)
             self._bn_bwd(stem, ws.Sda, ws.a[id(stem)], ws.Sg, ws.Sdc, tr)
             self._conv_bwd(stem, ws.Sdc, x, None, nchw=1)
-        out = []
-        for p in self.parameters():
-            out.append(G(p).view(p.shape) if p.requires_grad else None)
-        return out
+        return self._grads_out(self._grad_views())
 
 
 # ---------------------------------------------------------------------------------------------- trainer

@@ -24,11 +24,11 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, eegnet_canon
 from .optim import CrossEntropyLoss, FusedAdam
 # re-exported: bench.py, tools/ and the tests import GraphStep, gather_batch and DeviceLoader from this module
 from .runtime import (DeviceLoader, GraphStep, KernelFn, KernelModule, cached_workspace, eager_step,  # noqa: F401
-                      gather_batch)
+                      gather_batch, train_step)
 
 _PARAM_ORDER = [
     "firstConv.weight", "firstBN.weight", "firstBN.bias",
@@ -73,31 +73,18 @@ class _Workspace:
         self.part_cw = f(self.np_cw, 64 * 1024)
 
 
-class _GenericWorkspace:
-    """Device buffers of the run-time-parametrised path (EEGNet_tor._generic)."""
+class _GenericWorkspace(eegnet_canon.Workspace):
+    """Device buffers of the run-time-parametrised path (EEGNet_tor._generic): eegnet_canon.Workspace + block 2 (the dense
+    "separableConv" output u3, pooled p3)."""
 
     def __init__(self, m, B, dev):
+        super().__init__(m, B, dev)
         f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
-        C, S, F1, C2, F2, K = m.Chans, m.Samples, m.F1, m.F1 * m.D, m.F2, m.kernLength
-        T2, T3 = S // 4, S // 4 // 8
-        self.T2, self.T3, self.NF = T2, T3, F2 * T3
-        self.y1, self.g1 = f(B, F1, C, S), f(B, F1, C, S)
-        self.z, self.dz = f(B, C2, S), f(B, C2, S)
-        self.p2, self.dp2 = f(B, C2, T2), f(B, C2, T2)
+        C2, F2, T2 = m.F1 * m.D, m.F2, self.T2
         self.u3, self.du3 = f(B, F2, T2), f(B, F2, T2)
-        self.p3, self.dp3 = f(B, F2 * T3), f(B, F2 * T3)
-        self.bn1, self.bn2, self.bn3 = f(6 * F1), f(6 * C2), f(6 * F2)
-        self.np_t = _lib.plain("eav_tconv_fwd_nparts", B, C, S, F1, K)
-        self.part_t = f(self.np_t, 2 * F1)
-        self.np_s = _lib.plain("eav_spatial_nparts", B, S)
-        self.part_s = f(self.np_s, 2 * C2)
+        self.p3, self.dp3 = f(B, self.NF), f(B, self.NF)
         self.np_c = _lib.plain("eav_dconv_fwd_nparts", B, T2)
         self.part_c = f(self.np_c, 2 * F2)
-        self.part_pb = f(B, 2 * max(C2, F2))
-        self.part_sst = f(self.np_s, 2 * F1)
-        self.part_sw = f(self.np_s, C2 * C)
-        self.np_tw = _lib.plain("eav_tconv_wgrad_nparts", B, C, S, F1, K)
-        self.part_tw = f(self.np_tw, F1 * K)
         self.part_cw = f(B, F2 * C2 * 16)
 
 
@@ -171,7 +158,6 @@ class EEGNet_tor(KernelModule):
         self.dropout_seed = 0x0EA5EED          # base seed of the counter-based dropout generator
         # (set_dropout_masks, tests: (mask1 uint8 [B,64,S/4], mask2 uint8 [B,64,S/32]))
         self.apply_max_norm = True
-        self.kernel_events = None              # bench: {kernel name: [(start_event, end_event), ...]}
         # (the round-2 "split" mode - FIR / separableConv products on the fp16 matrix cores with two-piece operands - was
         # retired in round 5: with the FFT FIR and the frequency-domain separableConv it was the slower path)
         self.fir_precision = "fp32"
@@ -246,19 +232,6 @@ class EEGNet_tor(KernelModule):
         return _EEGNetFn.apply(IndexedBatch(data, idx), self, *self._params())
 
     # ------------------------------------------------------------------ kernels
-    def _call(self, name, *args):
-        """_lib.call, optionally bracketed by HIP events on the launch stream (bench.py's live
-        per-kernel timing of the dominant kernels)."""
-        ev = self.kernel_events
-        if ev is not None and name in ev:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            _lib.call(name, *args)
-            b.record()
-            ev[name].append((a, b))
-        else:
-            _lib.call(name, *args)
-
     def _forward_output(self):
         return self._saved[-1].detach()          # see _EEGNetFn
 
@@ -284,34 +257,29 @@ class EEGNet_tor(KernelModule):
             _lib.call("eav_gather_i64", ys.data_ptr(), idx.data_ptr(), targets.data_ptr(), batch, _lib.stream_ptr())
         return scores, targets
 
-    def _launch_forward(self, x):
-        if self._generic:
-            return self._launch_forward_generic(x)
-        L, P, st = self._call, _lib.ptr, _lib.stream_ptr()
-        B, C, S, K, nb = x.shape[0], self.Chans, self.Samples, self.kernLength, self.nb_classes
-        ws = self._workspace((B, C, S, str(x.device)), lambda: _Workspace(B, C, S, K, nb, x.device))
-        training = bool(self.training)
-        w1, g1w, g1b, w2, g2w, g2b, w3, g3w, g3b, wd, bd = [P(p) for p in self._params()]
-        bn1, bn2, bn3 = self.firstBN, self.depthwiseBN, self.separableBN
+    def _dropout_args(self, dev, training):
+        """(counter pointer, block-1 and block-2 dropout arguments (rate, seed, mask pointer, counter pointer), mk)."""
         drop = self.dropoutRate if training else 0.0
         if self.spatial_dropout:
             drop = -drop
-        masks = self._dropout_masks if training else None
-        self._token += 1
         # dropout stream: effective seed = base + 2 * (device-resident count of training forwards) - no host
         # argument changes from step to step, so the whole step can be replayed from a hipGraph
-        seed1, seed2 = self.dropout_seed, self.dropout_seed + 1
-        cnt = None
-        if drop != 0.0 and masks is None:
-            cnt = P(self._counter(x.device))
-        m1 = P(masks[0]) if masks is not None else None
-        m2 = P(masks[1]) if masks is not None else None
+        cnt, mk = self._dropout(dev, drop != 0.0)
+        return cnt, (drop, self.dropout_seed, mk(0), cnt), (drop, self.dropout_seed + 1, mk(1), cnt), mk
 
-        def bnfin(part, nparts, nch, count, gw, gb, bn, buf):
-            b0 = P(buf)
-            L("eav_bn_finalize", P(part), nparts, nch, float(count), gw, gb, P(bn.running_mean), P(bn.running_var),
-              int(training), float(bn.momentum), float(bn.eps), b0, b0 + 4 * nch, b0 + 8 * nch, b0 + 12 * nch, st)
-
+    def _launch_forward(self, x):
+        if self._generic:
+            return self._launch_forward_generic(x)
+        L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
+        B, C, S, K, nb = x.shape[0], self.Chans, self.Samples, self.kernLength, self.nb_classes
+        ws = self._workspace((B, C, S, str(x.device)), lambda: _Workspace(B, C, S, K, nb, x.device))
+        training = bool(self.training)
+        w1, _, _, w2, _, _, w3, _, _, wd, bd = [P(p) for p in self._params()]
+        bn1, bn2, bn3 = self.firstBN, self.depthwiseBN, self.separableBN
+        bnfin = self._bn_finalize
+        self._token += 1
+        cnt, drop1, drop2, mk = self._dropout_args(x.device, training)
+        drop, m1 = drop1[0], drop1[2]
         if self.fir_precision != "fp32":
             raise ValueError(f"fir_precision {self.fir_precision!r}: only 'fp32' exists (the split mode was retired)")
         counters = [cnt] + ([P(bn.num_batches_tracked) for bn in (bn1, bn2, bn3)] if training else [None] * 3)
@@ -332,8 +300,8 @@ class EEGNet_tor(KernelModule):
         if infer:
             # validate(): x -> block-1 output in ONE kernel (FIR -> firstBN -> ELU -> depthwiseConv -> depthwiseBN -> ELU ->
             # AvgPool4; BatchNorms on running statistics): y1 (614 MB at [64,1,30,10000]) and z are never written
-            bnfin(ws.part_fir, ws.np_fir, 8, B * C * S, g1w, g1b, bn1, ws.bn1)          # eval mode: running statistics only
-            bnfin(ws.part_dw, B * ws.nchunk, 64, B * S, g2w, g2b, bn2, ws.bn2)
+            bnfin(bn1, ws.part_fir, ws.np_fir, B * C * S, ws.bn1, training)       # eval mode: running statistics only
+            bnfin(bn2, ws.part_dw, B * ws.nchunk, B * S, ws.bn2, training)
             if isinstance(x, IndexedBatch):
                 L("eav_eegnet_block1_infer", P(x.data), P(x.idx), w1, P(ws.bn1), w2, P(ws.bn2), P(ws.p2), B, C, S, K, st)
             else:
@@ -351,18 +319,18 @@ class EEGNet_tor(KernelModule):
             else:
                 L("eav_eegnet_fir_fwd", P(x), w1, P(ws.y1), P(ws.part_fir), B, C, S, K, st)
         if not infer:
-            bnfin(ws.part_fir, np_fir, 8, B * C * S, g1w, g1b, bn1, ws.bn1)
+            bnfin(bn1, ws.part_fir, np_fir, B * C * S, ws.bn1, training)
             if not training and drop == 0.0 and m1 is None and S % 4 == 0:
                 # eval-mode step (what 349 of the reference's 350 epochs run, Q4): depthwiseBN's scale / shift come from the
                 # running statistics, i.e. they are known BEFORE the depthwise pass - which then leaves the pooled block-1
                 # output too (z is still written: the backward forms dz from it); one launch and one pass over z less
-                bnfin(ws.part_dw, B * ws.nchunk, 64, B * S, g2w, g2b, bn2, ws.bn2)
+                bnfin(bn2, ws.part_dw, B * ws.nchunk, B * S, ws.bn2, training)
                 L("eav_eegnet_dw_fwd_pool_eval", P(ws.y1), P(ws.bn1), w2, P(ws.z), P(ws.part_dw), P(ws.bn2), P(ws.p2), B, C, S,
                   st)
             else:
                 L("eav_eegnet_dw_fwd", P(ws.y1), P(ws.bn1), w2, P(ws.z), P(ws.part_dw), B, C, S, st)
-                bnfin(ws.part_dw, B * ws.nchunk, 64, B * S, g2w, g2b, bn2, ws.bn2)
-                L("eav_bn_elu_pool_fwd", P(ws.z), P(ws.bn2), P(ws.p2), B, 64, S, 4, drop, seed1, m1, cnt, st)
+                bnfin(bn2, ws.part_dw, B * ws.nchunk, B * S, ws.bn2, training)
+                L("eav_bn_elu_pool_fwd", P(ws.z), P(ws.bn2), P(ws.p2), B, 64, S, 4, *drop1, st)
         np_c3 = ws.np_c3
         if self._use_conv_fft(B):
             if ws.c64_ws is None:
@@ -372,13 +340,13 @@ class EEGNet_tor(KernelModule):
             L("eav_conv64_fft_fwd", P(ws.p2), w3, P(ws.u3), P(ws.part_c3), P(ws.c64_ws), B, ws.T2, 0, st)
         else:
             L("eav_conv64_fwd", P(ws.p2), P(ws.wTf), P(ws.u3), P(ws.part_c3), B, ws.T2, 7, st)
-        bnfin(ws.part_c3, np_c3, 64, B * ws.T2, g3w, g3b, bn3, ws.bn3)
-        L("eav_bn_elu_pool_fwd", P(ws.u3), P(ws.bn3), P(ws.p3), B, 64, ws.T2, 8, drop, seed2, m2, cnt, st)
+        bnfin(bn3, ws.part_c3, np_c3, B * ws.T2, ws.bn3, training)
+        L("eav_bn_elu_pool_fwd", P(ws.u3), P(ws.bn3), P(ws.p3), B, 64, ws.T2, 8, *drop2, st)
         probs = torch.empty(B, nb, dtype=torch.float32, device=x.device)   # fresh per forward: returned, kept for backward
         L("eav_dense_softmax_fwd", P(ws.p3), wd, bd, None, P(probs), B, ws.NF, nb, st)
         if self.apply_max_norm:  # the forward hooks of the reference (:33-34, :47-48), intended meaning: one launch
             L("eav_renorm_rows2", w2, 64, C, wd, nb, ws.NF, self.norm_rate, st)
-        self._saved = (self._token, x, training, drop, seed1, seed2, masks, cnt, ws, probs)
+        self._saved = (self._token, x, training, drop1, drop2, mk, ws, probs)      # (mk keeps explicit masks alive)
         return self._token
 
     # ------------------------------------------------------------------ generic widths (csrc/eegnet_canon.hip)
@@ -387,105 +355,58 @@ class EEGNet_tor(KernelModule):
         run-time-parametrised kernels: eav_tconv_* (firstConv), eav_spatial_* with the ELU flag (firstBN -> ELU ->
         depthwiseConv), eav_dconv_* (the dense "separableConv"), the shared BN -> ELU -> pool -> dropout and classifier
         kernels.  Same quirks as the specialised path: max-norm after the forward (Q1/Q2), softmax output (Q3)."""
-        L, P, st = self._call, _lib.ptr, _lib.stream_ptr()
-        B, C, S, K, nb = x.shape[0], self.Chans, self.Samples, self.kernLength, self.nb_classes
-        F1, D, F2 = self.F1, self.D, self.F2
-        C2 = F1 * D
-        ws = self._workspace(("generic", B, C, S, str(x.device)), lambda: _GenericWorkspace(self, B, x.device))
+        L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
+        B, C, nb, C2, F2 = x.shape[0], self.Chans, self.nb_classes, self.F1 * self.D, self.F2
+        ws = self._workspace(("generic", B, C, self.Samples, str(x.device)), lambda: _GenericWorkspace(self, B, x.device))
         training = bool(self.training)
-        w1, g1w, g1b, w2, g2w, g2b, w3, g3w, g3b, wd, bd = [P(p) for p in self._params()]
+        w1, _, _, w2, _, _, w3, _, _, wd, bd = self._params()
         bn1, bn2, bn3 = self.firstBN, self.depthwiseBN, self.separableBN
-        drop = self.dropoutRate if training else 0.0
-        if self.spatial_dropout:
-            drop = -drop
-        masks = self._dropout_masks if training else None
         self._token += 1
-        seed1, seed2 = self.dropout_seed, self.dropout_seed + 1
-        cnt = None
-        if drop != 0.0 and masks is None:
-            cnt = P(self._counter(x.device))
+        cnt, drop1, drop2, mk = self._dropout_args(x.device, training)
         if cnt is not None or training:
             L("eav_counter_inc4", cnt, *([P(bn.num_batches_tracked) for bn in (bn1, bn2, bn3)] if training else [None] * 3),
               st)
-        m1 = P(masks[0]) if masks is not None else None
-        m2 = P(masks[1]) if masks is not None else None
-
-        def bnfin(part, nparts, nch, count, gw, gb, bn, buf):
-            b0 = P(buf)
-            L("eav_bn_finalize", P(part), nparts, nch, float(count), gw, gb, P(bn.running_mean), P(bn.running_var),
-              int(training), float(bn.momentum), float(bn.eps), b0, b0 + 4 * nch, b0 + 8 * nch, b0 + 12 * nch, st)
-
-        L("eav_tconv_fwd", P(x), w1, P(ws.y1), P(ws.part_t), B, C, S, F1, K, st)                       # :51
-        bnfin(ws.part_t, ws.np_t, F1, B * C * S, g1w, g1b, bn1, ws.bn1)                                 # :52
-        L("eav_spatial_fwd", P(ws.y1), P(ws.bn1), w2, P(ws.z), P(ws.part_s), B, C, S, F1, D, 1, st)     # :53-54
-        bnfin(ws.part_s, ws.np_s, C2, B * S, g2w, g2b, bn2, ws.bn2)                                     # :55
-        L("eav_bn_elu_pool_fwd", P(ws.z), P(ws.bn2), P(ws.p2), B, C2, S, 4, drop, seed1, m1, cnt, st)   # :56-58
-        L("eav_dconv_fwd", P(ws.p2), w3, P(ws.u3), P(ws.part_c), B, C2, F2, ws.T2, 16, 0, st)           # :59
-        bnfin(ws.part_c, ws.np_c, F2, B * ws.T2, g3w, g3b, bn3, ws.bn3)                                 # :60
-        L("eav_bn_elu_pool_fwd", P(ws.u3), P(ws.bn3), P(ws.p3), B, F2, ws.T2, 8, drop, seed2, m2, cnt, st)   # :61-63
+        eegnet_canon.block1_forward(self, ws, x, w1, bn1, w2, bn2, 1, training, drop1)                 # :51-58
+        L("eav_dconv_fwd", P(ws.a2), P(w3), P(ws.u3), P(ws.part_c), B, C2, F2, ws.T2, 16, 0, st)        # :59
+        self._bn_finalize(bn3, ws.part_c, ws.np_c, B * ws.T2, ws.bn3, training)                         # :60
+        L("eav_bn_elu_pool_fwd", P(ws.u3), P(ws.bn3), P(ws.p3), B, F2, ws.T2, 8, *drop2, st)            # :61-63
         probs = torch.empty(B, nb, dtype=torch.float32, device=x.device)
-        L("eav_dense_softmax_fwd", P(ws.p3), wd, bd, None, P(probs), B, ws.NF, nb, st)                  # :64-66
+        L("eav_dense_softmax_fwd", P(ws.p3), P(wd), P(bd), None, P(probs), B, ws.NF, nb, st)            # :64-66
         if self.apply_max_norm:
-            L("eav_renorm_rows", w2, C2, C, self.norm_rate, st)
-            L("eav_renorm_rows", wd, nb, ws.NF, self.norm_rate, st)
-        self._saved = (self._token, x, training, drop, seed1, seed2, masks, cnt, False, ws, probs)
+            L("eav_renorm_rows", P(w2), C2, C, self.norm_rate, st)
+            L("eav_renorm_rows", P(wd), nb, ws.NF, self.norm_rate, st)
+        self._saved = (self._token, x, training, drop1, drop2, mk, ws, probs)
         return self._token
 
     def _launch_backward_generic(self, dprobs):
-        L, P, st = self._call, _lib.ptr, _lib.stream_ptr()
-        _, x, training, drop, seed1, seed2, masks, cnt, _, ws, probs = self._saved
-        B, C, S, K, nb = x.shape[0], self.Chans, self.Samples, self.kernLength, self.nb_classes
-        F1, D, F2 = self.F1, self.D, self.F2
-        C2, T2, NF = F1 * D, ws.T2, ws.NF
-        flat, gflat, offs = self._flat
-        g = {k: gflat[offs[k][0]:offs[k][0] + offs[k][1]] for k in _PARAM_ORDER}
-        w2, w3, wd = P(self.depthwiseConv.weight), P(self.separableConv.weight), P(self.dense.weight)
-        m1 = P(masks[0]) if masks is not None else None
-        m2 = P(masks[1]) if masks is not None else None
-        tr = int(training)
-        L("eav_dense_softmax_bwd", P(dprobs), P(probs), P(ws.p3), wd, P(g["dense.weight"]), P(g["dense.bias"]),
-          P(ws.dp3), B, NF, nb, st)
-        b3 = P(ws.bn3)
-        L("eav_bn_elu_pool_bwd_reduce", P(ws.dp3), P(ws.u3), b3, P(ws.part_pb), B, F2, T2, 8, drop, seed2, m2, cnt, st)
-        L("eav_bn_bwd_finalize", P(ws.part_pb), B, F2, float(B * T2), tr, P(g["separableBN.weight"]),
-          P(g["separableBN.bias"]), b3 + 16 * F2, b3 + 20 * F2, st)
-        L("eav_bn_elu_pool_bwd_apply", P(ws.dp3), P(ws.u3), b3, b3 + 16 * F2, P(ws.du3), B, F2, T2, 8, drop, seed2, m2,
-          cnt, st)
+        L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
+        _, x, training, drop1, drop2, _, ws, probs = self._saved
+        B, nb, C2, F2, T2 = x.shape[0], self.nb_classes, self.F1 * self.D, self.F2, ws.T2
+        g = self._grad_views()
+        w2, w3, wd = self.depthwiseConv.weight, self.separableConv.weight, self.dense.weight
+        L("eav_dense_softmax_bwd", P(dprobs), P(probs), P(ws.p3), P(wd), P(g["dense.weight"]), P(g["dense.bias"]),
+          P(ws.dp3), B, ws.NF, nb, st)
+        self._bn_elu_pool_bwd(ws.dp3, ws.u3, ws.du3, ws.bn3, ws.part_pb, g["separableBN.weight"], g["separableBN.bias"],
+                              B, F2, T2, 8, drop2, training)
         # the dense temporal conv: data gradient = the same kernel on the transposed, tap-flipped weights
-        L("eav_dconv_fwd", P(ws.du3), w3, P(ws.dp2), None, B, F2, C2, T2, 16, 1, st)
-        L("eav_dconv_wgrad", P(ws.du3), P(ws.p2), P(ws.part_cw), B, C2, F2, T2, 16, st)
+        L("eav_dconv_fwd", P(ws.du3), P(w3), P(ws.da2), None, B, F2, C2, T2, 16, 1, st)
+        L("eav_dconv_wgrad", P(ws.du3), P(ws.a2), P(ws.part_cw), B, C2, F2, T2, 16, st)
         n3 = F2 * C2 * 16
         L("eav_reduce_partials", P(ws.part_cw), B, n3, n3, 1.0, P(g["separableConv.weight"]), st)
-        b2 = P(ws.bn2)
-        L("eav_bn_elu_pool_bwd_reduce", P(ws.dp2), P(ws.z), b2, P(ws.part_pb), B, C2, S, 4, drop, seed1, m1, cnt, st)
-        L("eav_bn_bwd_finalize", P(ws.part_pb), B, C2, float(B * S), tr, P(g["depthwiseBN.weight"]),
-          P(g["depthwiseBN.bias"]), b2 + 16 * C2, b2 + 20 * C2, st)
-        L("eav_bn_elu_pool_bwd_apply", P(ws.dp2), P(ws.z), b2, b2 + 16 * C2, P(ws.dz), B, C2, S, 4, drop, seed1, m1,
-          cnt, st)
-        # depthwiseConv <- ELU <- firstBN (post-renorm depthwise weight, Q2), then the firstConv weight gradient
-        b1 = P(ws.bn1)
-        L("eav_spatial_bwd", P(ws.y1), P(ws.dz), b1, w2, P(ws.g1), P(ws.part_sst), P(ws.part_sw), B, C, S, F1, D, 1, st)
-        L("eav_reduce_partials", P(ws.part_sw), ws.np_s, C2 * C, C2 * C, 1.0, P(g["depthwiseConv.weight"]), st)
-        L("eav_bn_bwd_finalize", P(ws.part_sst), ws.np_s, F1, float(B * C * S), tr, P(g["firstBN.weight"]),
-          P(g["firstBN.bias"]), b1 + 16 * F1, b1 + 20 * F1, st)
-        L("eav_tconv_wgrad", P(x), P(ws.y1), P(ws.g1), b1, P(ws.part_tw), B, C, S, F1, K, st)
-        L("eav_reduce_partials", P(ws.part_tw), ws.np_tw, F1 * K, F1 * K, 1.0, P(g["firstConv.weight"]), st)
-        named = dict(self.named_parameters())
-        return [g[k].view(named[k].shape) if named[k].requires_grad else None for k in _PARAM_ORDER]
+        # block 1 (post-renorm depthwise weight, Q2)
+        eegnet_canon.block1_backward(self, ws, x, w2, [g[k] for k in _PARAM_ORDER[:6]], 1, training, drop1)
+        return self._grads_out(g)
 
     def _launch_backward(self, dprobs, token):
         self._check_token(token)
         if self._generic:
             return self._launch_backward_generic(dprobs)
-        L, P, st = self._call, _lib.ptr, _lib.stream_ptr()
-        _, x, training, drop, seed1, seed2, masks, cnt, ws, probs = self._saved
+        L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
+        _, x, training, drop1, drop2, _, ws, probs = self._saved
         B, C, S, K, nb = x.shape[0], self.Chans, self.Samples, self.kernLength, self.nb_classes
         T2, NF = ws.T2, ws.NF
-        flat, gflat, offs = self._flat
-        g = {k: gflat[offs[k][0]:offs[k][0] + offs[k][1]] for k in _PARAM_ORDER}
+        g = self._grad_views()
         w2, wd = P(self.depthwiseConv.weight), P(self.dense.weight)
-        m1 = P(masks[0]) if masks is not None else None
-        m2 = P(masks[1]) if masks is not None else None
         tr = int(training)
 
         L("eav_dense_softmax_bwd", P(dprobs), P(probs), P(ws.p3), wd, P(g["dense.weight"]), P(g["dense.bias"]),
@@ -494,25 +415,20 @@ class EEGNet_tor(KernelModule):
         b3 = P(ws.bn3)
         fuse = bool(self.conv_fuse) and self._use_conv_fft(B)
         if training:
-            L("eav_bn_elu_pool_bwd_reduce", P(ws.dp3), P(ws.u3), b3, P(ws.part_pb), B, 64, T2, 8, drop, seed2, m2, cnt, st)
-            L("eav_bn_bwd_finalize", P(ws.part_pb), B, 64, float(B * T2), tr, P(g["separableBN.weight"]),
-              P(g["separableBN.bias"]), b3 + 4 * 256, b3 + 4 * 320, st)
-            if not fuse:
-                L("eav_bn_elu_pool_bwd_apply", P(ws.dp3), P(ws.u3), b3, b3 + 4 * 256, P(ws.du3), B, 64, T2, 8, drop, seed2,
-                  m2, cnt, st)
+            self._bn_elu_pool_bwd(ws.dp3, ws.u3, None if fuse else ws.du3, ws.bn3, ws.part_pb, g["separableBN.weight"],
+                                  g["separableBN.bias"], B, 64, T2, 8, drop2, training)
         else:
             # eval-mode step (Q4: every epoch after the first): BatchNorm backward is a plain scale, so the gradient and the
             # sums for the BatchNorm weight / bias leave from ONE pass over u3 / dp3
-            L("eav_bn_elu_pool_bwd_eval", P(ws.dp3), P(ws.u3), b3, P(ws.du3), P(ws.part_pb), B, 64, T2, 8, drop, seed2, m2,
-              cnt, st)
+            L("eav_bn_elu_pool_bwd_eval", P(ws.dp3), P(ws.u3), b3, P(ws.du3), P(ws.part_pb), B, 64, T2, 8, *drop2, st)
             L("eav_bn_bwd_finalize", P(ws.part_pb), B, 64, float(B * T2), tr, P(g["separableBN.weight"]),
               P(g["separableBN.bias"]), b3 + 4 * 256, b3 + 4 * 320, st)
         # separableConv: data gradient (flipped/transposed taps, pad 8) and weight gradient
         if fuse:
             # one pack launch for both (the filter spectra of the data gradient were prepared by this step's forward call);
-            # training step: du3 = the eav_bn_elu_pool_bwd_apply above is formed inside it and never written
-            L("eav_conv64_fft_bwd", None if training else P(ws.du3), P(ws.dp3), P(ws.u3), b3, b3 + 4 * 256, drop, seed2, m2,
-              cnt, P(ws.dp2), P(g["separableConv.weight"]), P(ws.c64_ws), B, T2, st)
+            # training step: du3 = the apply pass that _bn_elu_pool_bwd left out is formed inside it and never written
+            L("eav_conv64_fft_bwd", None if training else P(ws.du3), P(ws.dp3), P(ws.u3), b3, b3 + 4 * 256, *drop2,
+              P(ws.dp2), P(g["separableConv.weight"]), P(ws.c64_ws), B, T2, st)
         elif self._use_conv_fft(B):
             # (bwd = 2: the filter spectra of the data gradient were prepared by this step's forward call)
             L("eav_conv64_fft_fwd", P(ws.du3), P(self.separableConv.weight), P(ws.dp2), None, P(ws.c64_ws), B, T2, 2, st)
@@ -527,16 +443,15 @@ class EEGNet_tor(KernelModule):
         b1 = P(ws.bn1)
         # dz = backward of BN2 -> ELU -> pool -> dropout is formed inside dw_bwd: no dz tensor in HBM
         if training:
-            L("eav_bn_elu_pool_bwd_reduce", P(ws.dp2), P(ws.z), b2, P(ws.part_pb), B, 64, S, 4, drop, seed1, m1, cnt, st)
-            L("eav_bn_bwd_finalize", P(ws.part_pb), B, 64, float(B * S), tr, P(g["depthwiseBN.weight"]),
-              P(g["depthwiseBN.bias"]), b2 + 4 * 256, b2 + 4 * 320, st)
+            self._bn_elu_pool_bwd(ws.dp2, ws.z, None, ws.bn2, ws.part_pb, g["depthwiseBN.weight"], g["depthwiseBN.bias"],
+                                  B, 64, S, 4, drop1, training)
             L("eav_eegnet_dw_bwd_fused", P(ws.y1), P(ws.z), P(ws.dp2), b2, b1, w2, P(ws.g1), P(ws.part_dst),
-              P(ws.part_dw2), B, C, S, drop, seed1, m1, cnt, st)
+              P(ws.part_dw2), B, C, S, *drop1, st)
         else:
             # eval-mode step: no sums are needed before dz = scale2 g - they leave from the depthwise pass itself (no reduce
             # launch, no extra read of z and dp2)
             L("eav_eegnet_dw_bwd_fused_eval", P(ws.y1), P(ws.z), P(ws.dp2), b2, b1, w2, P(ws.g1), P(ws.part_dst),
-              P(ws.part_dw2), P(ws.part_dw), B, C, S, drop, seed1, m1, cnt, st)
+              P(ws.part_dw2), P(ws.part_dw), B, C, S, *drop1, st)
         # the finishing work behind the depthwise pass in ONE launch: depthwiseConv.weight (fixed-order sum of the partial
         # rows), firstBN's backward sums -> its gradients and the m1 / m2 the FIR weight gradient folds in, and - eval-mode
         # step - depthwiseBN's, which left from the same pass
@@ -563,8 +478,7 @@ class EEGNet_tor(KernelModule):
                 L("eav_eegnet_fir_wgrad", P(x), P(ws.y1) if training else None, P(ws.g1), b1, P(ws.part_fw), B, C, S, K,
                   st)
             L("eav_reduce_partials", P(ws.part_fw), ws.np_fw, 8 * K, 8 * K, 1.0, P(g["firstConv.weight"]), st)
-        named = dict(self.named_parameters())
-        return [g[k].view(named[k].shape) if named[k].requires_grad else None for k in _PARAM_ORDER]
+        return self._grads_out(g)
 
 
 class Trainer_uni:
@@ -598,15 +512,9 @@ class Trainer_uni:
         dl = self.train_dataloader
         for epoch in range(self.num_epochs):
             for batch_idx, idx in enumerate(dl.index_batches()):
-                if self.use_graph and len(idx) == self.batch_size:
-                    # one captured graph per (batch size, BN mode): epochs >= 2 train in eval mode (Q4)
-                    key = (len(idx), bool(self.model.training))
-                    if key not in self._graphs:
-                        self._graphs[key] = GraphStep(self.model, self.optimizer, self.criterion, dl.x, dl.y,
-                                                      len(idx), self.grad_sync)
-                    scores, loss = self._graphs[key].run(idx)
-                else:
-                    scores, loss = eager_step(self.model, self.optimizer, self.criterion, *dl.gather(idx), self.grad_sync)
+                # one captured graph per (batch size, BN mode): epochs >= 2 train in eval mode (Q4)
+                scores, loss, _ = train_step(self._graphs, self.model, self.optimizer, self.criterion, dl, idx,
+                                             self.use_graph, self.grad_sync)
                 if batch_idx % 100 == 0:
                     print(f"Epoch [{epoch+1}/{self.num_epochs}], Step [{batch_idx}/{len(self.train_dataloader)}], "
                           f"Loss: {loss.item():.4f}")

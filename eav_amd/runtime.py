@@ -1,10 +1,12 @@
 """What the kernel-backed models and their trainers share on the host.
 
     KernelModule     base class of EEGNet_tor, cnn_eeg.EEGNet, ShallowConvNet, AudioModel, VideoModel and
-                     transformer.Encoder: flat parameter storage, the workspace cache, the device checks, the
-                     one-outstanding-forward guard, the dropout step counter, and what GraphStep asks of a model
+                     transformer.Encoder: flat parameter storage and the gradient views a backward returns, the workspace
+                     cache, the device checks, the one-outstanding-forward guard, the dropout set-up of a forward, the
+                     BatchNorm launches the convolutional models share, and what GraphStep asks of a model
     KernelFn         the autograd bridge of all of them
     cached_workspace / gather_batch / DeviceLoader / GraphStep / eager_step   the device-resident training loop
+    train_step       the graph-or-eager step of every trainer
 
 Imports _lib and optim only, never a model module.
 """
@@ -98,6 +100,16 @@ class KernelModule(nn.Module):
         """The parameters in the order of the autograd bridge's gradients: named_parameters() order (= _PARAM_ORDER)."""
         return list(self.parameters())
 
+    def _grad_views(self):
+        """{parameter name: its 1-D view of the flat gradient buffer}."""
+        gflat, offs = self._flat[1], self._flat[2]
+        return {k: gflat[offs[k][0]:offs[k][0] + offs[k][1]] for k in self._names}
+
+    def _grads_out(self, views):
+        """What a backward hands to autograd: the views in the parameters' shapes, None where requires_grad is off."""
+        named = dict(self.named_parameters())
+        return [views[k].view(named[k].shape) if named[k].requires_grad else None for k in self._names]
+
     def set_dropout_masks(self, masks):
         """Testing hook: explicit uint8 keep-masks instead of the counter-based generator; None restores the generator."""
         self._dropout_masks = masks
@@ -108,6 +120,35 @@ class KernelModule(nn.Module):
         if self._fwd_counter is None or self._fwd_counter.device != dev:
             self._fwd_counter = torch.zeros((), dtype=torch.int64, device=dev)
         return self._fwd_counter
+
+    def _dropout(self, dev, active, check=None):
+        """(counter pointer, mk) of a forward: mk(i) is the pointer of the i-th explicit keep-mask, which a training-mode
+        forward uses when set (`check(masks)` validates them first), else None; the counter pointer is that of _counter()
+        when a rate is `active` and the generator draws the masks, else None."""
+        masks = self._dropout_masks if self.training else None
+        if masks is not None:
+            masks = list(masks if check is None else check(masks))
+        cnt = _lib.ptr(self._counter(dev)) if active and masks is None else None
+        return cnt, (lambda i: None if masks is None else masks[i].data_ptr())
+
+    # ------------------------------------------------------------------ BatchNorm launches
+    def _bn_finalize(self, bn, part, nparts, count, buf, training):
+        """Partial sums of `count` values per channel -> mean, invstd, scale, shift in buf[0:4n] and bn's running statistics
+        (eval mode: scale / shift from the running statistics).  num_batches_tracked is the caller's."""
+        b0, n = _lib.ptr(buf), bn.num_features
+        _lib.call("eav_bn_finalize", _lib.ptr(part), nparts, n, float(count), _lib.ptr(bn.weight), _lib.ptr(bn.bias),
+                  _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), int(training), float(bn.momentum), float(bn.eps),
+                  b0, b0 + 4 * n, b0 + 8 * n, b0 + 12 * n, _lib.stream_ptr())
+
+    def _bn_elu_pool_bwd(self, dy, z, dz, buf, part, gw, gb, B, nch, T, pool, dropout, training):
+        """Backward of z [B,nch,T] -> BatchNorm (buf) -> ELU -> AvgPool(pool) -> Dropout from dy: BatchNorm's gradients to
+        gw / gb, its two backward means to buf[4n:6n], d z to dz.  dropout = (rate, seed, mask pointer, counter pointer) of
+        the forward; dz = None stops after the means (the next kernel forms d z itself)."""
+        L, P, st, b = _lib.call, _lib.ptr, _lib.stream_ptr(), _lib.ptr(buf)
+        L("eav_bn_elu_pool_bwd_reduce", P(dy), P(z), b, P(part), B, nch, T, pool, *dropout, st)
+        L("eav_bn_bwd_finalize", P(part), B, nch, float(B * T), int(training), P(gw), P(gb), b + 16 * nch, b + 20 * nch, st)
+        if dz is not None:
+            L("eav_bn_elu_pool_bwd_apply", P(dy), P(z), b, b + 16 * nch, P(dz), B, nch, T, pool, *dropout, st)
 
     # ------------------------------------------------------------------ checks
     def _require_gpu(self, x):
@@ -161,6 +202,23 @@ def eager_step(model, optimizer, criterion, data, targets, grad_sync=None, post_
     # drop the eager step's autograd graph now: its AccumulateGrad nodes, kept alive into the next
     # GraphStep capture, would tie that capture to this stream
     return scores.detach(), loss.detach()
+
+
+def train_step(graphs, model, optimizer, criterion, loader, idx, use_graph, grad_sync=None, post_step=None,
+               eager_input=None):
+    """One training step on the samples `idx` of a DeviceLoader.  A full-size batch with `use_graph` on runs the GraphStep
+    of its (batch size, BN mode), built in `graphs` (the caller's dict) on first use; any other batch is gathered and runs
+    eager_step, the model being fed `eager_input(data)` where given.  Returns detached (scores, loss, targets): targets are
+    the gathered labels of an eager step, None after a GraphStep (which gathers its own inside the graph)."""
+    if use_graph and len(idx) == loader.batch_size:
+        key = (len(idx), bool(model.training))
+        if key not in graphs:
+            graphs[key] = GraphStep(model, optimizer, criterion, loader.x, loader.y, len(idx), grad_sync, post_step)
+        return (*graphs[key].run(idx), None)
+    data, targets = loader.gather(idx)
+    if eager_input is not None:
+        data = eager_input(data)
+    return (*eager_step(model, optimizer, criterion, data, targets, grad_sync, post_step), targets)
 
 
 class GraphStep:

@@ -203,7 +203,7 @@ class _HeadFn(torch.autograd.Function):
             raise _lib.EavError("Encoder.head backward: activations were overwritten by a later head forward")
         model._begin()
         model._head_backward(dlogits.contiguous(), hw.feat, hw, ctx.B, False)
-        return (None, None, *model._grad_views(False))
+        return (None, None, *model._trained_grads(False))
 
 
 class Encoder(KernelModule):
@@ -1378,16 +1378,12 @@ class Encoder(KernelModule):
           P(ws.part_ln), M, D, st)
         self._reduce_gamma_beta(ws.part_ln, ws.np_ln, gp(f"{Lk}.layernorm_before.weight"), gp(f"{Lk}.layernorm_before.bias"))
 
-    def _grad_views(self, full):
+    def _trained_grads(self, full):
         """What a backward hands to autograd, in the order of the parameters the forward took: views of the flat
         gradient buffer for the trained parameters (the classifier alone unless `full`), None for the others."""
-        gflat, offs, pm = self._flat[1], self._flat[2], self._pmap
-        out = []
-        for k in self._names:
-            p = pm[k]
-            trained = p.requires_grad and (full or k.startswith("classifier."))
-            out.append(gflat[offs[k][0]:offs[k][0] + offs[k][1]].view(p.shape) if trained else None)
-        return out
+        g, pm = self._grad_views(), self._pmap
+        return [g[k].view(pm[k].shape) if pm[k].requires_grad and (full or k.startswith("classifier.")) else None
+                for k in self._names]
 
     def _launch_backward(self, dlogits, token):
         self._check_token(token)
@@ -1457,7 +1453,7 @@ class Encoder(KernelModule):
             self._call("eav_reduce_partials", P(ws.part_cs), _lib.plain("eav_colsum_nparts", MP), D, D, 1.0,
                        gp(f"{pre}.embeddings.patch_embeddings.projection.bias"), st)
         self._join_wgrads()          # side-stream weight gradients complete before autograd / the optimiser see them
-        return self._grad_views(full)
+        return self._trained_grads(full)
 
 
 def ASTForAudioClassification(cfg=None, weights=None):

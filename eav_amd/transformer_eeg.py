@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import _lib
 from .optim import CrossEntropyLoss, FusedAdam
-from .runtime import DeviceLoader, GraphStep, KernelFn, KernelModule, eager_step
+from .runtime import DeviceLoader, KernelFn, KernelModule, train_step
 
 NF, KC, POOL, STRIDE, HD = 40, 13, 35, 7, 64     # filters / conv taps / pool window / pool stride / attention tile
 SLOT = 4128                                      # floats per operand-scale slot (EAV_SP_SLOT, include/eav_hip.h)
@@ -183,13 +183,10 @@ class ShallowConvNet(KernelModule):
         w = lambda k: P(n[k])  # noqa: E731
         training = bool(self.training)
         drop = self.drop_p if training else 0.0
-        masks = list(self._dropout_masks) if (training and self._dropout_masks is not None) else None
         self._token += 1
-        cnt = None
-        if drop > 0.0 and masks is None:
-            cnt = P(self._counter(x.device))
+        cnt, mk = self._dropout(x.device, drop > 0.0)
+        if cnt is not None:
             L("eav_counter_inc", cnt, st)
-        mk = (lambda i: P(masks[i])) if masks is not None else (lambda i: None)
         scale = 1.0 / math.sqrt(NF)
         split = self._split_attention()
         if split:
@@ -225,9 +222,7 @@ class ShallowConvNet(KernelModule):
         # head (:135-146): BatchNorm over (batch, time) per feature
         hl, b0 = P(ws.h[self.num_layers]), P(ws.bn)
         L("eav_colstats", hl, P(ws.part_cs), M, NF, NF, st)
-        L("eav_bn_finalize", P(ws.part_cs), ws.np_cs, NF, float(M), w("bn.weight"), w("bn.bias"),
-          P(self.bn.running_mean), P(self.bn.running_var), int(training), float(self.bn.momentum), float(self.bn.eps),
-          b0, b0 + 4 * NF, b0 + 8 * NF, b0 + 12 * NF, st)
+        self._bn_finalize(self.bn, ws.part_cs, ws.np_cs, M, ws.bn, training)
         if training:
             self.bn.num_batches_tracked += 1
         hs = self._seed(self.num_layers, 0)
@@ -235,14 +230,14 @@ class ShallowConvNet(KernelModule):
           mk(3 * self.num_layers), cnt, st)
         L("eav_dense_softmax_fwd", P(ws.feat), w("fc.weight"), P(ws.zero_bias), None, P(ws.probs), B, NF * 65,
           self.nb_classes, st)
-        self._saved = (self._token, x, training, drop, masks, cnt, ws, split)
+        self._saved = (self._token, x, training, drop, mk, cnt, ws, split)
         return self._token
 
     def _launch_backward(self, dprobs, token):
         self._check_token(token)
         L, P = _lib.call, _lib.ptr
         st = self._st = _lib.stream_ptr()
-        _, x, training, drop, masks, cnt, ws, split = self._saved
+        _, x, training, drop, mk, cnt, ws, split = self._saved
         if split:
             ws.bslots.zero_()
         self._ws = ws
@@ -251,7 +246,6 @@ class ShallowConvNet(KernelModule):
         n = dict(self.named_parameters())
         w = lambda k: P(n[k])  # noqa: E731
         gp = lambda k: P(gflat) + 4 * offs[k][0]  # noqa: E731
-        mk = (lambda i: P(masks[i])) if masks is not None else (lambda i: None)
         scale = 1.0 / math.sqrt(NF)
         dh, dy, da, df1, df2, dqkv = P(ws.dh), P(ws.dy), P(ws.da), P(ws.df1), P(ws.df2), P(ws.dqkv)
 
@@ -317,8 +311,7 @@ class ShallowConvNet(KernelModule):
         # the 40 Linear(30,1) weights sit 32 floats apart in the flat buffer (16-byte alignment of every tensor)
         assert offs["embedding.value_proj.1.weight"][0] - offs["embedding.value_proj.0.weight"][0] == 32
         L("eav_add_strided", P(ws.dwv), 30, None, 0, gp("embedding.value_proj.0.weight"), 32, NF, 30, st)
-        return [gflat[offs[k][0]:offs[k][0] + offs[k][1]].view(n[k].shape) if n[k].requires_grad else None
-                for k in self._names]
+        return self._grads_out(self._grad_views())
 
 
 class TrainerUni:
@@ -337,7 +330,7 @@ class TrainerUni:
         self.subject = subject
         self.grad_sync = None      # set by eav_amd.dist.attach(trainer) under torchrun
         self.use_graph = True
-        self._graph = None
+        self._graphs = {}
 
     def _loader(self, x, y, batch_size, shuffle):
         return DeviceLoader(x, y, batch_size, shuffle, self.device)
@@ -352,13 +345,8 @@ class TrainerUni:
         for epoch in range(self.epochs):
             self.model.train()
             for idx in dl.index_batches():
-                if self.use_graph and len(idx) == self.batch_size:
-                    if self._graph is None:
-                        self._graph = GraphStep(self.model, self.optimizer, self.criterion, dl.x, dl.y, len(idx),
-                                                self.grad_sync, post_step=self._max_norm)
-                    self._graph.run(idx)
-                    continue
-                eager_step(self.model, self.optimizer, self.criterion, *dl.gather(idx), self.grad_sync, self._max_norm)
+                train_step(self._graphs, self.model, self.optimizer, self.criterion, dl, idx, self.use_graph,
+                           self.grad_sync, self._max_norm)
             self.criterion.check()        # labels outside [0, classes) seen by any step of this epoch raise here
             acc = self.validate()
             if epoch == self.epochs - 1:

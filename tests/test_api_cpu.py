@@ -388,6 +388,35 @@ def test_runtime_module_is_shared_by_the_models_and_reexported_by_eegnet():
         rt.GraphStep(lin, FusedAdam(lin.parameters(), capturable=True), None, torch.zeros(4, 2), torch.zeros(4), 2)
 
 
+def test_gradient_views_alias_the_flat_gradient_buffer():
+    """KernelModule._grad_views() are the parameters' slices of the flat gradient buffer; _grads_out() hands autograd those
+    slices in the parameters' shapes, in named_parameters() order, and None exactly for the frozen parameters."""
+    import eav_amd.eegnet as eg
+    from eav_amd.cnn_audio import AudioModel
+    from eav_amd.cnn_eeg import EEGNet
+    from eav_amd.transformer_eeg import ShallowConvNet
+    generic = eg.EEGNet_tor(5, F1=4, D=2, F2=8, kernLength=32, Chans=6, Samples=64)
+    assert generic._generic
+    for model in (eg.EEGNet_tor(5), generic, EEGNet(5), ShallowConvNet(5, num_layers=1), AudioModel()):
+        named = list(model.named_parameters())
+        frozen = {named[1][0], named[-1][0]}
+        for k, p in named:
+            p.requires_grad_(k not in frozen)
+        model._ensure_flat()
+        gflat, offs = model._flat[1], model._flat[2]
+        views = model._grad_views()
+        assert list(views) == [k for k, _ in named]
+        for k, v in views.items():
+            assert v.dim() == 1 and v.data_ptr() == gflat.data_ptr() + 4 * offs[k][0] and v.numel() == offs[k][1], k
+        out = model._grads_out(views)
+        assert len(out) == len(named)
+        for (k, p), g in zip(named, out):
+            assert (g is None) == (k in frozen), k
+            if g is not None:
+                assert g.shape == p.shape and g.data_ptr() == views[k].data_ptr(), k
+                assert g.untyped_storage().data_ptr() == gflat.untyped_storage().data_ptr(), k
+
+
 @pytest.mark.parametrize("kind", ["ast", "vit"])
 def test_encoder_flat_layout_is_the_param_shapes_order(kind):
     """The Encoder's flat buffer follows param_shapes (q, k, v weights adjacent, then their biases - the fused q/k/v GEMM,

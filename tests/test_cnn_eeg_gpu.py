@@ -176,6 +176,8 @@ def test_trainer_matches_reference(golden_dir):
             trainer.train_loader.order_override = [g["order0"], g["order1"]]
             trainer.train()
             preds = trainer.predict()
+        captured = [gs for gs in trainer._graphs.values() if gs.graph is not None]
+        assert (len(captured) == 1 and len(trainer._graphs) == 1) if use_graph else trainer._graphs == {}
         model.eval()
         with torch.no_grad():
             logits = model(torch.from_numpy(x[ntr:]).cuda()).cpu()

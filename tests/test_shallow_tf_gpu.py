@@ -161,6 +161,8 @@ def test_trainer_matches_reference(golden_dir, tmp_path, monkeypatch):
             tr.use_graph = use_graph
             tr.train_loader.order_override = [g["order0"], g["order1"]]
             tr.train()
+        captured = [gs for gs in tr._graphs.values() if gs.graph is not None]
+        assert (len(captured) == 1 and len(tr._graphs) == 1) if use_graph else tr._graphs == {}
         # Nothing is copied from the golden into the model.  Six Adam steps at lr 1e-3 through 12 post-norm layers amplify
         # rounding differences ~10x per step (two CPU fp32 runs of the reference's own loop differ by 6e-3 at the end), so
         # against the reference's recorded run this test checks the mechanics (batch order, eval switch, max-norm, printed
