@@ -64,6 +64,8 @@ SIGNATURES = {
     "eav_dense_wide_fwd": [_p, _p, _p, _p, _i, _i, _i, _p],
     "eav_dense_wide_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "eav_ce_wide_fwd_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p],
+    "eav_bce_logits_fwd_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p],
+    "eav_mse_fwd_bwd": [_p, _p, _p, _p, _p, _i, _i, _p],
     "eav_scale_by_scalar": [_p, _p, _i64, _p],
     "eav_adam_step": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _i, _p, _p],
     "eav_counter_inc": [_p, _p],
@@ -198,6 +200,7 @@ PLAIN = {
     "eav_conv64_wgrad_nparts": ([_i, _i], _i),
     "eav_dense_wide_bwd_ws_floats": ([_i, _i, _i], _i64),
     "eav_ce_wide_ws_floats": ([_i], _i64),
+    "eav_head_loss_ws_floats": ([_i], _i64),
     "eav_layernorm_bwd_nparts": ([_i], _i),
     "eav_gemm_f32_splitk_plan": ([_i, _i, _i], _i),
     "eav_colsum_nparts": ([_i], _i),

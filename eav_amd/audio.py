@@ -9,7 +9,9 @@ Transformer_Audio.py:22-24 does) and `num_classes` anything up to transformer.HE
 equal-length clips go through the HIP log-mel front-end, ragged ones through the reference's own host call of
 ASTFeatureExtractor.  Kept quirks: `weight_decay` is accepted and ignored (Q10); one optimiser spans both phases
 (Q11); outputs_test only after the last unfrozen epoch (Q15); one line per epoch appended to
-training_performance_audio.txt in the cwd (Q17).
+training_performance_audio.txt in the cwd (Q17).  Beyond the reference: the keyword-only `problem_type`
+("multi_label_classification" / "regression": fp32 label rows, BCE-with-logits / MSE, the epoch lines of
+finetune.FineTuneBase's docstring) and `save_pretrained(dir)`.
 """
 from __future__ import annotations
 
@@ -20,15 +22,16 @@ from .finetune import FineTuneBase, require_gpu
 
 
 class AudioModelTrainer(FineTuneBase):
-    def __init__(self, DATA, model_path, sub='', num_classes=5, weight_decay=1e-5, lr=0.001, batch_size=128):
+    def __init__(self, DATA, model_path, sub='', num_classes=5, weight_decay=1e-5, lr=0.001, batch_size=128, *,
+                 problem_type=None):
         device = require_gpu("AudioModelTrainer")
         self.device = device
         self.tr, self.tr_y, self.te, self.te_y = DATA
         self.tr_x, self.te_x = self._feature_extract(self.tr), self._feature_extract(self.te)
-        self.sub, self.batch_size = sub, batch_size
+        self.sub, self.batch_size, self.problem_type = sub, batch_size, problem_type
         self.train_dataloader = self._prepare_dataloader(self.tr_x, self.tr_y, shuffle=True)
         self.test_dataloader = self._prepare_dataloader(self.te_x, self.te_y, shuffle=False)
-        self._build(model_path, num_classes, lr, device)          # :22-31
+        self._build(model_path, num_classes, lr, device, problem_type)          # :22-31
 
     def _prepare_dataloader(self, x, y, shuffle=False):
         return self._loader(x, y, shuffle)
@@ -48,6 +51,15 @@ class AudioModelTrainer(FineTuneBase):
         self._enter_phase(lr, freeze)
         for epoch in range(epochs):
             correct, seen = self._train_one_epoch()
+            if not self._classifies():
+                train_metric = float(correct.item()) / seen
+                rows = self._evaluate()
+                test_metric = self._metric_text(sum(r[1] for r in rows) / sum(r[2] for r in rows))
+                self._keep_outputs(rows, epoch == epochs - 1, freeze)
+                print(f"Epoch {epoch + 1}/{epochs}, Training {self._metric_text(train_metric)}, Test {test_metric}")
+                with open('training_performance_audio.txt', 'a') as f:
+                    f.write(f"{self.sub}, Epoch {epoch + 1}, Test {test_metric}\n")
+                continue
             train_accuracy = int(correct.item()) / seen
             rows = self._evaluate()
             test_accuracy = sum(r[1] for r in rows) / sum(r[2] for r in rows)      # sample-weighted (:92-97)

@@ -9,13 +9,16 @@ audio.py / vision.py keep the reference's constructors, method signatures and co
 """
 from __future__ import annotations
 
+import os
+import shutil
+
 import numpy as np
 import torch
 
 from . import _lib
-from .optim import CrossEntropyLoss, FusedAdam
+from .optim import BCEWithLogitsLoss, CrossEntropyLoss, FusedAdam, MSELoss
 from .runtime import DeviceLoader
-from .transformer import Encoder
+from .transformer import PROBLEM_TYPES, Encoder
 
 
 def require_gpu(who):
@@ -26,9 +29,23 @@ def require_gpu(who):
 
 
 class FineTuneBase:
-    """Owns model, optimiser, loaders; subclasses provide the reference-specific reporting."""
+    """Owns model, optimiser, loaders; subclasses provide the reference-specific reporting.
 
-    def _build(self, model_path, n_classes, lr, device):
+    `problem_type` (keyword-only argument of both trainers, HF's config.problem_type): None or
+    "single_label_classification" is the reference's schedule - integer labels, cross-entropy, argmax accuracy, the
+    reference's printed lines.  "multi_label_classification" and "regression" take fp32 label rows [N, num_labels]
+    ([N] for one label), train with BCEWithLogitsLoss / MSELoss, and report, where the reference's lines say
+    "Accuracy: x%",
+        multi-label   "Label Accuracy: x%"   elements with (logit > 0) == (target > 0.5) over all samples x labels,
+                                             counted on the device by the criterion (nhits)
+        regression    "MSE: v"               the mean squared error over all samples x labels (no accuracy exists)
+    e.g. "Epoch 1/20, Training Label Accuracy: 50.00%, Test Label Accuracy: 50.00%" (audio) and "Epoch 1, Test MSE:
+    0.123456" (vision); the log files get the same wording.  The model's cfg.problem_type is set, so save_pretrained
+    writes it; `outputs_test` holds raw logits in every mode."""
+
+    problem_type = None
+
+    def _build(self, model_path, n_classes, lr, device, problem_type=None):
         """The reference's order (Transformer_Audio.py:22-24, Transformer_Vision.py:29-30): load the checkpoint with the
         head its config.json describes - 527 AudioSet or 1000 ImageNet classes for the stock downloads - then replace
         that head by a fresh Linear(hidden, n_classes); 1 <= n_classes <= transformer.HEAD_MAX_CLASSES."""
@@ -41,11 +58,48 @@ class FineTuneBase:
         self.initial_lr = lr
         # AdamW with torch's default weight decay 0.01: the reference never forwards its own argument (Q10)
         self.optimizer = FusedAdam(self.model.parameters(), lr=lr, weight_decay=0.01, decoupled=True)
-        self.loss_fn = CrossEntropyLoss()
+        if problem_type is not None and problem_type not in PROBLEM_TYPES:
+            raise ValueError(f"problem_type {problem_type!r}: expected None or one of {PROBLEM_TYPES}")
+        self.problem_type = problem_type
+        if problem_type is not None:
+            self.model.cfg.problem_type = problem_type
+        self.loss_fn = {"multi_label_classification": BCEWithLogitsLoss, "regression": MSELoss}.get(
+            problem_type, CrossEntropyLoss)()
         self.grad_sync = None
 
+    def _classifies(self):
+        """Integer class labels and cross-entropy (the reference's schedule)."""
+        return self.problem_type in (None, "single_label_classification")
+
     def _loader(self, x, y, shuffle):
-        return DeviceLoader(x, y, self.batch_size, shuffle, self.device)
+        if self._classifies():
+            return DeviceLoader(x, y, self.batch_size, shuffle, self.device)
+        return DeviceLoader(x, y, self.batch_size, shuffle, self.device, label_dtype=torch.float32)
+
+    def save_pretrained(self, save_directory):
+        """The fine-tuned model as an HF directory (Encoder.save_pretrained), with the preprocessor_config.json of the
+        directory it was loaded from, if that had one."""
+        self.model.save_pretrained(save_directory)
+        src = os.path.join(self.model.source_dir or "", "preprocessor_config.json")
+        if self.model.source_dir and os.path.exists(src):
+            shutil.copyfile(src, os.path.join(save_directory, "preprocessor_config.json"))
+
+    def _metric_text(self, value):
+        """The new modes' replacement of the reference's "Accuracy: x%" (class docstring)."""
+        return f"MSE: {value:.6f}" if self.problem_type == "regression" else f"Label Accuracy: {value * 100:.2f}%"
+
+    def _count(self, logits, tb, out, loss=None):
+        """The epoch metrics of the new modes, on the device: multi-label adds the batch's element hits to the int32
+        `out`, regression its squared-error sum (mean loss x elements; `loss`: the step's own, where there was one) to
+        the fp32 `out`.  Returns the element count."""
+        if self.problem_type == "regression":
+            if loss is None:
+                self.loss_fn.accumulate(logits, tb, self._batch_loss)
+                loss = self._batch_loss
+            out += loss * tb.numel()
+        else:
+            self.loss_fn.accumulate(logits, tb, self._batch_loss, out)
+        return tb.numel()
 
     def _enter_phase(self, lr, freeze):
         lr = self.initial_lr if lr is None else lr
@@ -90,9 +144,13 @@ class FineTuneBase:
                                 "have_train": False, "have_test": False}
 
     def _train_one_epoch(self, after_batch=None):
-        """Returns (#correct on device, #seen).  One optimiser step per batch; nothing is read back per step."""
+        """Returns (#correct on device, #seen).  One optimiser step per batch; nothing is read back per step.
+        Multi-label: (#element hits, #elements); regression: (squared-error sum, #elements)."""
         self.model.train()
-        correct = torch.zeros((), dtype=torch.long, device=self.device)
+        classifies = self._classifies()
+        correct = torch.zeros((), device=self.device, dtype=torch.long if classifies else
+                              torch.float32 if self.problem_type == "regression" else torch.int32)
+        self._batch_loss = torch.zeros((), dtype=torch.float32, device=self.device)
         dl = self.train_dataloader
         seen, nb = 0, len(dl)
         fc = getattr(self, "_feat_cache", None)
@@ -106,12 +164,16 @@ class FineTuneBase:
                 logits = self.model(xb).logits
                 if fc is not None:
                     fc["train"][self._index(idx)] = self.model.last_features()
-            self.loss_fn(logits, tb).backward()
+            loss = self.loss_fn(logits, tb)
+            loss.backward()
             if self.grad_sync is not None:
                 self.grad_sync()
             self.optimizer.step()
-            correct += (logits.argmax(dim=-1) == tb).sum()
-            seen += tb.size(0)
+            if classifies:
+                correct += (logits.argmax(dim=-1) == tb).sum()
+                seen += tb.size(0)
+            else:
+                seen += self._count(logits.detach(), tb, correct, loss.detach())
             if after_batch is not None:
                 after_batch(k, nb)
         if fc is not None:
@@ -125,13 +187,17 @@ class FineTuneBase:
     def _evaluate(self):
         """Test pass: list of (logits numpy [b, classes], #correct, b) per batch.  Logits and per-batch hit counts stay on
         the device until the pass is over - ONE device-to-host copy per epoch (the reference synchronises twice per
-        batch: Transformer_Audio.py:91-96, Transformer_Vision.py:111-116)."""
+        batch: Transformer_Audio.py:91-96, Transformer_Vision.py:111-116).  Multi-label: (logits, #element hits,
+        #elements); regression: (logits, squared-error sum, #elements)."""
+        classifies = self._classifies()
         self.model.eval()
         dl = self.test_dataloader
         n, nb = len(dl.dataset), len(dl)
         fc = getattr(self, "_feat_cache", None)
         all_logits = torch.empty(n, self.model.cfg.num_labels, device=self.device)
-        hits = torch.zeros(nb, dtype=torch.long, device=self.device)
+        hits = torch.zeros(nb, device=self.device, dtype=torch.long if classifies else
+                           torch.float32 if self.problem_type == "regression" else torch.int32)
+        self._batch_loss = torch.zeros((), dtype=torch.float32, device=self.device)
         spans, pos = [], 0
         with torch.no_grad():
             for k, idx in enumerate(dl.index_batches()):
@@ -144,12 +210,17 @@ class FineTuneBase:
                     if fc is not None:
                         fc["test"][pos:pos + len(idx)] = self.model.last_features()
                 all_logits[pos:pos + len(idx)] = logits
-                hits[k] = (logits.argmax(dim=-1) == tb).sum()
-                spans.append((pos, len(idx)))
+                if classifies:
+                    hits[k] = (logits.argmax(dim=-1) == tb).sum()
+                    spans.append((pos, len(idx)))
+                else:
+                    spans.append((pos, len(idx), self._count(logits, tb, hits[k:k + 1])))
                 pos += len(idx)
         if fc is not None:
             fc["have_test"] = True
         host_logits, host_hits = all_logits.cpu().numpy(), hits.cpu().tolist()      # the epoch's only read-back
+        if not classifies:
+            return [(host_logits[a:a + b], h, n) for (a, b, n), h in zip(spans, host_hits)]
         return [(host_logits[a:a + b], int(h), b) for (a, b), h in zip(spans, host_hits)]
 
     def _keep_outputs(self, rows, is_last_epoch, freeze):

@@ -1,4 +1,4 @@
-"""Fused Adam / AdamW over flat parameter storage + the cross-entropy criterion.
+"""Fused Adam / AdamW over flat parameter storage + the criteria (cross-entropy, BCE-with-logits, MSE).
 
 Host-side mirrors of what the reference trainers construct:
   * ``optim.Adam(model.parameters(), lr)``            CNN_torch/EEGNet_tor.py:82
@@ -6,7 +6,10 @@ Host-side mirrors of what the reference trainers construct:
     (weight_decay is torch's default 0.01 - the trainer's ctor argument is ignored)
   * ``nn.CrossEntropyLoss()``                          EEGNet_tor.py:81, Transformer_Audio.py:31
 
-The arithmetic runs in libeav_hip.so (``eav_adam_step`` / ``eav_ce_fwd_bwd``).
+  * ``nn.BCEWithLogitsLoss()`` / ``nn.MSELoss()``      the other two losses HF's classification models pick by
+    ``config.problem_type`` (transformers/loss/loss_utils.py, ForSequenceClassificationLoss)
+
+The arithmetic runs in libeav_hip.so (``eav_adam_step`` / ``eav_ce_fwd_bwd`` / ``eav_bce_logits_fwd_bwd`` / ``eav_mse_fwd_bwd``).
 Parameters that live in one flat buffer (``flatten_parameters``) are updated
 with one launch per run of tensors that share a step count - the frozen and
 unfrozen fine-tuning phases give the head and the backbone different counts
@@ -186,17 +189,21 @@ class _CEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        # d loss / d scores was produced by the forward launch; the incoming gradient (1.0 for loss.backward()) is
-        # applied in place by the library - no torch kernel inside a captured step.  `unit_gradient(device)` is a constant
-        # 1.0 that callers may pass as the seed (loss.backward(gradient=...)): recognised here, nothing is launched
-        if gout.data_ptr() != _UNIT.get(gout.device, (None, 0))[1]:
-            # any other upstream gradient scales a COPY: ctx.dsc stays the unit-gradient result, so a second backward
-            # (retain_graph=True) or a re-used graph never scales twice
-            out = ctx.dsc.clone()
-            _lib.call("eav_scale_by_scalar", out.data_ptr(), gout.contiguous().data_ptr(), out.numel(),
-                      _lib.stream_ptr())
-            return out, None, None, None
-        return ctx.dsc, None, None, None
+        return _seeded(ctx.dsc, gout), None, None, None
+
+
+def _seeded(dsc, gout):
+    """The gradient a criterion's backward returns.  d loss / d scores (`dsc`) was produced by the forward launch; the
+    incoming gradient (1.0 for loss.backward()) is applied by the library - no torch kernel inside a captured step.
+    `unit_gradient(device)` is a constant 1.0 that callers may pass as the seed (loss.backward(gradient=...)): recognised
+    here, nothing is launched."""
+    if gout.data_ptr() != _UNIT.get(gout.device, (None, 0))[1]:
+        # any other upstream gradient scales a COPY: dsc stays the unit-gradient result, so a second backward
+        # (retain_graph=True) or a re-used graph never scales twice
+        out = dsc.clone()
+        _lib.call("eav_scale_by_scalar", out.data_ptr(), gout.contiguous().data_ptr(), out.numel(), _lib.stream_ptr())
+        return out
+    return dsc
 
 
 # classes the narrow head kernels are meant for (eav_dense_softmax_* keeps them in registers, eav_ce_fwd_bwd walks a row
@@ -309,3 +316,111 @@ class CrossEntropyLoss:
         if self._flag is None or self._flag.device != scores.device:
             self._flag = torch.zeros((), dtype=torch.int32, device=scores.device)
         return _CEFn.apply(scores, targets.contiguous(), self._flag, self._scratch_for(scores))
+
+
+class _ElementLossFn(torch.autograd.Function):
+    """_CEFn's shape for the element-wise criteria: the forward launch produces the loss and d loss / d scores together."""
+
+    @staticmethod
+    def forward(ctx, scores, targets, crit):
+        loss = torch.empty((), dtype=torch.float32, device=scores.device)
+        dsc = torch.empty_like(scores) if ctx.needs_input_grad[0] else None      # no gradient buffer under no_grad
+        crit._launch(scores, targets, loss, dsc, None)
+        ctx.dsc = dsc
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        return _seeded(ctx.dsc, gout), None, None
+
+
+class _ElementLoss:
+    """What BCEWithLogitsLoss and MSELoss share: the mean over all batch x classes elements and its gradient from one
+    launch of csrc/head_loss.hip (one wave per row, row sums added in row order - no atomics, two runs give the same bits).
+
+    Targets are fp32 [batch, classes] on the scores' device ([batch] accepted for one class; integer targets are
+    converted to fp32) and are not validated - torch accepts any float - so `check()` has nothing to report and is a
+    no-op that trainers may call blindly.  The kernels' per-row scratch is kept on the criterion, one buffer per
+    (batch, device): nothing is allocated for it in the launch path, and nothing synchronises with the host."""
+
+    _NAME = _ENTRY = None
+
+    def __init__(self):
+        self._scratch = {}
+
+    def check(self):
+        pass
+
+    def _scratch_for(self, scores):
+        key = (scores.shape[0], scores.device)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(_lib.plain("eav_head_loss_ws_floats", scores.shape[0]), dtype=torch.float32,
+                                             device=scores.device)
+        return self._scratch[key]
+
+    def _operands(self, scores, targets, who):
+        if not isinstance(scores, torch.Tensor) or not scores.is_cuda or not isinstance(targets, torch.Tensor) \
+                or not targets.is_cuda:
+            raise _lib.EavError(f"{who} needs device tensors (no CPU fallback)")
+        if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
+            raise _lib.EavError(f"{who}: scores must be a contiguous fp32 [batch, classes] tensor, got "
+                                f"{tuple(scores.shape)} {scores.dtype}")
+        B, NC = scores.shape
+        # every operand goes to the kernel as a raw pointer: a tensor elsewhere would be dereferenced on this GPU
+        if targets.device != scores.device:
+            raise _lib.EavError(f"{who}: targets are on {targets.device}, the scores on {scores.device}")
+        if tuple(targets.shape) != (B, NC) and not (NC == 1 and tuple(targets.shape) == (B,)):
+            raise _lib.EavError(f"{who}: targets {tuple(targets.shape)} for scores {(B, NC)}")
+        if targets.dtype != torch.float32:
+            targets = targets.float()
+        return targets.reshape(B, NC).contiguous()
+
+    def _out_check(self, t, dtype, what, scores, who):
+        if not isinstance(t, torch.Tensor) or t.device != scores.device or t.dtype != dtype or t.numel() < 1:
+            raise _lib.EavError(f"{who}: {what} must be a {str(dtype).replace('torch.', '')} tensor on {scores.device}")
+
+    def __call__(self, scores, targets):
+        targets = self._operands(scores, targets, self._NAME)
+        return _ElementLossFn.apply(scores, targets, self)
+
+
+class BCEWithLogitsLoss(_ElementLoss):
+    """``nn.BCEWithLogitsLoss()`` (mean over batch x classes; no pos_weight): HF's loss for
+    problem_type "multi_label_classification".  Term max(x, 0) - x t + log1p(exp(-|x|)), torch's form, finite for any
+    finite logit; gradient (sigmoid(x) - t) / (batch x classes).  See _ElementLoss for targets, scratch and check()."""
+
+    _NAME = "BCEWithLogitsLoss"
+
+    def _launch(self, scores, targets, loss, dsc, nhits):
+        B, NC = scores.shape
+        _lib.call("eav_bce_logits_fwd_bwd", scores.data_ptr(), targets.data_ptr(), _lib.ptr(loss), _lib.ptr(dsc),
+                  _lib.ptr(nhits), self._scratch_for(scores).data_ptr(), B, NC, _lib.stream_ptr())
+
+    def accumulate(self, scores, targets, loss_out, nhits):
+        """Evaluation form (no gradient, nothing read back): the batch's mean loss into the 0-dim device tensor
+        `loss_out`, and the number of elements with (score > 0) == (target > 0.5) - the multi-label counterpart of
+        CrossEntropyLoss's argmax hits - added to the device int32 `nhits`."""
+        who = "BCEWithLogitsLoss.accumulate"
+        targets = self._operands(scores, targets, who)
+        self._out_check(loss_out, torch.float32, "loss_out", scores, who)
+        self._out_check(nhits, torch.int32, "nhits", scores, who)
+        self._launch(scores, targets, loss_out, None, nhits)
+
+
+class MSELoss(_ElementLoss):
+    """``nn.MSELoss()`` (mean over batch x classes): HF's loss for problem_type "regression".  Term (x - t)^2, gradient
+    2 (x - t) / (batch x classes).  See _ElementLoss for targets, scratch and check()."""
+
+    _NAME = "MSELoss"
+
+    def _launch(self, scores, targets, loss, dsc, nhits):
+        B, NC = scores.shape
+        _lib.call("eav_mse_fwd_bwd", scores.data_ptr(), targets.data_ptr(), _lib.ptr(loss), _lib.ptr(dsc),
+                  self._scratch_for(scores).data_ptr(), B, NC, _lib.stream_ptr())
+
+    def accumulate(self, scores, targets, loss_out):
+        """Evaluation form (no gradient, nothing read back): the batch's mean loss into the 0-dim device tensor `loss_out`."""
+        who = "MSELoss.accumulate"
+        targets = self._operands(scores, targets, who)
+        self._out_check(loss_out, torch.float32, "loss_out", scores, who)
+        self._launch(scores, targets, loss_out, None, None)

@@ -43,11 +43,20 @@ def gather_batch(xs, ys, idx_dev):
     if not xs.is_cuda:   # host tensors (CPU-side unit tests of the loader only)
         return xs.index_select(0, idx_dev), ys.index_select(0, idx_dev)
     data = torch.empty((n,) + tuple(xs.shape[1:]), dtype=torch.float32, device=xs.device)
-    targets = torch.empty(n, dtype=torch.long, device=xs.device)
-    st = _lib.stream_ptr()
-    _lib.call("eav_gather_rows", xs.data_ptr(), idx_dev.data_ptr(), data.data_ptr(), n, xs[0].numel(), st)
-    _lib.call("eav_gather_i64", ys.data_ptr(), idx_dev.data_ptr(), targets.data_ptr(), n, st)
-    return data, targets
+    _lib.call("eav_gather_rows", xs.data_ptr(), idx_dev.data_ptr(), data.data_ptr(), n, xs[0].numel(), _lib.stream_ptr())
+    return data, gather_labels(ys, idx_dev)
+
+
+def gather_labels(ys, idx_dev):
+    """ys[idx] in HBM: int64 class indices [N] through eav_gather_i64, fp32 label rows [N] / [N, NC] (regression and
+    multi-label targets, DeviceLoader(label_dtype=torch.float32)) through eav_gather_rows."""
+    n = idx_dev.numel()
+    out = torch.empty((n,) + tuple(ys.shape[1:]), dtype=ys.dtype, device=ys.device)
+    if ys.dtype == torch.float32:
+        _lib.call("eav_gather_rows", ys.data_ptr(), idx_dev.data_ptr(), out.data_ptr(), n, ys[0].numel(), _lib.stream_ptr())
+    else:
+        _lib.call("eav_gather_i64", ys.data_ptr(), idx_dev.data_ptr(), out.data_ptr(), n, _lib.stream_ptr())
+    return out
 
 
 class KernelFn(torch.autograd.Function):
@@ -303,12 +312,19 @@ class DeviceLoader:
     torch samplers (RandomSampler / SequentialSampler + BatchSampler), consuming
     the torch RNG exactly as ``iter(DataLoader)`` does, so a seeded run visits
     the same batches as the reference.
+
+    label_dtype: torch.long (default) keeps class indices [N]; torch.float32 keeps regression / multi-label targets as
+    fp32 [N] or [N, NC], gathered by rows.
     """
 
-    def __init__(self, x, y, batch_size, shuffle, device):
+    def __init__(self, x, y, batch_size, shuffle, device, label_dtype=torch.long):
         from torch.utils.data import TensorDataset
+        if label_dtype not in (torch.long, torch.float32):
+            raise ValueError(f"DeviceLoader: label_dtype must be torch.long or torch.float32, not {label_dtype}")
         self.x = torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
-        self.y = torch.as_tensor(y, dtype=torch.long).to(device).contiguous()
+        self.y = torch.as_tensor(y, dtype=label_dtype).to(device).contiguous()
+        if label_dtype == torch.float32 and self.y.dim() not in (1, 2):
+            raise ValueError(f"DeviceLoader: labels of shape {tuple(self.y.shape)}")
         self.dataset = TensorDataset(self.x, self.y)
         self.batch_size, self.shuffle, self.device = batch_size, shuffle, device
         self.order_override = None  # tests: list of index arrays, one per epoch
@@ -338,9 +354,9 @@ class DeviceLoader:
         if idx[-1] - idx[0] == len(idx) - 1 and all(b - a == 1 for a, b in zip(idx, idx[1:])):
             return self.y[idx[0]:idx[-1] + 1]
         i = torch.as_tensor(idx, dtype=torch.long, device=self.device)
-        out = torch.empty(len(idx), dtype=torch.long, device=self.device)
-        _lib.call("eav_gather_i64", self.y.data_ptr(), i.data_ptr(), out.data_ptr(), len(idx), _lib.stream_ptr())
-        return out
+        if not self.y.is_cuda:   # host tensors (CPU-side unit tests of the loader only)
+            return self.y.index_select(0, i)
+        return gather_labels(self.y, i)
 
     def __iter__(self):
         for idx in self.index_batches():

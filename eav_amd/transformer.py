@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .optim import HEAD_NARROW_CLASSES, flatten_parameters
+from .optim import HEAD_NARROW_CLASSES, BCEWithLogitsLoss, CrossEntropyLoss, MSELoss, flatten_parameters
 from .runtime import KernelFn, KernelModule, gather_batch
 from .weight_planes import SLOT, WeightPlanes
 
@@ -43,13 +43,19 @@ DEFAULT_PRECISION = "split"
 # registers), beyond that on eav_dense_wide_* (csrc/head_wide.hip; EAV_HEAD_MAX_CLASSES of include/eav_hip.h) - AudioSet's
 # 527, ImageNet's 1000, ImageNet-21k's 21 843.
 HEAD_MAX_CLASSES = 32768
+# HF config.problem_type: which loss a labelled forward takes (transformers/loss/loss_utils.py, ForSequenceClassificationLoss)
+PROBLEM_TYPES = ("regression", "single_label_classification", "multi_label_classification")
 
 # ----------------------------------------------------------------------------- configuration
 def make_config(kind, hidden=768, layers=12, heads=12, ff=3072, eps=1e-12, num_labels=5, patch=16, mel=128,
                 frames=1024, fstride=10, tstride=10, image=224, channels=3, hidden_dropout=0.0, attention_dropout=0.0,
-                id2label=None):
+                id2label=None, problem_type=None):
     """hidden_dropout / attention_dropout: HF hidden_dropout_prob / attention_probs_dropout_prob, applied in training mode
-    at the four sites of Encoder.dropout_sites; 0 <= p < 1 (0: the site does not exist)."""
+    at the four sites of Encoder.dropout_sites; 0 <= p < 1 (0: the site does not exist).  problem_type: HF's
+    config.problem_type, one of PROBLEM_TYPES or None (resolved by the first labelled forward, resolve_problem_type)."""
+    if problem_type is not None and problem_type not in PROBLEM_TYPES:
+        raise ValueError(f"problem_type {problem_type!r}: expected None or one of {PROBLEM_TYPES}")
+    _check_single_label(problem_type, num_labels)
     for name, p in (("hidden_dropout", hidden_dropout), ("attention_dropout", attention_dropout)):
         if not (isinstance(p, (int, float)) and 0.0 <= float(p) < 1.0):
             raise ValueError(f"make_config: {name} must satisfy 0 <= p < 1, got {p!r}")
@@ -67,7 +73,7 @@ def make_config(kind, hidden=768, layers=12, heads=12, ff=3072, eps=1e-12, num_l
                            num_labels=num_labels, patch=patch, ny=ny, nx=nx, npatch=ny * nx, nextra=nextra,
                            ntok=ny * nx + nextra, prefix=prefix, kp=geo["C"] * patch * patch,
                            hidden_dropout=float(hidden_dropout), attention_dropout=float(attention_dropout),
-                           id2label=id2label, **geo)
+                           id2label=id2label, problem_type=problem_type, **geo)
 
 
 def config_from_hf(cfg_json: dict):
@@ -80,7 +86,8 @@ def config_from_hf(cfg_json: dict):
                   num_labels=len(cfg_json["id2label"]) if "id2label" in cfg_json else cfg_json.get("num_labels", 2),
                   hidden_dropout=cfg_json.get("hidden_dropout_prob", 0.0),
                   attention_dropout=cfg_json.get("attention_probs_dropout_prob", 0.0),
-                  id2label=[names[k] for k in sorted(names, key=int)] if names else None)
+                  id2label=[names[k] for k in sorted(names, key=int)] if names else None,
+                  problem_type=cfg_json.get("problem_type"))
     if cfg_json.get("hidden_act", "gelu") != "gelu":
         raise NotImplementedError("only the exact erf GELU is implemented")
     if mt == "audio-spectrogram-transformer":
@@ -91,6 +98,45 @@ def config_from_hf(cfg_json: dict):
         return make_config("vit", image=cfg_json.get("image_size", 224), channels=cfg_json.get("num_channels", 3),
                            **common)
     raise NotImplementedError(f"model_type {mt!r}")
+
+
+def _check_single_label(problem_type, num_labels):
+    """HF's configuration refuses this pair too: a cross-entropy over one class is identically 0."""
+    if problem_type == "single_label_classification" and num_labels == 1:
+        raise ValueError('problem_type "single_label_classification" requires num_labels > 1: use num_labels = 2 for a '
+                         'binary classification, or problem_type "regression" for a single-output head')
+
+
+def resolve_problem_type(num_labels, labels):
+    """The problem_type HF's ForSequenceClassificationLoss settles on when the config leaves it unset: one label is a
+    regression, several labels with integer targets (torch.long / torch.int) a single-label classification, anything
+    else - float targets - a multi-label one."""
+    if num_labels == 1:
+        return "regression"
+    if num_labels > 1 and labels.dtype in (torch.long, torch.int):
+        return "single_label_classification"
+    return "multi_label_classification"
+
+
+def config_to_hf(cfg):
+    """config.json of `cfg` (the inverse of config_from_hf): what HF needs to rebuild the model, and everything
+    config_from_hf reads.  problem_type is left out while it is unset; labels without names are LABEL_i, HF's default."""
+    names = list(cfg.id2label) if cfg.id2label is not None else [f"LABEL_{i}" for i in range(cfg.num_labels)]
+    if len(names) != cfg.num_labels:
+        raise ValueError(f"{len(names)} label names for {cfg.num_labels} labels")
+    out = dict(hidden_size=cfg.hidden, num_hidden_layers=cfg.layers, num_attention_heads=cfg.heads,
+               intermediate_size=cfg.ff, hidden_act="gelu", layer_norm_eps=cfg.eps, patch_size=cfg.patch, qkv_bias=True,
+               hidden_dropout_prob=cfg.hidden_dropout, attention_probs_dropout_prob=cfg.attention_dropout)
+    if cfg.kind == "ast":
+        out.update(model_type="audio-spectrogram-transformer", architectures=["ASTForAudioClassification"],
+                   num_mel_bins=cfg.H, max_length=cfg.W, frequency_stride=cfg.sy, time_stride=cfg.sx)
+    else:
+        out.update(model_type="vit", architectures=["ViTForImageClassification"], image_size=cfg.H, num_channels=cfg.C)
+    if cfg.problem_type is not None:
+        out["problem_type"] = cfg.problem_type
+    out["id2label"] = {str(i): n for i, n in enumerate(names)}
+    out["label2id"] = {n: i for i, n in enumerate(names)}
+    return out
 
 
 def param_shapes(cfg):
@@ -227,6 +273,9 @@ class Encoder(KernelModule):
             _set_param(self, k, v)
         self._names = list(shapes)
         self._hws = {}                # batch size -> head-only workspace (Encoder.head)
+        self._criteria = {}           # problem type -> the criterion of forward(labels=...), built on first use
+        self._inferred_problem_type = None      # what a labelled forward resolved cfg.problem_type to (reset_head)
+        self.source_dir = None        # the directory from_pretrained read
         self.kernel_events = None
         # Dropout (cfg.hidden_dropout / cfg.attention_dropout, training mode only): every keep decision is a hash of
         # (dropout_seed, site, device-resident forward counter, element index) - no mask is stored, the backward
@@ -321,7 +370,25 @@ class Encoder(KernelModule):
         missing = [k for k in shapes if k not in w]
         if missing:
             raise KeyError(f"checkpoint lacks {missing[:4]} ...")
-        return cls(cfg, w)
+        model = cls(cfg, w)
+        model.source_dir = str(model_path)
+        return model
+
+    def save_pretrained(self, save_directory):
+        """The inverse of from_pretrained: config.json (config_to_hf) and model.safetensors - state_dict() as it stands,
+        HF 5.x key names, fp32, read from the parameters (views of the flat buffer: current after any number of optimiser
+        steps; the fp16 operand planes are never read).  Works for a CPU- or device-resident model; the Hugging Face
+        classes load the directory."""
+        from safetensors.numpy import save_file
+        os.makedirs(save_directory, exist_ok=True)
+        shapes = param_shapes(self.cfg)
+        sd = self.state_dict()
+        assert sorted(sd) == sorted(shapes), set(sd) ^ set(shapes)
+        tensors = {k: np.ascontiguousarray(sd[k].detach().cpu().numpy().reshape(shapes[k])) for k in shapes}
+        save_file(tensors, os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
+        with open(os.path.join(save_directory, "config.json"), "w") as f:
+            json.dump(config_to_hf(self.cfg), f, indent=2)
+            f.write("\n")
 
     def reset_head(self, weight, bias):
         """Replace the classification Linear (the reference does `classifier.dense = nn.Linear(768, n)`,
@@ -336,6 +403,11 @@ class Encoder(KernelModule):
         head.bias = nn.Parameter(torch.as_tensor(bias, dtype=torch.float32).clone().to(dev))
         self.cfg.num_labels = head.weight.shape[0]
         self.cfg.id2label = None            # the checkpoint's names belonged to the head that just left
+        # so did a problem type that a labelled forward inferred from that head's width; one set in the config or by the
+        # caller stays
+        if self._inferred_problem_type is not None and self.cfg.problem_type == self._inferred_problem_type:
+            self.cfg.problem_type = None
+        self._inferred_problem_type = None
         self._flat = None
         self._ws = None
         self._wss, self._hws = {}, {}
@@ -391,9 +463,25 @@ class Encoder(KernelModule):
         logits = KernelFn.apply(x, self, *[self._pmap[k] for k in self._names])
         loss = None
         if labels is not None:
-            from .optim import CrossEntropyLoss
-            loss = CrossEntropyLoss()(logits, labels)
+            loss = self.criterion(labels)(logits, labels)
         return _Out(logits, loss)
+
+    def criterion(self, labels=None):
+        """The criterion of cfg.problem_type, held on the encoder: CrossEntropyLoss, BCEWithLogitsLoss or MSELoss
+        (optim.py).  While the type is unset, `labels` resolve it as HF does (resolve_problem_type) and it is written into
+        cfg.problem_type, where it stays - HF mutates its config in the same way."""
+        c = self.cfg
+        if c.problem_type is None:
+            if labels is None:
+                raise ValueError("Encoder.criterion: cfg.problem_type is unset and there are no labels to resolve it from")
+            c.problem_type = self._inferred_problem_type = resolve_problem_type(c.num_labels, labels)
+        if c.problem_type not in PROBLEM_TYPES:
+            raise ValueError(f"problem_type {c.problem_type!r}: expected one of {PROBLEM_TYPES}")
+        _check_single_label(c.problem_type, c.num_labels)
+        if c.problem_type not in self._criteria:
+            self._criteria[c.problem_type] = {"regression": MSELoss, "single_label_classification": CrossEntropyLoss,
+                                              "multi_label_classification": BCEWithLogitsLoss}[c.problem_type]()
+        return self._criteria[c.problem_type]
 
     def forward_batch(self, xs, ys, idx, optimizer):
         data, targets = gather_batch(xs, ys, idx)

@@ -8,6 +8,9 @@ plus the trial-level vote of the driver block (:174-185) as `trial_vote`.  The V
 eav_amd.transformer.Encoder; uniform uint8 frames are pre-processed by one HIP kernel (bit-identical to the HF
 processor), anything else by the reference's host route; processed frames live in HBM (Q13).  Kept quirks:
 test accuracy is the mean of per-batch accuracies (Q14), outputs_test only after the last unfrozen epoch (Q15).
+Beyond the reference: the keyword-only `problem_type` ("multi_label_classification" / "regression": fp32 label rows,
+repeated per frame; BCE-with-logits / MSE; the epoch lines of finetune.FineTuneBase's docstring, their metric weighted by
+elements) and `save_pretrained(dir)`.
 """
 from __future__ import annotations
 
@@ -40,14 +43,14 @@ def _load_processor(model_path):
 
 
 class ImageClassifierTrainer(FineTuneBase):
-    def __init__(self, DATA, model_path, sub='', num_labels=5, lr=5e-5, batch_size=128):
+    def __init__(self, DATA, model_path, sub='', num_labels=5, lr=5e-5, batch_size=128, *, problem_type=None):
         device = require_gpu("ImageClassifierTrainer")
         self.tr_x, self.tr_y, self.te_x, self.te_y = DATA
         self.model_path, self.num_labels, self.batch_size, self.sub = model_path, num_labels, batch_size, sub
         self.frame_per_sample = np.shape(self.tr_x)[1]
         self.test_prediction = list()
         self.processor = _load_processor(model_path)                          # :28
-        self._build(model_path, num_labels, lr, device)                       # :29-36
+        self._build(model_path, num_labels, lr, device, problem_type)         # :29-36
         self.model.num_labels = num_labels                                    # :31
         print("Image preprocessing..")
         self.train_dataloader = self._prepare_dataloader(self.tr_x, self.tr_y, shuffle=True)[0]
@@ -56,7 +59,10 @@ class ImageClassifierTrainer(FineTuneBase):
 
     def _prepare_dataloader(self, x, y, shuffle=True):
         processed_x = self.preprocess_images(x)
-        y_repeated = torch.from_numpy(np.repeat(y, self.frame_per_sample)).long()
+        if self._classifies():
+            y_repeated = torch.from_numpy(np.repeat(y, self.frame_per_sample)).long()
+        else:       # label rows [N] / [N, num_labels]: one copy of the row per frame
+            y_repeated = torch.from_numpy(np.repeat(np.asarray(y, dtype=np.float32), self.frame_per_sample, axis=0))
         c, hw = self.model.cfg.C, self.model.cfg.H
         return self._loader(processed_x.view(-1, c, hw, hw), y_repeated, shuffle), processed_x, y_repeated
 
@@ -82,6 +88,13 @@ class ImageClassifierTrainer(FineTuneBase):
             self._train_one_epoch(after_batch=lambda k, nb: print(f'batch ({k}/{nb})'))
             rows = self._evaluate()
             self._keep_outputs(rows, epoch == epochs - 1, freeze)
+            if not self._classifies():
+                test_metric = self._metric_text(sum(r[1] for r in rows) / sum(r[2] for r in rows))
+                print(f"Epoch {epoch + 1}, Test {test_metric}")
+                if log:
+                    with open('training_performance.txt', 'a') as f:
+                        f.write(f"{self.sub}, Epoch {epoch + 1}, Test {test_metric}\n")
+                continue
             avg_accuracy = sum(r[1] / r[2] for r in rows) / len(rows)          # mean of batch accuracies (Q14)
             print(f"Epoch {epoch + 1}, Test Accuracy: {avg_accuracy * 100:.2f}%")
             if log:

@@ -261,6 +261,17 @@ int eav_dense_wide_bwd(const float* dlogits, const float* in, const float* w, fl
 int64_t eav_ce_wide_ws_floats(int B);
 int eav_ce_wide_fwd_bwd(const float* in, const int64_t* y, float* loss, float* din, int* ncorrect, int* bad_label,
                         float* ws, int B, int NC, void* stream);
+/* The other two losses of HF's ForSequenceClassificationLoss (csrc/head_loss.hip), mean over all B * NC elements like torch's
+ * defaults, laid out like eav_ce_wide_fwd_bwd (one wave per row, row sums in ws, added in row order: no atomics, two runs
+ * give the same bits).  logits, targets fp32 [B,NC], 1 <= NC <= EAV_HEAD_MAX_CLASSES, B * NC < 2^31; targets are not
+ * validated (torch accepts any float); loss, dlogits and nhits may each be NULL; ws: eav_head_loss_ws_floats(B) floats.
+ * nn.BCEWithLogitsLoss: term max(x,0) - x t + log1p(exp(-|x|)), dlogits = (sigmoid(x) - t) / (B NC), *nhits += the number
+ * of elements with (x > 0) == (t > 0.5).  nn.MSELoss: term (x - t)^2, dlogits = 2 (x - t) / (B NC). */
+int64_t eav_head_loss_ws_floats(int B);
+int eav_bce_logits_fwd_bwd(const float* logits, const float* targets, float* loss, float* dlogits, int* nhits, float* ws,
+                           int B, int NC, void* stream);
+int eav_mse_fwd_bwd(const float* logits, const float* targets, float* loss, float* dlogits, float* ws, int B, int NC,
+                    void* stream);
 /* v[i] *= *scalar (device scalar): the upstream gradient applied to the stored d loss / d scores. */
 int eav_scale_by_scalar(float* v, const float* scalar, int64_t n, void* stream);
 /* torch.optim.Adam (decoupled=0) / AdamW (decoupled=1) update of one flat tensor; step >= 1.

@@ -15,7 +15,7 @@ group (the reference's nn.DataParallel wrap, Transformer_Audio.py:59-60 / Transf
 all_gather of `outputs_test` (SURVEY 8e level 1); vision adds the trial vote + weighted F1 of Transformer_Vision.py:174-185.
 `--audio-root DIR` (audio only) loads every subject from DIR/subjectNN/Audio instead: eav_amd.audio_data.DataLoadAudio
 (WAV files, resampled to 16 kHz on the GPU, 5 s clips) and EAVDataSplit(...).get_split(h_idx=56), as the reference driver
-does.  For vision, replace `synthetic_subject` by the pickles the reference driver reads.  The model directory is an HF-format
+does.  `--save-dir DIR` keeps every subject's fine-tuned model as DIR/subjectNN/ (FineTuneBase.save_pretrained).  For vision, replace `synthetic_subject` by the pickles the reference driver reads.  The model directory is an HF-format
 directory (`--model-path`); without one a random-init full-size model is written to a temporary directory.
 """
 import argparse
@@ -67,6 +67,8 @@ def main():
     ap.add_argument("--audio-root", default=None, help="audio only: dataset folder holding subjectNN/Audio/*.wav")
     ap.add_argument("--no-hybrid", action="store_true", help="plain round-robin: the remainder one subject per rank")
     ap.add_argument("--backend", default=os.environ.get("EAV_DIST_BACKEND"))
+    ap.add_argument("--save-dir", default=None, help="write every fine-tuned subject model to DIR/subjectNN/ (HF directory: "
+                    "config.json, model.safetensors, preprocessor_config.json when the source had one); off by default")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     audio = args.kind == "audio"
@@ -114,6 +116,8 @@ def main():
                 tr.train(epochs=args.frozen_epochs, lr=5e-4, freeze=True)
                 tr.train(epochs=unfrozen, lr=5e-6, freeze=False)
             if n == 1 or ranks[0] == rank:                    # one report per subject
+                if args.save_dir:                             # after the subject's last phase
+                    tr.save_pretrained(os.path.join(cwd, args.save_dir, f"subject{sub:02d}"))
                 out[sub] = (np.asarray(tr.outputs_test, dtype=np.float32), np.asarray(data[3]))
             del tr
             torch.cuda.empty_cache()
