@@ -32,7 +32,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, pos_interp
 from .optim import HEAD_NARROW_CLASSES, BCEWithLogitsLoss, CrossEntropyLoss, MSELoss, flatten_parameters
 from .runtime import KernelFn, KernelModule, gather_batch
 from .weight_planes import SLOT, WeightPlanes
@@ -43,6 +43,8 @@ DEFAULT_PRECISION = "split"
 # registers), beyond that on eav_dense_wide_* (csrc/head_wide.hip; EAV_HEAD_MAX_CLASSES of include/eav_hip.h) - AudioSet's
 # 527, ImageNet's 1000, ImageNet-21k's 21 843.
 HEAD_MAX_CLASSES = 32768
+# Tokens per sequence the attention / softmax kernels take
+MAX_TOKENS = 2048
 # HF config.problem_type: which loss a labelled forward takes (transformers/loss/loss_utils.py, ForSequenceClassificationLoss)
 PROBLEM_TYPES = ("regression", "single_label_classification", "multi_label_classification")
 
@@ -105,6 +107,30 @@ def _check_single_label(problem_type, num_labels):
     if problem_type == "single_label_classification" and num_labels == 1:
         raise ValueError('problem_type "single_label_classification" requires num_labels > 1: use num_labels = 2 for a '
                          'binary classification, or problem_type "regression" for a single-output head')
+
+
+def interpolated_geometry(cfg, H, W):
+    """The geometry of a forward of a ViT `cfg` on H x W images with interpolate_pos_encoding on: a copy of cfg whose H, W,
+    ny, nx, npatch and ntok are those of the input (ny = H // patch, nx = W // patch: the remainder pixels are dropped, as the
+    strided patch convolution drops them), everything else unchanged, plus pos_grid - the side g of the stored g x g position
+    grid when the table has to be resampled to ny x nx, None when HF uses the stored table as it is (ny nx == g g and
+    H == W: HF's own shortcut, kept literally).  Pure: needs no device.  ValueError for an image smaller than a patch,
+    NotImplementedError beyond MAX_TOKENS tokens and for AST (HF's AST has no such argument)."""
+    if cfg.kind != "vit":
+        raise NotImplementedError("interpolate_pos_encoding exists for ViT only (HF's AST takes no such argument)")
+    H, W = int(H), int(W)
+    if H < cfg.patch or W < cfg.patch:
+        raise ValueError(f"interpolate_pos_encoding: a {H} x {W} image holds no {cfg.patch} x {cfg.patch} patch")
+    ny, nx = H // cfg.patch, W // cfg.patch
+    if ny * nx + cfg.nextra > MAX_TOKENS:
+        raise NotImplementedError(f"at most {MAX_TOKENS} tokens: a {H} x {W} image gives {ny * nx + cfg.nextra}")
+    g = int(cfg.npatch ** 0.5)
+    if g * g != cfg.npatch:
+        raise NotImplementedError(f"interpolate_pos_encoding needs a square stored position grid, not {cfg.ny} x {cfg.nx}")
+    geo = SimpleNamespace(**vars(cfg))
+    geo.H, geo.W, geo.ny, geo.nx, geo.npatch, geo.ntok = H, W, ny, nx, ny * nx, ny * nx + cfg.nextra
+    geo.pos_grid = None if (ny * nx == g * g and H == W) else g
+    return geo
 
 
 def resolve_problem_type(num_labels, labels):
@@ -344,10 +370,17 @@ class Encoder(KernelModule):
         self._scales_all = False
         # multi-GPU: called as hook(lo, hi) from inside the backward whenever flat_grad[lo:hi] is final
         self.grad_ready_hook = None
+        # ViT, HF's forward(..., interpolate_pos_encoding=True): images of any size >= one patch, the position table resampled
+        # to their patch grid (csrc/pos_interp.hip).  This attribute is the default of forward()'s argument - what
+        # forward_batch, a captured step and the trainers run with.  The geometry (H, W, ny, nx, npatch, ntok) then belongs to
+        # the forward, not to the model: _geo is that of the forward in flight (or of the one whose backward runs), cfg itself
+        # - param_shapes, state_dict, save_pretrained - never changes.
+        self.interpolate_pos_encoding = False
+        self._active_geo = None       # None: the geometry of cfg
         if cfg.hidden % cfg.heads or (cfg.hidden // cfg.heads) % 4 or cfg.hidden % 4 or cfg.hidden > 1024:
             raise NotImplementedError("hidden size must be <= 1024, a multiple of 4, head_dim a multiple of 4")
-        if cfg.ntok > 2048:
-            raise NotImplementedError("at most 2048 tokens")
+        if cfg.ntok > MAX_TOKENS:
+            raise NotImplementedError(f"at most {MAX_TOKENS} tokens")
         if not 1 <= cfg.num_labels <= HEAD_MAX_CLASSES:
             raise NotImplementedError(f"the classification head takes 1 .. HEAD_MAX_CLASSES = {HEAD_MAX_CLASSES} classes, "
                                       f"not {cfg.num_labels}")
@@ -449,13 +482,32 @@ class Encoder(KernelModule):
             self._flat = flatten_parameters(self, order=self._names)
             self._pmap = dict(self.named_parameters())
 
-    def forward(self, x=None, labels=None, pixel_values=None, input_values=None):
+    @property
+    def _geo(self):
+        """The geometry the launch functions read: cfg, or what interpolated_geometry derived for the forward in flight."""
+        return self._active_geo if self._active_geo is not None else self.cfg
+
+    def forward(self, x=None, labels=None, pixel_values=None, input_values=None, interpolate_pos_encoding=None):
         x = x if x is not None else (pixel_values if pixel_values is not None else input_values)
         self._require_gpu(x)
         c = self.cfg
-        want = (c.W, c.H) if c.kind == "ast" else (c.C, c.H, c.W)
-        if tuple(x.shape[1:]) != want:
-            raise ValueError(f"expected input [B,{','.join(map(str, want))}], got {tuple(x.shape)}")
+        interp = self.interpolate_pos_encoding if interpolate_pos_encoding is None else bool(interpolate_pos_encoding)
+        geo = None
+        if interp:
+            if c.kind != "vit":
+                raise NotImplementedError("interpolate_pos_encoding exists for ViT only (HF's AST takes no such argument)")
+            if x.dim() != 4 or x.shape[1] != c.C:
+                raise ValueError(f"expected input [B,{c.C},H,W], got {tuple(x.shape)}")
+            if (x.shape[2], x.shape[3]) != (c.H, c.W):          # (the native size keeps cfg: today's launches, bit for bit)
+                geo = interpolated_geometry(c, x.shape[2], x.shape[3])
+                if self.training and self.dropout_active():
+                    raise NotImplementedError("dropout at a non-native image size is not implemented (DESIGN.md section 11): "
+                                              "the dropout sites are laid out for cfg.ntok tokens")
+        else:
+            want = (c.W, c.H) if c.kind == "ast" else (c.C, c.H, c.W)
+            if tuple(x.shape[1:]) != want:
+                raise ValueError(f"expected input [B,{','.join(map(str, want))}], got {tuple(x.shape)}")
+        self._active_geo = geo
         x = x.contiguous().float()
         self._ensure_flat()
         self._want_full = torch.is_grad_enabled() and any(
@@ -595,7 +647,7 @@ class Encoder(KernelModule):
         return "eav_gemm_bf16" if low else "eav_gemm_f32"
 
     def _alloc(self, B, dev, full_backward):
-        c = self.cfg
+        c = self._geo
         D, FF, N, H, Lr = c.hidden, c.ff, c.ntok, c.heads, c.layers
         M = B * N
         ldn = (N + 3) // 4 * 4
@@ -604,6 +656,10 @@ class Encoder(KernelModule):
         ws = SimpleNamespace(B=B, M=M, ldn=ldn, full=full_backward, sp=sp)
         nsave = Lr if full_backward else 1
         ws.col = f(B * c.npatch, c.kp)
+        if getattr(c, "pos_grid", None) is not None:      # the position table resampled to this forward's patch grid
+            ws.pos_i = f(N, D)
+            if full_backward:                             # ... and the gradient eav_embed_bwd leaves for that table
+                ws.dpos_i = f(N, D)
         ws.hs = [f(M, D) for _ in range(Lr + 1)] if full_backward else [f(M, D), f(M, D)]
         ws.y1 = [f(M, D) for _ in range(1 if sp else nsave)]     # split mode keeps planes, not fp32 copies
         ws.fused = self._fused_attention()
@@ -656,7 +712,7 @@ class Encoder(KernelModule):
     FS, BS = 5, 8   # slots per layer: forward y1, qkv, ao, y2, act; backward dh(fc2), dact, dh(o), dao, dS, dqkv, dy(fc1), dy(qkv)
 
     def _alloc_split(self, ws, dev, nsave):
-        c = self.cfg
+        c = self._geo
         D, FF, Lr, M = c.hidden, c.ff, c.layers, ws.M
         MP = ws.B * c.npatch
         kp = lambda k: _lib.plain("eav_sp_kpad", k)  # noqa: E731
@@ -751,7 +807,7 @@ class Encoder(KernelModule):
         """Whether this step runs its weight gradients / final reductions beside the main stream (overlap_wgrad)."""
         o = self.overlap_wgrad
         if o == "auto":
-            return self._ws is not None and self._ws.B * self.cfg.ntok >= 8192
+            return self._ws is not None and self._ws.B * self._geo.ntok >= 8192
         return bool(o)
 
     def _begin(self):
@@ -964,7 +1020,8 @@ class Encoder(KernelModule):
         evaluation batch): the 5000 % 128 = 8 frames at the end of every vision epoch must not free and re-zero the 19 GB
         of the B = 128 one.  One allocated for a full backward also serves the no_grad forwards of its batch size; one
         without the backward's buffers is replaced when a full backward comes."""
-        key = (B, str(dev), self._fused_attention(), self.precision == "split", self._head_wide())
+        key = (B, str(dev), self._fused_attention(), self.precision == "split", self._head_wide(),
+               (self._geo.H, self._geo.W))
         old = self._wss.get(key)
         if old is not None and full and not old.full:
             del self._wss[key]
@@ -978,7 +1035,7 @@ class Encoder(KernelModule):
         return self._workspace(key, make, keep_unpinned=3)
 
     def _launch_forward(self, x):
-        c = self.cfg
+        c = self._geo
         P, L = _lib.ptr, self._call
         st = self._begin()
         self._phase = "fwd"
@@ -1007,9 +1064,14 @@ class Encoder(KernelModule):
                        P(h0) + 4 * c.nextra * D, c.npatch, D, c.kp, c.kp, c.kp, D, batch=B,
                        sA=(c.npatch * c.kp, 0), sC=(N * D, 0),
                        bias=w(f"{pre}.embeddings.patch_embeddings.projection.bias"))
+        pos = w(f"{pre}.embeddings.position_embeddings")
+        g = getattr(c, "pos_grid", None)
+        if g is not None:
+            tb = pos_interp.device_tables(g, c.ny, c.nx, x.device)
+            L("eav_pos_bicubic_fwd", pos, P(ws.pos_i), g, c.ny, c.nx, D, c.nextra, *[P(t) for t in tb["fwd"]], st)
+            pos = P(ws.pos_i)
         L("eav_embed_finish", P(h0), w(f"{pre}.embeddings.cls_token"),
-          w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None,
-          w(f"{pre}.embeddings.position_embeddings"), B, N, D, c.nextra, st)
+          w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None, pos, B, N, D, c.nextra, st)
         if drop.ph > 0.0:
             self._drop_add(P(h0), None, P(h0), ws.M * D, drop.ph, 0, "emb")
         scale = (D // c.heads) ** -0.5
@@ -1031,12 +1093,12 @@ class Encoder(KernelModule):
             L("eav_pair_mean", P(ws.seqr), P(ws.pooled), B, D, 0, st)
         self._head_forward(ws.pooled if c.kind == "ast" else ws.seqr, ws, B)
         self._token += 1
-        self._saved = (self._token, x, full)
+        self._saved = (self._token, x, full, self._active_geo)
         return self._token
 
     def _layer_forward_f32(self, i, j, hin, hout, Lk, stp, scale):
         """One encoder layer on the exact-fp32 GEMM and attention kernels (precision "fp32"; _gemm_name: also bf16)."""
-        c, ws = self.cfg, self._ws
+        c, ws = self._geo, self._ws
         P, L, st = _lib.ptr, self._call, self._st
         D, FF, N, H, M, B, ldn = c.hidden, c.ff, c.ntok, c.heads, ws.M, ws.B, ws.ldn
         hd = D // H
@@ -1091,7 +1153,7 @@ class Encoder(KernelModule):
         """Materialised-score path, backward of the attention core of layer i with the batched product `g`: dV = Pd^T dO,
         dP = dO V^T, dS = softmax backward (in place over dP), dQ = s dS K, dK = s dS^T Q.  With attention dropout the
         softmax backward gates dP and regenerates the dropped probabilities Pd, so it runs before the dV product."""
-        c, ws = self.cfg, self._ws
+        c, ws = self._geo, self._ws
         D, N, H = c.hidden, c.ntok, c.heads
         hd, ldn, B = D // H, ws.ldn, ws.B
         P, d = _lib.ptr, ws.drop
@@ -1143,7 +1205,7 @@ class Encoder(KernelModule):
         """One encoder layer with every projection on the split-operand GEMM; the attention core stays on the fp32
         kernels.  LayerNorm / attention / GELU outputs are converted to planes once (plus the transposed planes when
         a backward will follow); only the planes are kept per layer."""
-        c, ws = self.cfg, self._ws
+        c, ws = self._geo, self._ws
         P, L, st = _lib.ptr, self._call, self._st
         D, FF, N, H, M = c.hidden, c.ff, c.ntok, c.heads, ws.M
         hd = D // H
@@ -1259,7 +1321,7 @@ class Encoder(KernelModule):
         """Backward of one layer: dh (gradient w.r.t. the layer output, fp32) in ws.dh on entry, gradient w.r.t. the
         layer input on exit.  Every weight gradient is a split-K GEMM over the transposed planes; data gradients use
         the planes of the transposed weights."""
-        c, ws = self.cfg, self._ws
+        c, ws = self._geo, self._ws
         P, L, st = _lib.ptr, self._call, self._st
         D, FF, N, H, M = c.hidden, c.ff, c.ntok, c.heads, ws.M
         hd = D // H
@@ -1419,7 +1481,7 @@ class Encoder(KernelModule):
     def _layer_backward_f32(self, i, Lk, stp, gp, scale):
         """Backward of one layer on the exact-fp32 kernels: ws.dh holds the gradient w.r.t. the layer output on entry, the
         gradient w.r.t. the layer input on exit."""
-        c, ws = self.cfg, self._ws
+        c, ws = self._geo, self._ws
         P, L, st = _lib.ptr, self._call, self._st
         D, FF, N, H, M, B = c.hidden, c.ff, c.ntok, c.heads, ws.M, ws.B
         hd = D // H
@@ -1475,11 +1537,11 @@ class Encoder(KernelModule):
 
     def _launch_backward(self, dlogits, token):
         self._check_token(token)
-        c = self.cfg
+        full, self._active_geo = self._saved[2], self._saved[3]       # the geometry of the forward this backward belongs to
+        c = self._geo
         P, L = _lib.ptr, self._call
         st = self._begin()
         self._phase = "bwd"
-        full = self._saved[2]
         ws = self._ws
         B, M, sp = ws.B, ws.M, ws.sp
         D, N = c.hidden, c.ntok
@@ -1520,7 +1582,16 @@ class Encoder(KernelModule):
             # ---- embeddings ("emb" dropout: dh is final here, so its gate runs in place)
             if drop.ph > 0.0:
                 self._drop_add(dh, None, dh, M * D, drop.ph, 0, "emb")
-            L("eav_embed_bwd", dh, gp(f"{pre}.embeddings.position_embeddings"), P(ws.demb), B, N, D, c.nextra, st)
+            g = getattr(c, "pos_grid", None)
+            if g is None:
+                L("eav_embed_bwd", dh, gp(f"{pre}.embeddings.position_embeddings"), P(ws.demb), B, N, D, c.nextra, st)
+            else:
+                # the gradient of the RESAMPLED table first; the stored table's is its image under the adjoint operator
+                # (row 0, the cls position, is copied - the cls-token gradient below reads the same values as ever)
+                L("eav_embed_bwd", dh, P(ws.dpos_i), P(ws.demb), B, N, D, c.nextra, st)
+                tb = pos_interp.device_tables(g, c.ny, c.nx, ws.dpos_i.device)
+                L("eav_pos_bicubic_bwd", P(ws.dpos_i), gp(f"{pre}.embeddings.position_embeddings"), g, c.ny, c.nx, D,
+                  c.nextra, *[P(t) for t in tb["bwd_y"]], tb["nnzy"], *[P(t) for t in tb["bwd_x"]], tb["nnzx"], st)
             gpos = gflat[offs[f"{pre}.embeddings.position_embeddings"][0]:]
             gflat[offs[f"{pre}.embeddings.cls_token"][0]:][:D].copy_(gpos[:D])
             if c.kind == "ast":

@@ -10,7 +10,10 @@ processor), anything else by the reference's host route; processed frames live i
 test accuracy is the mean of per-batch accuracies (Q14), outputs_test only after the last unfrozen epoch (Q15).
 Beyond the reference: the keyword-only `problem_type` ("multi_label_classification" / "regression": fp32 label rows,
 repeated per frame; BCE-with-logits / MSE; the epoch lines of finetune.FineTuneBase's docstring, their metric weighted by
-elements) and `save_pretrained(dir)`.
+elements), `save_pretrained(dir)`, and the keyword-only `image_size` (an int or (H, W)): the frames are resized to that
+size instead of the processor's and the ViT runs with interpolate_pos_encoding on - the checkpoint's position table
+resampled to the smaller patch grid (transformer.Encoder.forward), so a 56 x 56 face crop need not be blown up to
+224 x 224 and its 197 tokens; the saved checkpoint keeps the stored table and image_size.
 """
 from __future__ import annotations
 
@@ -43,8 +46,15 @@ def _load_processor(model_path):
 
 
 class ImageClassifierTrainer(FineTuneBase):
-    def __init__(self, DATA, model_path, sub='', num_labels=5, lr=5e-5, batch_size=128, *, problem_type=None):
+    def __init__(self, DATA, model_path, sub='', num_labels=5, lr=5e-5, batch_size=128, *, problem_type=None,
+                 image_size=None):
         device = require_gpu("ImageClassifierTrainer")
+        if image_size is not None:
+            hw = (image_size, image_size) if isinstance(image_size, (int, np.integer)) else tuple(image_size)
+            if len(hw) != 2 or not all(isinstance(v, (int, np.integer)) and v > 0 for v in hw):
+                raise ValueError(f"image_size must be a positive int or (H, W), got {image_size!r}")
+            image_size = (int(hw[0]), int(hw[1]))
+        self.image_size = image_size
         self.tr_x, self.tr_y, self.te_x, self.te_y = DATA
         self.model_path, self.num_labels, self.batch_size, self.sub = model_path, num_labels, batch_size, sub
         self.frame_per_sample = np.shape(self.tr_x)[1]
@@ -52,6 +62,10 @@ class ImageClassifierTrainer(FineTuneBase):
         self.processor = _load_processor(model_path)                          # :28
         self._build(model_path, num_labels, lr, device, problem_type)         # :29-36
         self.model.num_labels = num_labels                                    # :31
+        if image_size is not None:
+            from .transformer import interpolated_geometry
+            interpolated_geometry(self.model.cfg, *image_size)                # refuse a size the encoder cannot take now
+            self.model.interpolate_pos_encoding = True
         print("Image preprocessing..")
         self.train_dataloader = self._prepare_dataloader(self.tr_x, self.tr_y, shuffle=True)[0]
         self.test_dataloader = self._prepare_dataloader(self.te_x, self.te_y, shuffle=False)[0]
@@ -63,8 +77,9 @@ class ImageClassifierTrainer(FineTuneBase):
             y_repeated = torch.from_numpy(np.repeat(y, self.frame_per_sample)).long()
         else:       # label rows [N] / [N, num_labels]: one copy of the row per frame
             y_repeated = torch.from_numpy(np.repeat(np.asarray(y, dtype=np.float32), self.frame_per_sample, axis=0))
-        c, hw = self.model.cfg.C, self.model.cfg.H
-        return self._loader(processed_x.view(-1, c, hw, hw), y_repeated, shuffle), processed_x, y_repeated
+        c = self.model.cfg.C
+        h, w = self.image_size if self.image_size is not None else (self.model.cfg.H, self.model.cfg.H)
+        return self._loader(processed_x.view(-1, c, h, w), y_repeated, shuffle), processed_x, y_repeated
 
     def preprocess_images(self, image_list):
         """:52-59 - per-frame processor + one stack().to(device) in the reference."""
@@ -76,9 +91,13 @@ class ImageClassifierTrainer(FineTuneBase):
             from .preprocess import frames_to_pixel_values
             sz = p.size
             hw = (int(sz["height"]), int(sz["width"])) if isinstance(sz, dict) else (int(sz.height), int(sz.width))
+            if self.image_size is not None:
+                hw = self.image_size
             return frames_to_pixel_values(arr.reshape(-1, *arr.shape[2:]), hw, p.image_mean, p.image_std,
                                           p.rescale_factor, self.device)
-        frames = [self.processor(images=img, return_tensors="pt").pixel_values.squeeze() for s in image_list for img in s]
+        size = {} if self.image_size is None else {"size": {"height": self.image_size[0], "width": self.image_size[1]}}
+        frames = [self.processor(images=img, return_tensors="pt", **size).pixel_values.squeeze()
+                  for s in image_list for img in s]
         return torch.stack(frames).to(self.device)
 
     def train(self, epochs=3, lr=None, freeze=True, log=False):

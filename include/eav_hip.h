@@ -552,6 +552,20 @@ int eav_im2col(const float* x, float* col, int B, int C, int H, int W, int P, in
 int eav_embed_finish(float* h, const float* cls, const float* dist, const float* pos, int B, int ntok, int D,
                      int nextra, void* stream);
 int eav_embed_bwd(const float* dh, float* dpos, float* demb, int B, int ntok, int D, int nextra, void* stream);
+/* ViT position table at another patch grid (HF ViTEmbeddings.interpolate_pos_encoding: F.interpolate(mode="bicubic",
+ * align_corners=False), no antialiasing): pos [nextra + g*g, D] -> out [nextra + ny*nx, D], the first nextra rows copied,
+ * the patch rows out = (Wy (x) Wx) pos.  iy / ix [n_out][4] are the source indices of the four taps of every output index
+ * along its axis (each within [0, g)), wy / wx [n_out][4] their weights; a tap of weight 0 is skipped, so an identity
+ * resampling copies bit for bit.  The tables are device arrays (eav_amd/pos_interp.py builds them in float64).
+ * eav_pos_bicubic_bwd is the exact adjoint in gather form: dpos [nextra + g*g, D] from dout [nextra + ny*nx, D], one
+ * workgroup per source row walking the transposed per-axis lists - ypt / xpt [g + 1] CSR row pointers, yidx / xidx the
+ * output indices, yw / xw the weights, nnzy / nnzx their lengths (<= 4 n_out) - in stored order: no atomics, the same bits
+ * on every run, every element of dpos written.  D % 4 == 0; pos / out / dout / dpos 16-byte aligned; g, ny, nx <= 2048. */
+int eav_pos_bicubic_fwd(const float* pos, float* out, int g, int ny, int nx, int D, int nextra, const int* iy,
+                        const float* wy, const int* ix, const float* wx, void* stream);
+int eav_pos_bicubic_bwd(const float* dout, float* dpos, int g, int ny, int nx, int D, int nextra, const int* ypt,
+                        const int* yidx, const float* yw, int nnzy, const int* xpt, const int* xidx, const float* xw,
+                        int nnzx, void* stream);
 /* gather (scatter=0) / scatter (1) the first nextra token rows of every image: rows[b*nextra+e] <-> h[b,e]. */
 int eav_token_rows(float* h, float* rows, int B, int ntok, int D, int nextra, int scatter, void* stream);
 /* AST pooled = (cls + dist)/2 (HF AST :304); backward=1 writes dseq from dpooled. */

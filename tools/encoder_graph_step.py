@@ -2,7 +2,12 @@
 """Encoder train step at small per-rank batches: eager two-stream (default) vs eager single-stream vs ONE hipGraph replay of
 the single-stream step (forward, CE, backward, AdamW).  Prints ms per step and checks that the replayed losses equal the
 eager single-stream ones bit for bit.
-    python tools/encoder_graph_step.py vit 16 [steps]"""
+    python tools/encoder_graph_step.py vit 16 [steps] [--image-size N] [--freeze]
+--image-size N (ViT): N x N frames with interpolate_pos_encoding on - the position table resampled to (N // 16)^2 patches.
+--freeze: the backbone frozen (forward, head backward, AdamW on the head) - the trainers' first frozen epoch, before the
+feature cache takes over.  One JSON line with the three step times and samples / s closes the output."""
+import argparse
+import json
 import os
 import sys
 import time
@@ -14,13 +19,18 @@ from eav_amd import synth, transformer as T  # noqa: E402
 from eav_amd.optim import CrossEntropyLoss, FusedAdam, unit_gradient  # noqa: E402
 
 
-def build(kind, B, dev, overlap, capturable):
+def build(kind, B, dev, overlap, capturable, image_size=None, freeze=False):
     torch.manual_seed(0)
     model = T.Encoder(T.make_config(kind)).to(dev).train()
     model.overlap_wgrad = overlap
-    x, y = (synth.mel_batch(5, B) if kind == "ast" else synth.frame_batch(5, B))
+    if image_size is not None:
+        model.interpolate_pos_encoding = True
+    if freeze:
+        for k, p in model.named_parameters():
+            p.requires_grad = k.startswith("classifier.")
+    x, y = (synth.mel_batch(5, B) if kind == "ast" else synth.frame_batch(5, B, image_size or 224))
     x, y = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
-    opt = FusedAdam(model.parameters(), lr=5e-6, weight_decay=0.01, decoupled=True, capturable=capturable)
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=5e-6, weight_decay=0.01, decoupled=True, capturable=capturable)
     crit = CrossEntropyLoss()
 
     def step():
@@ -42,22 +52,31 @@ def timeit(step, steps):
 
 
 def main():
-    kind, B = sys.argv[1], int(sys.argv[2])
-    steps = int(sys.argv[3]) if len(sys.argv) > 3 else 12
+    ap = argparse.ArgumentParser()
+    ap.add_argument("kind", choices=("ast", "vit"))
+    ap.add_argument("batch", type=int)
+    ap.add_argument("steps", type=int, nargs="?", default=12)
+    ap.add_argument("--image-size", type=int, default=None)
+    ap.add_argument("--freeze", action="store_true")
+    args = ap.parse_args()
+    if args.image_size is not None and args.kind != "vit":
+        ap.error("--image-size is a ViT option")
+    kind, B, steps = args.kind, args.batch, args.steps
     dev = torch.device("cuda", 0)
-    _, s2 = build(kind, B, dev, True, False)
+    geo = (args.image_size, args.freeze)
+    _, s2 = build(kind, B, dev, True, False, *geo)
     for _ in range(4):
         s2()
     t2 = timeit(s2, steps)
     del s2
     torch.cuda.empty_cache()
-    _, s1 = build(kind, B, dev, False, True)
+    _, s1 = build(kind, B, dev, False, True, *geo)
     ref = [float(s1()) for _ in range(4)]
     t1 = timeit(s1, steps)
     ref += [float(s1()) for _ in range(3)]
     del s1
     torch.cuda.empty_cache()
-    mg, sg = build(kind, B, dev, False, True)
+    mg, sg = build(kind, B, dev, False, True, *geo)
     got = [float(sg()) for _ in range(4)]
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
@@ -76,6 +95,10 @@ def main():
     print("  losses graph             :", [f"{v:.6f}" for v in got + after])
     ok = ref[:4] == got and ref[4:] == after
     print("  trajectories bit-equal:", ok)
+    best = min(t2, t1, tg)
+    print(json.dumps({"kind": kind, "batch": B, "image_size": args.image_size, "freeze": args.freeze,
+                      "eager_two_stream_ms": round(t2, 3), "eager_single_stream_ms": round(t1, 3),
+                      "graph_replay_ms": round(tg, 3), "samples_per_s": round(B / best * 1e3, 1), "bit_equal": ok}))
 
 
 if __name__ == "__main__":

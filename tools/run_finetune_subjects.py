@@ -3,6 +3,8 @@
 
     python tools/run_finetune_subjects.py audio  [--subjects 42] [--frozen-epochs 10] [--unfrozen-epochs 15]
     python tools/run_finetune_subjects.py vision [--subjects 42] [--frozen-epochs 10] [--unfrozen-epochs 5]
+    python tools/run_finetune_subjects.py vision --image-size 112     (frames resized to 112 x 112, not the processor's 224:
+                                                                       the ViT resamples its position table, 50 tokens)
     python tools/run_finetune_subjects.py audio --audio-root Datasets/EAV      (the dataset folder, Dataload_audio.py:87-93)
     python -m torch.distributed.run --nproc-per-node 8 tools/run_finetune_subjects.py audio ...
 
@@ -69,9 +71,13 @@ def main():
     ap.add_argument("--backend", default=os.environ.get("EAV_DIST_BACKEND"))
     ap.add_argument("--save-dir", default=None, help="write every fine-tuned subject model to DIR/subjectNN/ (HF directory: "
                     "config.json, model.safetensors, preprocessor_config.json when the source had one); off by default")
+    ap.add_argument("--image-size", type=int, default=None, help="vision only: train on N x N frames with "
+                    "interpolate_pos_encoding (ImageClassifierTrainer(image_size=N)); default: the processor's size")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     audio = args.kind == "audio"
+    if audio and args.image_size is not None:
+        ap.error("--image-size is a vision option")
     unfrozen = args.unfrozen_epochs if args.unfrozen_epochs is not None else (15 if audio else 5)
     if "EAV_FORCE_DEVICE" in os.environ:                      # several ranks on one GPU (logic runs on a 1-GPU box)
         os.environ["LOCAL_RANK"] = os.environ["EAV_FORCE_DEVICE"]
@@ -110,7 +116,7 @@ def main():
                                            weight_decay=1e-5, lr=0.005, batch_size=bsz)
                 else:
                     tr = ImageClassifierTrainer(data, model_path=path, sub=f"subject_{sub:02d}", num_labels=5, lr=5e-5,
-                                                batch_size=bsz)
+                                                batch_size=bsz, image_size=args.image_size)
                 if n > 1:
                     eav_dist.attach(tr, group=groups[sub])
                 tr.train(epochs=args.frozen_epochs, lr=5e-4, freeze=True)
