@@ -127,6 +127,8 @@ SIGNATURES = {
     "eav_embed_bwd": [_p, _p, _p, _i, _i, _i, _i, _p],
     "eav_pos_bicubic_fwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "eav_pos_bicubic_bwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p],
+    "eav_pos_time_fwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
+    "eav_pos_time_bwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p],
     "eav_token_rows": [_p, _p, _i, _i, _i, _i, _i, _p],
     "eav_pair_mean": [_p, _p, _i, _i, _i, _p],
     "eav_ast_fbank": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _d, _f, _f, _p],

@@ -11,9 +11,16 @@ ASTFeatureExtractor.  Kept quirks: `weight_decay` is accepted and ignored (Q10);
 (Q11); outputs_test only after the last unfrozen epoch (Q15); one line per epoch appended to
 training_performance_audio.txt in the cwd (Q17).  Beyond the reference: the keyword-only `problem_type`
 ("multi_label_classification" / "regression": fp32 label rows, BCE-with-logits / MSE, the epoch lines of
-finetune.FineTuneBase's docstring) and `save_pretrained(dir)`.
+finetune.FineTuneBase's docstring), `save_pretrained(dir)`, and the keyword-only `max_length`: None is the reference's
+behaviour (every clip padded to the checkpoint's 1024 frames, 1214 tokens); an int is the number of log-mel frames the clips
+are padded or truncated to; "auto" is the longest clip's own length (auto_max_length: 506 frames, 602 tokens for EAV's 5 s
+clips).  The front-end extracts that many frames and the AST runs with variable_length on - the checkpoint's position table
+fitted along time (transformer.Encoder, pos_time); `save_pretrained` then writes a stock HF AST of that length.
 """
 from __future__ import annotations
+
+import json
+import os
 
 import numpy as np
 import torch
@@ -21,31 +28,68 @@ import torch
 from .finetune import FineTuneBase, require_gpu
 
 
+def auto_max_length(n_samples, patch=16, tstride=10):
+    """The shortest admissible length for clips of up to n_samples samples at 16 kHz: the front-end's frame count
+    n = 1 + (n_samples - 400) // 160 (25 ms windows, 10 ms hop), rounded up to the next T' with (T' - patch) % tstride == 0,
+    so that the patch grid covers every frame and no padding beyond the last patch is carried."""
+    n = max(1 + (int(n_samples) - 400) // 160, patch)
+    return n + (-(n - patch)) % tstride
+
+
+def _longest_clip(x):
+    arr = np.asarray(x) if not isinstance(x, (list, tuple)) else None
+    if arr is not None and arr.dtype != object and arr.ndim == 2:
+        return arr.shape[1]
+    return max(len(w) for w in x)
+
+
 class AudioModelTrainer(FineTuneBase):
     def __init__(self, DATA, model_path, sub='', num_classes=5, weight_decay=1e-5, lr=0.001, batch_size=128, *,
-                 problem_type=None):
+                 problem_type=None, max_length=None):
         device = require_gpu("AudioModelTrainer")
         self.device = device
         self.tr, self.tr_y, self.te, self.te_y = DATA
+        self.max_length = self._resolve_max_length(max_length, model_path)      # refuses a bad length before any extraction
         self.tr_x, self.te_x = self._feature_extract(self.tr), self._feature_extract(self.te)
         self.sub, self.batch_size, self.problem_type = sub, batch_size, problem_type
         self.train_dataloader = self._prepare_dataloader(self.tr_x, self.tr_y, shuffle=True)
         self.test_dataloader = self._prepare_dataloader(self.te_x, self.te_y, shuffle=False)
         self._build(model_path, num_classes, lr, device, problem_type)          # :22-31
+        self.model.variable_length = self.max_length is not None
 
     def _prepare_dataloader(self, x, y, shuffle=False):
         return self._loader(x, y, shuffle)
 
+    def _resolve_max_length(self, max_length, model_path):
+        """None, or the frame count the clips are extracted at: an int as given, "auto" from the longest clip of train +
+        test; checked against the checkpoint's configuration (transformer.ast_length_geometry)."""
+        if max_length is None:
+            return None
+        from .transformer import ast_length_geometry, config_from_hf
+        cfg = config_from_hf(json.load(open(os.path.join(model_path, "config.json"))))
+        if isinstance(max_length, str):
+            if max_length != "auto":
+                raise ValueError(f'max_length must be None, an int or "auto", got {max_length!r}')
+            feats = [x for x in (self.tr, self.te) if isinstance(x, torch.Tensor) and x.dim() == 3]
+            if feats:                            # features extracted by the caller: their own length
+                max_length = max(int(x.shape[1]) for x in feats)
+            else:
+                max_length = auto_max_length(max(_longest_clip(self.tr), _longest_clip(self.te)), cfg.patch, cfg.sx)
+        elif not isinstance(max_length, (int, np.integer)) or isinstance(max_length, bool):
+            raise ValueError(f'max_length must be None, an int or "auto", got {max_length!r}')
+        return ast_length_geometry(cfg, int(max_length)).W
+
     def _feature_extract(self, x):
-        """:38-42 - log-mel features [N, 1024, 128]."""
+        """:38-42 - log-mel features [N, 1024, 128] ([N, max_length, 128] with the keyword)."""
         if isinstance(x, torch.Tensor) and x.dim() == 3:
             return x
+        T = {} if self.max_length is None else {"max_length": self.max_length}
         arr = np.asarray(x)
         if arr.ndim == 2 and arr.dtype != object and arr.shape[1] >= 400:
             from .preprocess import waveforms_to_input_values
-            return waveforms_to_input_values(arr, device=self.device).cpu()
+            return waveforms_to_input_values(arr, device=self.device, **T).cpu()
         from transformers import ASTFeatureExtractor
-        return ASTFeatureExtractor()(x, sampling_rate=16000, padding='max_length', return_tensors='pt')['input_values']
+        return ASTFeatureExtractor(**T)(x, sampling_rate=16000, padding='max_length', return_tensors='pt')['input_values']
 
     def train(self, epochs=20, lr=None, freeze=True):
         self._enter_phase(lr, freeze)

@@ -78,11 +78,21 @@ class FineTuneBase:
 
     def save_pretrained(self, save_directory):
         """The fine-tuned model as an HF directory (Encoder.save_pretrained), with the preprocessor_config.json of the
-        directory it was loaded from, if that had one."""
-        self.model.save_pretrained(save_directory)
+        directory it was loaded from, if that had one.  An audio trainer built with max_length saves a model of that
+        length (the position table fitted to it)."""
+        length = getattr(self, "max_length", None)
+        self.model.save_pretrained(save_directory, **({} if length is None else {"max_length": length}))
         src = os.path.join(self.model.source_dir or "", "preprocessor_config.json")
         if self.model.source_dir and os.path.exists(src):
-            shutil.copyfile(src, os.path.join(save_directory, "preprocessor_config.json"))
+            dst = os.path.join(save_directory, "preprocessor_config.json")
+            shutil.copyfile(src, dst)
+            if length is not None:              # the feature extractor of the saved model pads to the saved length
+                import json
+                pre = json.load(open(dst))
+                pre["max_length"] = int(length)
+                with open(dst, "w") as f:
+                    json.dump(pre, f, indent=2)
+                    f.write("\n")
 
     def _metric_text(self, value):
         """The new modes' replacement of the reference's "Accuracy: x%" (class docstring)."""

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, pos_interp
+from . import _lib, pos_interp, pos_time
 from .optim import HEAD_NARROW_CLASSES, BCEWithLogitsLoss, CrossEntropyLoss, MSELoss, flatten_parameters
 from .runtime import KernelFn, KernelModule, gather_batch
 from .weight_planes import SLOT, WeightPlanes
@@ -130,6 +130,28 @@ def interpolated_geometry(cfg, H, W):
     geo = SimpleNamespace(**vars(cfg))
     geo.H, geo.W, geo.ny, geo.nx, geo.npatch, geo.ntok = H, W, ny, nx, ny * nx, ny * nx + cfg.nextra
     geo.pos_grid = None if (ny * nx == g * g and H == W) else g
+    return geo
+
+
+def ast_length_geometry(cfg, T):
+    """The geometry of a forward of an AST `cfg` on clips of T frames with variable_length on (the AST twin of
+    interpolated_geometry): a copy of cfg whose W, nx, npatch and ntok are those of the input
+    (nx = (T - patch) // tstride + 1; ny, the mel side, is the checkpoint's), everything else unchanged, plus time_grid - the
+    number nx0 of time patches of the stored position table when that table has to be fitted to nx (pos_time: a centre cut for
+    nx < nx0, linear interpolation for nx > nx0), None when nx == nx0 and the stored table serves as it is.  Pure: needs no
+    device.  ValueError for a clip shorter than a patch, NotImplementedError beyond MAX_TOKENS tokens and for ViT (which has
+    interpolate_pos_encoding)."""
+    if cfg.kind != "ast":
+        raise NotImplementedError("variable_length exists for AST only (a ViT takes interpolate_pos_encoding)")
+    T = int(T)
+    if T < cfg.patch:
+        raise ValueError(f"variable_length: a clip of {T} frames holds no {cfg.patch}-frame patch")
+    nx = (T - cfg.patch) // cfg.sx + 1
+    if cfg.ny * nx + cfg.nextra > MAX_TOKENS:
+        raise NotImplementedError(f"at most {MAX_TOKENS} tokens: a clip of {T} frames gives {cfg.ny * nx + cfg.nextra}")
+    geo = SimpleNamespace(**vars(cfg))
+    geo.W, geo.nx, geo.npatch, geo.ntok = T, nx, cfg.ny * nx, cfg.ny * nx + cfg.nextra
+    geo.time_grid = None if nx == cfg.nx else cfg.nx
     return geo
 
 
@@ -376,6 +398,10 @@ class Encoder(KernelModule):
         # the forward, not to the model: _geo is that of the forward in flight (or of the one whose backward runs), cfg itself
         # - param_shapes, state_dict, save_pretrained - never changes.
         self.interpolate_pos_encoding = False
+        # AST: clips of any length from one patch up to MAX_TOKENS tokens, input_values [B, T', mel], the position table
+        # fitted along time (csrc/pos_time.hip; ast_length_geometry).  An attribute only: HF's AST forward has no such
+        # argument, and forward()'s parameter list is HF's.
+        self.variable_length = False
         self._active_geo = None       # None: the geometry of cfg
         if cfg.hidden % cfg.heads or (cfg.hidden // cfg.heads) % 4 or cfg.hidden % 4 or cfg.hidden > 1024:
             raise NotImplementedError("hidden size must be <= 1024, a multiple of 4, head_dim a multiple of 4")
@@ -407,20 +433,30 @@ class Encoder(KernelModule):
         model.source_dir = str(model_path)
         return model
 
-    def save_pretrained(self, save_directory):
+    def save_pretrained(self, save_directory, max_length=None):
         """The inverse of from_pretrained: config.json (config_to_hf) and model.safetensors - state_dict() as it stands,
         HF 5.x key names, fp32, read from the parameters (views of the flat buffer: current after any number of optimiser
         steps; the fp16 operand planes are never read).  Works for a CPU- or device-resident model; the Hugging Face
-        classes load the directory."""
+        classes load the directory.  max_length (AST, an int): config.json gets that max_length and the position table is
+        written fitted to it (pos_time.fit_time, on the host) - a stock HF AST of that length; None keeps the checkpoint's."""
         from safetensors.numpy import save_file
-        os.makedirs(save_directory, exist_ok=True)
         shapes = param_shapes(self.cfg)
+        hf = config_to_hf(self.cfg)
+        geo = None
+        if max_length is not None:
+            geo = ast_length_geometry(self.cfg, max_length)          # (refuses a ViT and an inadmissible length)
+            hf["max_length"] = geo.W
+        os.makedirs(save_directory, exist_ok=True)
         sd = self.state_dict()
         assert sorted(sd) == sorted(shapes), set(sd) ^ set(shapes)
         tensors = {k: np.ascontiguousarray(sd[k].detach().cpu().numpy().reshape(shapes[k])) for k in shapes}
+        if geo is not None and geo.time_grid is not None:
+            key = f"{self.cfg.prefix}.embeddings.position_embeddings"
+            fitted = pos_time.fit_time(tensors[key][0], geo.ny, geo.time_grid, geo.nx, geo.nextra)
+            tensors[key] = np.ascontiguousarray(fitted.astype(np.float32)[None])
         save_file(tensors, os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
         with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(config_to_hf(self.cfg), f, indent=2)
+            json.dump(hf, f, indent=2)
             f.write("\n")
 
     def reset_head(self, weight, bias):
@@ -484,7 +520,8 @@ class Encoder(KernelModule):
 
     @property
     def _geo(self):
-        """The geometry the launch functions read: cfg, or what interpolated_geometry derived for the forward in flight."""
+        """The geometry the launch functions read: cfg, or what interpolated_geometry / ast_length_geometry derived for the
+        forward in flight."""
         return self._active_geo if self._active_geo is not None else self.cfg
 
     def forward(self, x=None, labels=None, pixel_values=None, input_values=None, interpolate_pos_encoding=None):
@@ -492,7 +529,10 @@ class Encoder(KernelModule):
         self._require_gpu(x)
         c = self.cfg
         interp = self.interpolate_pos_encoding if interpolate_pos_encoding is None else bool(interpolate_pos_encoding)
+        varlen = bool(self.variable_length)
         geo = None
+        if varlen and c.kind != "ast":
+            raise NotImplementedError("variable_length exists for AST only (a ViT takes interpolate_pos_encoding)")
         if interp:
             if c.kind != "vit":
                 raise NotImplementedError("interpolate_pos_encoding exists for ViT only (HF's AST takes no such argument)")
@@ -503,6 +543,14 @@ class Encoder(KernelModule):
                 if self.training and self.dropout_active():
                     raise NotImplementedError("dropout at a non-native image size is not implemented (DESIGN.md section 11): "
                                               "the dropout sites are laid out for cfg.ntok tokens")
+        elif varlen:
+            if x.dim() != 3 or x.shape[2] != c.H:
+                raise ValueError(f"expected input [B,T,{c.H}], got {tuple(x.shape)}")
+            if x.shape[1] != c.W:                               # (the native length keeps cfg: today's launches, bit for bit)
+                geo = ast_length_geometry(c, x.shape[1])
+                if self.training and self.dropout_active():
+                    raise NotImplementedError("dropout at a non-native clip length is not implemented (DESIGN.md section "
+                                              "11): the dropout sites are laid out for cfg.ntok tokens")
         else:
             want = (c.W, c.H) if c.kind == "ast" else (c.C, c.H, c.W)
             if tuple(x.shape[1:]) != want:
@@ -656,7 +704,8 @@ class Encoder(KernelModule):
         ws = SimpleNamespace(B=B, M=M, ldn=ldn, full=full_backward, sp=sp)
         nsave = Lr if full_backward else 1
         ws.col = f(B * c.npatch, c.kp)
-        if getattr(c, "pos_grid", None) is not None:      # the position table resampled to this forward's patch grid
+        if getattr(c, "pos_grid", None) is not None or getattr(c, "time_grid", None) is not None:
+            # the position table resampled (ViT) / fitted along time (AST) to this forward's patch grid
             ws.pos_i = f(N, D)
             if full_backward:                             # ... and the gradient eav_embed_bwd leaves for that table
                 ws.dpos_i = f(N, D)
@@ -1069,6 +1118,11 @@ class Encoder(KernelModule):
         if g is not None:
             tb = pos_interp.device_tables(g, c.ny, c.nx, x.device)
             L("eav_pos_bicubic_fwd", pos, P(ws.pos_i), g, c.ny, c.nx, D, c.nextra, *[P(t) for t in tb["fwd"]], st)
+            pos = P(ws.pos_i)
+        nx0 = getattr(c, "time_grid", None)
+        if nx0 is not None:
+            tb = pos_time.device_tables(nx0, c.nx, x.device)
+            L("eav_pos_time_fwd", pos, P(ws.pos_i), c.ny, nx0, c.nx, D, c.nextra, *[P(t) for t in tb["fwd"]], st)
             pos = P(ws.pos_i)
         L("eav_embed_finish", P(h0), w(f"{pre}.embeddings.cls_token"),
           w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None, pos, B, N, D, c.nextra, st)
@@ -1582,8 +1636,15 @@ class Encoder(KernelModule):
             # ---- embeddings ("emb" dropout: dh is final here, so its gate runs in place)
             if drop.ph > 0.0:
                 self._drop_add(dh, None, dh, M * D, drop.ph, 0, "emb")
-            g = getattr(c, "pos_grid", None)
-            if g is None:
+            g, nx0 = getattr(c, "pos_grid", None), getattr(c, "time_grid", None)
+            if nx0 is not None:
+                # AST at another length: the fitted table's gradient, then the adjoint of the fit (rows 0 and 1, the cls and
+                # distillation positions, are copied - the token gradients below read the same values as ever)
+                L("eav_embed_bwd", dh, P(ws.dpos_i), P(ws.demb), B, N, D, c.nextra, st)
+                tb = pos_time.device_tables(nx0, c.nx, ws.dpos_i.device)
+                L("eav_pos_time_bwd", P(ws.dpos_i), gp(f"{pre}.embeddings.position_embeddings"), c.ny, nx0, c.nx, D,
+                  c.nextra, *[P(t) for t in tb["bwd"]], tb["nnz"], st)
+            elif g is None:
                 L("eav_embed_bwd", dh, gp(f"{pre}.embeddings.position_embeddings"), P(ws.demb), B, N, D, c.nextra, st)
             else:
                 # the gradient of the RESAMPLED table first; the stored table's is its image under the adjoint operator

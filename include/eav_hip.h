@@ -566,6 +566,19 @@ int eav_pos_bicubic_fwd(const float* pos, float* out, int g, int ny, int nx, int
 int eav_pos_bicubic_bwd(const float* dout, float* dpos, int g, int ny, int nx, int D, int nextra, const int* ypt,
                         const int* yidx, const float* yw, int nnzy, const int* xpt, const int* xidx, const float* xw,
                         int nnzx, void* stream);
+/* AST position table at another number of time patches: pos [nextra + ny*nx0, D] -> out [nextra + ny*nx, D], rows
+ * frequency-major (nextra + f*nx + t), the first nextra rows copied, out[f, t] = sum_a w[t][a] pos[f, idx[t][a]] with
+ * idx / w [nx][2] device arrays (eav_amd/pos_time.py: one tap of weight 1 for a centre cut, nx < nx0; the two taps of a
+ * linear interpolation, align_corners=False, for nx > nx0); the frequency axis is untouched.  A tap of weight 0 is skipped
+ * and the first term is a plain product, so a cut copies bit for bit.  eav_pos_time_bwd is the exact adjoint in gather
+ * form: dpos [nextra + ny*nx0, D] from dout [nextra + ny*nx, D], one workgroup per source row walking the transposed list -
+ * ptr [nx0 + 1] CSR row pointers, oidx the output time indices, w the weights, nnz their length (<= 2 nx) - in stored
+ * order: no atomics, the same bits on every run, every element of dpos written (zeros where no output reads the row).
+ * D % 4 == 0; pos / out / dout / dpos 16-byte aligned and distinct; ny, nx0, nx in 1 .. 2048; nextra <= 2. */
+int eav_pos_time_fwd(const float* pos, float* out, int ny, int nx0, int nx, int D, int nextra, const int* idx,
+                     const float* w, void* stream);
+int eav_pos_time_bwd(const float* dout, float* dpos, int ny, int nx0, int nx, int D, int nextra, const int* ptr,
+                     const int* oidx, const float* w, int nnz, void* stream);
 /* gather (scatter=0) / scatter (1) the first nextra token rows of every image: rows[b*nextra+e] <-> h[b,e]. */
 int eav_token_rows(float* h, float* rows, int B, int ntok, int D, int nextra, int scatter, void* stream);
 /* AST pooled = (cls + dist)/2 (HF AST :304); backward=1 writes dseq from dpooled. */

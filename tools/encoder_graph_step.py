@@ -3,7 +3,10 @@
 the single-stream step (forward, CE, backward, AdamW).  Prints ms per step and checks that the replayed losses equal the
 eager single-stream ones bit for bit.
     python tools/encoder_graph_step.py vit 16 [steps] [--image-size N] [--freeze]
+    python tools/encoder_graph_step.py ast 8 [steps] [--max-length N] [--freeze]
 --image-size N (ViT): N x N frames with interpolate_pos_encoding on - the position table resampled to (N // 16)^2 patches.
+--max-length N (AST): clips of N frames with variable_length on - the position table fitted to (N - 16) // 10 + 1 time patches
+(N = 1024: the flag on at the native length, the same launches as without it).
 --freeze: the backbone frozen (forward, head backward, AdamW on the head) - the trainers' first frozen epoch, before the
 feature cache takes over.  One JSON line with the three step times and samples / s closes the output."""
 import argparse
@@ -19,16 +22,18 @@ from eav_amd import synth, transformer as T  # noqa: E402
 from eav_amd.optim import CrossEntropyLoss, FusedAdam, unit_gradient  # noqa: E402
 
 
-def build(kind, B, dev, overlap, capturable, image_size=None, freeze=False):
+def build(kind, B, dev, overlap, capturable, image_size=None, freeze=False, max_length=None):
     torch.manual_seed(0)
     model = T.Encoder(T.make_config(kind)).to(dev).train()
     model.overlap_wgrad = overlap
     if image_size is not None:
         model.interpolate_pos_encoding = True
+    if max_length is not None:
+        model.variable_length = True
     if freeze:
         for k, p in model.named_parameters():
             p.requires_grad = k.startswith("classifier.")
-    x, y = (synth.mel_batch(5, B) if kind == "ast" else synth.frame_batch(5, B, image_size or 224))
+    x, y = (synth.mel_batch(5, B, max_length or 1024) if kind == "ast" else synth.frame_batch(5, B, image_size or 224))
     x, y = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
     opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=5e-6, weight_decay=0.01, decoupled=True, capturable=capturable)
     crit = CrossEntropyLoss()
@@ -57,13 +62,16 @@ def main():
     ap.add_argument("batch", type=int)
     ap.add_argument("steps", type=int, nargs="?", default=12)
     ap.add_argument("--image-size", type=int, default=None)
+    ap.add_argument("--max-length", type=int, default=None)
     ap.add_argument("--freeze", action="store_true")
     args = ap.parse_args()
     if args.image_size is not None and args.kind != "vit":
         ap.error("--image-size is a ViT option")
+    if args.max_length is not None and args.kind != "ast":
+        ap.error("--max-length is an AST option")
     kind, B, steps = args.kind, args.batch, args.steps
     dev = torch.device("cuda", 0)
-    geo = (args.image_size, args.freeze)
+    geo = (args.image_size, args.freeze, args.max_length)
     _, s2 = build(kind, B, dev, True, False, *geo)
     for _ in range(4):
         s2()
@@ -96,7 +104,7 @@ def main():
     ok = ref[:4] == got and ref[4:] == after
     print("  trajectories bit-equal:", ok)
     best = min(t2, t1, tg)
-    print(json.dumps({"kind": kind, "batch": B, "image_size": args.image_size, "freeze": args.freeze,
+    print(json.dumps({"kind": kind, "batch": B, "image_size": args.image_size, "max_length": args.max_length, "freeze": args.freeze,
                       "eager_two_stream_ms": round(t2, 3), "eager_single_stream_ms": round(t1, 3),
                       "graph_replay_ms": round(tg, 3), "samples_per_s": round(B / best * 1e3, 1), "bit_equal": ok}))
 

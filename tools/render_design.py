@@ -2,7 +2,8 @@
 """DESIGN.md = docs/DESIGN.md.in with its @PLACEHOLDERS@ filled from the measured files under profiles/:
     python tools/render_design.py r04
 reads profiles/<tag>_bench_detail.json (bench.py's detail record), profiles/<tag>_{eeg,ast,vit}[_serial]_kernel_stats.csv
-(rocprofv3 --kernel-trace --stats) and profiles/<tag>_fir_fft_bench.txt, so that every number in the document's
+(rocprofv3 --kernel-trace --stats), profiles/<tag>_fir_fft_bench.txt and the untagged records of single features
+(head_wide_bench.json, ast_length_step_times.json), so that every number in the document's
 current-state tables is one that a committed measurement file holds."""
 import csv
 import json
@@ -196,6 +197,22 @@ if os.path.exists(P("head_wide_bench.json")):
                     f"{h['w_read_plus_dw_written_bytes'] / 1e6:.1f} MB, {h['gbps']:.0f} GB/s | "
                     f"{100 * h['head_share_of_step']:.1f} % of {h['unfrozen_step']['ms']:.2f} ms ({h['unfrozen_step']['model']}) |")
     v["HEAD_WIDE_TABLE"] = "\n".join(rows)
+
+# AST at other clip lengths (tools/encoder_graph_step.py ast 8 --max-length N, profiles/ast_length_step_times.json)
+if os.path.exists(P("ast_length_step_times.json")):
+    al = json.load(open(P("ast_length_step_times.json")))
+    cell = {(r["config"], r["freeze"]): r for r in al["summary"]}
+    names = {"parent": "parent commit, 1024", "off": "attribute off, 1024", "1024": "attribute on, 1024", "512": "512", "506": "506"}
+    rows = ["  | frames | tokens per clip | unfrozen step: median (spread) | samples / s | frozen step (forward + head): median "
+            "(spread) | samples / s |", "  |---|---|---|---|---|---|"]
+    for key, name in names.items():
+        u, f = cell[(key, False)], cell[(key, True)]
+        tok = al["tokens_per_clip"].get(key, al["tokens_per_clip"]["1024"])
+        gain = lambda r, base: "" if key in ("parent", "off", "1024") else f" ({base['median_ms'] / r['median_ms']:.2f} x)"  # noqa: E731
+        rows.append(f"  | {name} | {fmt(tok)} | {u['median_ms']:.2f} ms ({u['spread_ms']:.2f}) | "
+                    f"{fmt(u['samples_per_s'])}{gain(u, cell[('off', False)])} | {f['median_ms']:.2f} ms ({f['spread_ms']:.2f}) | "
+                    f"{fmt(f['samples_per_s'])}{gain(f, cell[('off', True)])} |")
+    v["AST_LENGTH_TABLE"] = "\n".join(rows)
 
 src = open(os.path.join(ROOT, "docs", "DESIGN.md.in")).read()
 missing = sorted(set(re.findall(r"@([A-Z0-9_]+)@", src)) - set(v))

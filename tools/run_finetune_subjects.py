@@ -5,6 +5,8 @@
     python tools/run_finetune_subjects.py vision [--subjects 42] [--frozen-epochs 10] [--unfrozen-epochs 5]
     python tools/run_finetune_subjects.py vision --image-size 112     (frames resized to 112 x 112, not the processor's 224:
                                                                        the ViT resamples its position table, 50 tokens)
+    python tools/run_finetune_subjects.py audio --max-length auto     (clips at their own length, not padded to 1024 frames:
+                                                                       5 s -> 506 frames, 602 tokens instead of 1214)
     python tools/run_finetune_subjects.py audio --audio-root Datasets/EAV      (the dataset folder, Dataload_audio.py:87-93)
     python -m torch.distributed.run --nproc-per-node 8 tools/run_finetune_subjects.py audio ...
 
@@ -73,11 +75,16 @@ def main():
                     "config.json, model.safetensors, preprocessor_config.json when the source had one); off by default")
     ap.add_argument("--image-size", type=int, default=None, help="vision only: train on N x N frames with "
                     "interpolate_pos_encoding (ImageClassifierTrainer(image_size=N)); default: the processor's size")
+    ap.add_argument("--max-length", default=None, help="audio only: N frames or 'auto' (the longest clip's own length) instead "
+                    "of the checkpoint's 1024 (AudioModelTrainer(max_length=...)); default: the checkpoint's")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     audio = args.kind == "audio"
     if audio and args.image_size is not None:
         ap.error("--image-size is a vision option")
+    if not audio and args.max_length is not None:
+        ap.error("--max-length is an audio option")
+    max_length = args.max_length if args.max_length in (None, "auto") else int(args.max_length)
     unfrozen = args.unfrozen_epochs if args.unfrozen_epochs is not None else (15 if audio else 5)
     if "EAV_FORCE_DEVICE" in os.environ:                      # several ranks on one GPU (logic runs on a 1-GPU box)
         os.environ["LOCAL_RANK"] = os.environ["EAV_FORCE_DEVICE"]
@@ -113,7 +120,7 @@ def main():
             with contextlib.redirect_stdout(sys.stdout if args.verbose else io.StringIO()):
                 if audio:
                     tr = AudioModelTrainer(data, model_path=path, sub=f"subject_{sub:02d}", num_classes=5,
-                                           weight_decay=1e-5, lr=0.005, batch_size=bsz)
+                                           weight_decay=1e-5, lr=0.005, batch_size=bsz, max_length=max_length)
                 else:
                     tr = ImageClassifierTrainer(data, model_path=path, sub=f"subject_{sub:02d}", num_labels=5, lr=5e-5,
                                                 batch_size=bsz, image_size=args.image_size)
