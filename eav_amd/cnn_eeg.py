@@ -123,13 +123,14 @@ class EEGNet(KernelModule):
         self._bn_finalize(self.block2[2], ws.part_c, ws.np_c, B * ws.T2, ws.bn3, training)
         L("eav_bn_elu_pool_fwd", P(ws.z3), P(ws.bn3), P(ws.a3), B, F2, ws.T2, 8, *drop2, st)
         L("eav_dense_softmax_fwd", P(ws.a3), P(wc), P(bc), P(ws.logits), None, B, ws.NF, self.nb_classes, st)
-        self._saved = (self._token, x, training, drop1, drop2, mk, ws)      # (mk keeps explicit masks alive)
+        self._saved = eegnet_canon.Saved(self._token, x, training, drop1, drop2, mk, ws)
         return self._token
 
     def _launch_backward(self, dlogits, token):
         self._check_token(token)
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
-        _, x, training, drop1, drop2, _, ws = self._saved
+        s = self._saved
+        x, training, drop1, drop2, ws = s.x, s.training, s.drop1, s.drop2, s.ws
         B, K2, F2, C2, T2 = x.shape[0], self.K2, self.F2, self.F1 * self.D, ws.T2
         g = self._grad_views()
         _, _, _, wd, _, _, wdw, wp, _, _, wc, _ = self._params()

@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from . import _lib
 from .optim import CrossEntropyLoss, FusedAdam
-from .runtime import DeviceLoader, KernelFn, KernelModule, eager_step
+from .runtime import (BN_M1, BN_M2, BN_SCALE, BN_SHIFT, DeviceLoader, KernelFn, KernelModule, bn_field,
+                      eager_step)
 
 NCMAX = 16                  # classes the head kernels take (eav_dense_softmax_*)
 FEAT = 2048
@@ -282,12 +283,13 @@ class VideoModel(KernelModule):
 
     def _bn_apply(self, u, dst, relu=1, res=None, ures=None):
         L, P, st, ws = _lib.call, _lib.ptr, _lib.stream_ptr(), self._ws
-        C, base = u.Co, ws.bn[id(u)].data_ptr()
+        C, bn = u.Co, ws.bn[id(u)]
         rsc = rsh = None
         if ures is not None:
-            rb = ws.bn[id(ures)].data_ptr()
-            rsc, rsh = rb + 8 * C, rb + 12 * C
-        L("eav_video_bn_apply", P(ws.c[id(u)]), base + 8 * C, base + 12 * C, P(res), rsc, rsh, P(dst), u.M, C, relu, st)
+            rbn = ws.bn[id(ures)]
+            rsc, rsh = bn_field(rbn, C, BN_SCALE), bn_field(rbn, C, BN_SHIFT)
+        L("eav_video_bn_apply", P(ws.c[id(u)]), bn_field(bn, C, BN_SCALE), bn_field(bn, C, BN_SHIFT), P(res), rsc, rsh,
+          P(dst), u.M, C, relu, st)
 
     def _launch_forward(self, x):
         L, P, st = _lib.call, _lib.ptr, _lib.stream_ptr()
@@ -353,11 +355,12 @@ class VideoModel(KernelModule):
     def _bn_bwd(self, u, dy, gate, gbuf, dx, training):
         """dy -> (gate) -> BN backward: writes g (when gated) to gbuf, dgamma / dbeta, and dx = d conv output."""
         L, P, st, ws = _lib.call, _lib.ptr, _lib.stream_ptr(), self._ws
-        C, base = u.Co, ws.bn[id(u)].data_ptr()
+        C, bn = u.Co, ws.bn[id(u)]
+        base = bn.data_ptr()
         L("eav_video_bn_bwd", P(dy), P(gate), P(ws.c[id(u)]), base, P(gbuf) if gate is not None else None, P(ws.stat),
           u.M, C, st)
         L("eav_bn_bwd_finalize", P(ws.stat), _lib.plain("eav_video_bn_nparts", u.M), C, float(u.M), int(training),
-          P(self._grad_of(u.bn.weight)), P(self._grad_of(u.bn.bias)), base + 16 * C, base + 20 * C, st)
+          P(self._grad_of(u.bn.weight)), P(self._grad_of(u.bn.bias)), bn_field(bn, C, BN_M1), bn_field(bn, C, BN_M2), st)
         L("eav_bn_rows_bwd", P(gbuf if gate is not None else dy), P(ws.c[id(u)]), base, P(dx), u.M, C, st)
 
     def _conv_bwd(self, u, dc, act, din, add=None, accumulate=0, nchw=0):

@@ -10,9 +10,24 @@ the first BatchNorm, cnn_eeg.EEGNet has none); `dropout` = (rate, seed, mask poi
 """
 from __future__ import annotations
 
+from typing import Any, Callable, NamedTuple, Optional
+
 import torch
 
 from . import _lib
+from .runtime import BN_M1, BN_M2, bn_field
+
+
+class Saved(NamedTuple):
+    """What a forward of either EEGNet keeps for its backward (KernelModule._saved: the token first)."""
+    token: int
+    x: Any                      # the input: a tensor [B,1,Chans,Samples] (EEGNet_tor's fast path: or an IndexedBatch)
+    training: bool
+    drop1: tuple                # (rate, seed, mask pointer, counter pointer) of block 1's dropout
+    drop2: tuple                # ... of block 2's
+    mk: Callable                # keeps explicit masks alive
+    ws: Any                     # the workspace of this forward
+    probs: Optional[torch.Tensor] = None     # EEGNet_tor: the probabilities it returned
 
 
 class Workspace:
@@ -62,6 +77,6 @@ def block1_backward(m, ws, x, w2, grads, elu, training, dropout):
     L("eav_spatial_bwd", P(ws.y1), P(ws.dz2), b1, P(w2), P(ws.g1), P(ws.part_sst), P(ws.part_sw), B, C, S, F1, D, elu, st)
     L("eav_reduce_partials", P(ws.part_sw), ws.np_s, C2 * C, C2 * C, 1.0, P(gw2), st)
     L("eav_bn_bwd_finalize", P(ws.part_sst), ws.np_s, F1, float(B * C * S), int(training), P(gbn1w), P(gbn1b),
-      b1 + 16 * F1, b1 + 20 * F1, st)
+      bn_field(ws.bn1, F1, BN_M1), bn_field(ws.bn1, F1, BN_M2), st)
     L("eav_tconv_wgrad", P(x), P(ws.y1), P(ws.g1), b1, P(ws.part_tw), B, C, S, F1, K, st)
     L("eav_reduce_partials", P(ws.part_tw), ws.np_tw, F1 * K, F1 * K, 1.0, P(gw1), st)

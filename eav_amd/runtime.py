@@ -18,6 +18,15 @@ import torch.nn as nn
 from . import _lib
 from .optim import flatten_parameters, unit_gradient
 
+# A BatchNorm parameter block of n channels: six fields of n floats each, in the order the kernels take them
+# (include/eav_hip.h: "mean, invstd, scale, shift, m1, m2"; m1 / m2 are the two means of the backward).
+BN_MEAN, BN_INVSTD, BN_SCALE, BN_SHIFT, BN_M1, BN_M2 = range(6)
+
+
+def bn_field(buf, n, k):
+    """Device address of field k (BN_*) of the n-channel BatchNorm parameter block `buf`."""
+    return buf.data_ptr() + 4 * n * k
+
 
 def cached_workspace(cache, key, make, keep_unpinned=2):
     """Workspace cache of a KernelModule.  A captured hipGraph (GraphStep) has the raw device pointers of the
@@ -144,20 +153,21 @@ class KernelModule(nn.Module):
     def _bn_finalize(self, bn, part, nparts, count, buf, training):
         """Partial sums of `count` values per channel -> mean, invstd, scale, shift in buf[0:4n] and bn's running statistics
         (eval mode: scale / shift from the running statistics).  num_batches_tracked is the caller's."""
-        b0, n = _lib.ptr(buf), bn.num_features
+        n = bn.num_features
         _lib.call("eav_bn_finalize", _lib.ptr(part), nparts, n, float(count), _lib.ptr(bn.weight), _lib.ptr(bn.bias),
                   _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), int(training), float(bn.momentum), float(bn.eps),
-                  b0, b0 + 4 * n, b0 + 8 * n, b0 + 12 * n, _lib.stream_ptr())
+                  *(bn_field(buf, n, k) for k in (BN_MEAN, BN_INVSTD, BN_SCALE, BN_SHIFT)), _lib.stream_ptr())
 
     def _bn_elu_pool_bwd(self, dy, z, dz, buf, part, gw, gb, B, nch, T, pool, dropout, training):
         """Backward of z [B,nch,T] -> BatchNorm (buf) -> ELU -> AvgPool(pool) -> Dropout from dy: BatchNorm's gradients to
         gw / gb, its two backward means to buf[4n:6n], d z to dz.  dropout = (rate, seed, mask pointer, counter pointer) of
         the forward; dz = None stops after the means (the next kernel forms d z itself)."""
         L, P, st, b = _lib.call, _lib.ptr, _lib.stream_ptr(), _lib.ptr(buf)
+        m1, m2 = bn_field(buf, nch, BN_M1), bn_field(buf, nch, BN_M2)
         L("eav_bn_elu_pool_bwd_reduce", P(dy), P(z), b, P(part), B, nch, T, pool, *dropout, st)
-        L("eav_bn_bwd_finalize", P(part), B, nch, float(B * T), int(training), P(gw), P(gb), b + 16 * nch, b + 20 * nch, st)
+        L("eav_bn_bwd_finalize", P(part), B, nch, float(B * T), int(training), P(gw), P(gb), m1, m2, st)
         if dz is not None:
-            L("eav_bn_elu_pool_bwd_apply", P(dy), P(z), b, b + 16 * nch, P(dz), B, nch, T, pool, *dropout, st)
+            L("eav_bn_elu_pool_bwd_apply", P(dy), P(z), b, m1, P(dz), B, nch, T, pool, *dropout, st)
 
     # ------------------------------------------------------------------ checks
     def _require_gpu(self, x):

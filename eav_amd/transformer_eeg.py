@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import _lib
 from .optim import CrossEntropyLoss, FusedAdam
-from .runtime import DeviceLoader, KernelFn, KernelModule, train_step
+from .runtime import BN_M1, BN_M2, DeviceLoader, KernelFn, KernelModule, bn_field, train_step
 
 NF, KC, POOL, STRIDE, HD = 40, 13, 35, 7, 64     # filters / conv taps / pool window / pool stride / attention tile
 SLOT = 4128                                      # floats per operand-scale slot (EAV_SP_SLOT, include/eav_hip.h)
@@ -271,7 +271,7 @@ class ShallowConvNet(KernelModule):
         L("eav_sqpool_log_bwd", P(ws.dfeat), P(ws.pooled), hl, b0, P(ws.g), P(ws.part_bn), B, T, NF, 65, POOL, STRIDE,
           1e-7, 1e4, drop, self._seed(self.num_layers, 0), mk(3 * self.num_layers), cnt, st)
         L("eav_bn_bwd_finalize", P(ws.part_bn), B, NF, float(M), int(training), gp("bn.weight"), gp("bn.bias"),
-          b0 + 16 * NF, b0 + 20 * NF, st)
+          bn_field(ws.bn, NF, BN_M1), bn_field(ws.bn, NF, BN_M2), st)
         L("eav_bn_rows_bwd", P(ws.g), hl, b0, dh, M, NF, st)
         for l in reversed(range(self.num_layers)):
             p = f"transformer.{l}."

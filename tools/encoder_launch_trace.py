@@ -4,20 +4,14 @@ step (a refactor of the host code): run it on both with the same built library (
     python tools/encoder_launch_trace.py out.json
 Every configuration trains for two steps (B = 3, torch.manual_seed(0), FusedAdam).  Per configuration the JSON holds `step`,
 the ordered launches of the second step, and `sha256` of that step's logits and loss, of its gradients and of the parameters
-after its optimiser step (one digest over every gradient / every parameter, in named_parameters() order).  A launch is
-(entry point, scalar arguments) - None kept, an integer >= 2^32 (device addresses, stream handles, 64-bit seeds) written as
-"P", every other integer and float as it is; the configurations share most of theirs, so the file holds every distinct launch
-once, in `launches` in the order of first use, and `step` lists indices into it.  Only the public surface of the package is
-used."""
-import hashlib
-import json
-import os
+after its optimiser step (one digest over every gradient / every parameter, in named_parameters() order); launch_trace.py has
+the recorder and the file format.  Only the public surface of the package is used."""
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import torch
 
-from eav_amd import _lib, synth, transformer as T  # noqa: E402
+from launch_trace import digest, recording, write      # (puts the repository root on sys.path)
+from eav_amd import synth, transformer as T  # noqa: E402
 from eav_amd.optim import CrossEntropyLoss, FusedAdam  # noqa: E402
 
 B = 3
@@ -52,20 +46,6 @@ def configurations():
     return out
 
 
-def scalar(a):
-    if a is None or isinstance(a, float):
-        return a
-    a = int(a)
-    return "P" if a >= 1 << 32 else a
-
-
-def digest(*tensors):
-    h = hashlib.sha256()
-    for t in tensors:
-        h.update(t.detach().float().cpu().contiguous().numpy().tobytes())
-    return h.hexdigest()
-
-
 def run(kind, cfg_args, attrs, frozen, size, dev):
     torch.manual_seed(0)
     model = T.Encoder(T.make_config(kind, **cfg_args)).to(dev).train()
@@ -84,16 +64,9 @@ def run(kind, cfg_args, attrs, frozen, size, dev):
     x, y = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
     opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=5e-6, weight_decay=0.01, decoupled=True)
     crit = CrossEntropyLoss()
-    launches, orig = [], _lib.call
-
-    def recording(name, *a):
-        launches.append([name, [scalar(v) for v in a]])
-        return orig(name, *a)
-
+    launches = []
     for step in range(2):
-        if step == 1:
-            _lib.call = recording
-        try:
+        with recording(launches, on=step == 1):
             opt.zero_grad()
             logits = model(x).logits
             loss = crit(logits, y)
@@ -102,21 +75,9 @@ def run(kind, cfg_args, attrs, frozen, size, dev):
                 sha = {"logits": digest(logits), "loss": digest(loss),
                        "gradients": digest(*[p.grad for p in model.parameters() if p.grad is not None])}
             opt.step()
-        finally:
-            _lib.call = orig
     torch.cuda.synchronize()
     sha["parameters"] = digest(*model.parameters())
     return {"launches": launches, "sha256": sha}
-
-
-def encode(result):
-    """The JSON text of {configuration: {"launches", "sha256"}}: one distinct launch per line, one configuration per line."""
-    dumps = lambda v: json.dumps(v, separators=(",", ":"))  # noqa: E731
-    index = {}
-    steps = {name: [index.setdefault(dumps(launch), len(index)) for launch in r["launches"]] for name, r in result.items()}
-    return ('{"launches":[\n' + ",\n".join(index) + '],\n"configurations":{\n'
-            + ",\n".join(f'{dumps(name)}:{{"sha256":{dumps(r["sha256"])},"step":{dumps(steps[name])}}}'
-                          for name, r in result.items()) + "}}\n")
 
 
 def main():
@@ -126,9 +87,7 @@ def main():
     for name, kind, cfg_args, attrs, frozen, size in configurations():
         result[name] = run(kind, cfg_args, attrs, frozen, size, dev)
         print(f"{name}: {len(result[name]['launches'])} launches", flush=True)
-    with open(out_path, "w") as f:
-        f.write(encode(result))
-    print(f"{len(result)} configurations -> {out_path}")
+    write(result, out_path)
 
 
 if __name__ == "__main__":

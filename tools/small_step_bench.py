@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Step time of EEGNet at the reference's own shape (B=32, [32,1,30,500]): launch-bound regime."""
+"""Step time of EEGNet, eager and replayed from a hipGraph; by default at the reference's own shape (B=32, [32,1,30,500]): the
+launch-bound regime.
+    python tools/small_step_bench.py [B=32] [Samples=500] [steps=300]"""
 import os
 import sys
 import time
@@ -11,7 +13,7 @@ from eav_amd import synth  # noqa: E402
 from eav_amd.eegnet import EEGNet_tor  # noqa: E402
 from eav_amd.optim import CrossEntropyLoss, FusedAdam  # noqa: E402
 
-B, S = 32, 500
+B, S, n = (int(v) for v in (sys.argv[1:4] + ["32", "500", "300"][len(sys.argv) - 1:]))
 x, y = synth.eeg_batch(1, B, 30, S)
 x, y = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
 model = EEGNet_tor(5, Samples=S).cuda().train()
@@ -30,7 +32,6 @@ for _ in range(20):
     step()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-n = 300
 for _ in range(n):
     step()
 torch.cuda.synchronize()
