@@ -1,6 +1,7 @@
 """Checking helpers shared by the kernel-level GPU tests (test_audio_cnn_kernels_gpu.py, test_eegnet_canon_kernels_gpu.py,
-test_shallow_tf_kernels_gpu.py): sentinel-filled output buffers with a guard band, deterministic data, and the two
-comparisons - bit equality and an element-wise bound.
+test_shallow_tf_kernels_gpu.py, test_encoder_dropout_kernels_gpu.py): sentinel-filled output buffers with a guard band,
+deterministic data, and the two comparisons - bit equality and an element-wise bound; and the operand preparation of the
+split attention kernels (attn_prep, decode_planes: shared with test_split_kernels_gpu.py).
 
 Every output is filled with a NaN sentinel (payload 0x7fc0dead; 0xFF for uint8) and carries a guard band past its end:
 everything the contract says is written must be overwritten, the guard band must be untouched."""
@@ -68,6 +69,32 @@ def normal(seed, shape, std=1.0):
 
 def keep_mask(seed, shape, p):
     return torch.from_numpy((synth.uniform(seed, shape) >= p).astype(np.uint8))
+
+
+SLOT = 4128                 # floats of one scale slot of the split-operand kernels
+
+
+def attn_prep(x, B, N, ncols, secw, tmask):
+    """fp32 [B*N, ncols] on the device -> (scale slot, row planes, T planes) of the split attention kernels (eav_attn_sp_prep)."""
+    from eav_amd import _lib
+    Npad = _lib.plain("eav_attn_sp_npad", N)
+    slot = torch.zeros(SLOT, device="cuda")
+    _lib.call("eav_sp_absmax", ptr(x), B * N, ncols, ncols, ptr(slot), None)
+    rowp = torch.empty(B * N, 2 * ncols, dtype=torch.float16, device="cuda")
+    tp = torch.empty(B, ncols // 64, 64, 2 * Npad, dtype=torch.float16, device="cuda")
+    _lib.call("eav_attn_sp_prep", ptr(x), ptr(slot), ptr(rowp), ptr(tp), B, N, ncols, secw, tmask, None)
+    return slot, rowp, tp
+
+
+def decode_planes(pl, R, C, sigma):
+    """planes [Rp, 2*Cp] f16 ([R][Cp/8][2][8]) -> fp64 [R, C]: (hi + lo 2^-11) / sigma"""
+    v = pl[:R].view(R, -1, 2, 8).double()
+    return ((v[:, :, 0, :] + v[:, :, 1, :] / 2048.0).reshape(R, -1)[:, :C]) / sigma
+
+
+def slot_max(slot):
+    """The maximum a kernel published in a scale slot's shard words (non-negative floats: compared as integers)."""
+    return float(slot[:2048:32].view(torch.int32).max().view(torch.float32))
 
 
 def assert_exact(bound, quantum, what):

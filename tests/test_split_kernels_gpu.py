@@ -7,10 +7,10 @@ import pytest
 import torch
 
 from eav_amd import _lib
+from tests.kernel_check import SLOT, attn_prep as _attn_prep, decode_planes
 
 pytestmark = pytest.mark.gpu
 P = _lib.ptr
-SLOT = 4128
 
 
 def kpad(k):
@@ -228,16 +228,6 @@ def _attn_ref(qkv, dO, B, H, N):
     return out.detach(), x.grad.permute(1, 3, 0, 2, 4).reshape(B * N, 3 * D), torch.logsumexp(s, -1).reshape(B * H, N).detach()
 
 
-def _attn_prep(x, B, N, ncols, secw, tmask):
-    Npad = _lib.plain("eav_attn_sp_npad", N)
-    slot = torch.zeros(SLOT, device="cuda")
-    _lib.call("eav_sp_absmax", P(x), B * N, ncols, ncols, P(slot), None)
-    rowp = torch.empty(B * N, 2 * ncols, dtype=torch.float16, device="cuda")
-    tp = torch.empty(B, ncols // 64, 64, 2 * Npad, dtype=torch.float16, device="cuda")
-    _lib.call("eav_attn_sp_prep", P(x), P(slot), P(rowp), P(tp), B, N, ncols, secw, tmask, None)
-    return slot, rowp, tp
-
-
 # (3, 4, .) / (3, 3, .): 12 / 9 image-heads = one full group of 8 on the XCD-aware workgroup map plus a remainder;
 # N = 128 / 129: either side of the 64-row / 128-row workgroup switch
 @pytest.mark.parametrize("cfg", [(1, 2, 64, 1.0, False), (2, 3, 197, 1.0, False), (1, 2, 1214, 1.0, False),
@@ -409,12 +399,6 @@ def test_pre_activation_only_epilogue_and_gelu_conversion():
     assert torch.equal(pre3, pre1)
     assert float(s3[:2048:32].view(torch.int32).max()) == float(s1[:2048:32].view(torch.int32).max())
     assert torch.equal(p3.view(torch.int16), p1.view(torch.int16)) and torch.equal(p3T.view(torch.int16), p1T.view(torch.int16))
-
-
-def decode_planes(pl, R, C, sigma):
-    """planes [Rp, 2*Cp] f16 ([R][Cp/8][2][8]) -> fp64 [R, C]: (hi + lo 2^-11) / sigma"""
-    v = pl[:R].view(R, -1, 2, 8).double()
-    return ((v[:, :, 0, :] + v[:, :, 1, :] / 2048.0).reshape(R, -1)[:, :C]) / sigma
 
 
 @pytest.mark.parametrize("M,D", [(37, 64), (1214, 768), (300, 1024), (70, 8)])
