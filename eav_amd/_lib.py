@@ -68,6 +68,11 @@ SIGNATURES = {
     "eav_mse_fwd_bwd": [_p, _p, _p, _p, _p, _i, _i, _p],
     "eav_scale_by_scalar": [_p, _p, _i64, _p],
     "eav_adam_step": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _i, _p, _p],
+    "eav_adam_step_scaled": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _i, _p, _p, _p],
+    "eav_grad_sumsq": [_p, _i, _i64, _p, _p],
+    "eav_grad_fold": [_p, _p, _i, _i64, _p, _i, _p, _p],
+    "eav_grad_clip_finish": [_p, _i64, _f, _p, _p],
+    "eav_scale_ranges": [_p, _i, _i64, _p, _p],
     "eav_counter_inc": [_p, _p],
     "eav_counter_inc4": [_p, _p, _p, _p, _p],
     "eav_step_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
@@ -205,6 +210,8 @@ PLAIN = {
     "eav_dense_wide_bwd_ws_floats": ([_i, _i, _i], _i64),
     "eav_ce_wide_ws_floats": ([_i], _i64),
     "eav_head_loss_ws_floats": ([_i], _i64),
+    "eav_grad_chunk_elems": ([], _i64),
+    "eav_grad_nchunks": ([_i64], _i64),
     "eav_layernorm_bwd_nparts": ([_i], _i),
     "eav_gemm_f32_splitk_plan": ([_i, _i, _i], _i),
     "eav_colsum_nparts": ([_i], _i),

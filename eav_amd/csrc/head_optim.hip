@@ -208,11 +208,17 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ in, c
 // torch.optim.Adam / AdamW (foreach/fused semantics, fp32 state):
 //   adamw: p *= 1 - lr*wd;  adam: g += wd*p
 //   m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// SCALED (eav_adam_step_scaled): the gradient is g * *gscale (the clipping coefficient of eav_grad_clip_finish, a device
+// scalar), rounded to fp32 before anything else uses it - the update is the one a gradient tensor scaled beforehand gets.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
                                                    float b1, float b2, float eps, float wd, float bc1,
                                                    float bc2_sqrt, int decoupled,
-                                                   const int64_t* __restrict__ step_dev) {
+                                                   const int64_t* __restrict__ step_dev,
+                                                   const float* __restrict__ gscale) {
+  float gs = 1.f;
+  if (SCALED) gs = *gscale;
   if (step_dev) {  // capturable: bias corrections from a device-resident step count
     const double st = (double)*step_dev;
     bc1 = (float)(1.0 - pow((double)b1, st));
@@ -221,6 +227,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     float pv = p[i], gv = g[i];
+    if (SCALED) {
+      gv *= gs;
+      asm volatile("" : "+v"(gv));      // the rounded product is a value of its own: never one half of a later fma
+    }
     if (wd != 0.f) {
       if (decoupled) pv *= 1.f - lr * wd; else gv += wd * pv;
     }
@@ -283,19 +293,38 @@ extern "C" int eav_scale_by_scalar(float* v, const float* scalar, int64_t n, voi
   return EAV_OK;
 }
 
-extern "C" int eav_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
-                             float beta2, float eps, float weight_decay, int64_t step, int decoupled,
-                             const int64_t* step_dev, void* stream) {
-  EAV_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || step_dev), "eav_adam_step: bad arguments");
+static int adam_launch(const char* who, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, int64_t step, int decoupled, const int64_t* step_dev,
+                       const float* gscale, void* stream) {
   if (step < 1) step = 1;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   int64_t blocks = cdiv64(n, 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(adam_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), decoupled, step_dev);
-  EAV_CHECK_LAUNCH("eav_adam_step");
+  if (gscale)
+    hipLaunchKernelGGL(adam_kernel<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
+                       beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), decoupled, step_dev, gscale);
+  else
+    hipLaunchKernelGGL(adam_kernel<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
+                       beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), decoupled, step_dev, gscale);
+  EAV_CHECK_LAUNCH(who);
   return EAV_OK;
+}
+
+extern "C" int eav_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, int64_t step, int decoupled,
+                             const int64_t* step_dev, void* stream) {
+  EAV_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || step_dev), "eav_adam_step: bad arguments");
+  return adam_launch("eav_adam_step", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, decoupled, step_dev,
+                     nullptr, stream);
+}
+
+extern "C" int eav_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                                    float beta2, float eps, float weight_decay, int64_t step, int decoupled,
+                                    const int64_t* step_dev, const float* gscale, void* stream) {
+  EAV_REQUIRE(p && g && m && v && gscale && n > 0 && (step >= 1 || step_dev), "eav_adam_step_scaled: bad arguments");
+  return adam_launch("eav_adam_step_scaled", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, decoupled,
+                     step_dev, gscale, stream);
 }
 
 __global__ void counter_inc_kernel(int64_t* p) { *p += 1; }

@@ -45,6 +45,15 @@ class FineTuneBase:
 
     problem_type = None
 
+    # Training-loop options, set between construction and train() like `cache_frozen_features` (the constructors keep
+    # the reference's parameter lists):
+    #   max_grad_norm                 None (the reference: no clipping) or the bound of the gradients' global L2 norm, HF
+    #                                 Trainer's option of that name - FusedAdam(max_grad_norm=...), inside the step
+    #   gradient_accumulation_steps   k >= 1: one optimiser step per k consecutive micro-batches of `batch_size`
+    #                                 (_train_one_epoch); the effective batch is k * batch_size
+    max_grad_norm = None
+    gradient_accumulation_steps = 1
+
     def _build(self, model_path, n_classes, lr, device, problem_type=None):
         """The reference's order (Transformer_Audio.py:22-24, Transformer_Vision.py:29-30): load the checkpoint with the
         head its config.json describes - 527 AudioSet or 1000 ImageNet classes for the stock downloads - then replace
@@ -115,6 +124,7 @@ class FineTuneBase:
         lr = self.initial_lr if lr is None else lr
         for group in self.optimizer.param_groups:
             group['lr'] = lr
+        self.optimizer.max_grad_norm = self.max_grad_norm
         trainable_head = {id(p) for p in self.model.classifier.parameters()}
         for p in self.model.parameters():
             p.requires_grad = (not freeze) or (id(p) in trainable_head)
@@ -155,7 +165,21 @@ class FineTuneBase:
 
     def _train_one_epoch(self, after_batch=None):
         """Returns (#correct on device, #seen).  One optimiser step per batch; nothing is read back per step.
-        Multi-label: (#element hits, #elements); regression: (squared-error sum, #elements)."""
+        Multi-label: (#element hits, #elements); regression: (squared-error sum, #elements).
+
+        gradient_accumulation_steps = k > 1: the loader's batches are taken in groups of k consecutive micro-batches and
+        ONE optimiser step is made per group.  Micro-batch j is folded into the optimiser's accumulator with weight
+        len(batch j) / (samples of the group), so the update of a group is that of one batch holding the group's
+        samples - the ragged last group included (a last group of one micro-batch has weight 1).  The weights count
+        SAMPLES, not valid labels: with ignore_index (-100) labels each micro-batch's cross-entropy is the mean over its
+        own valid rows, and the group's gradient then differs from torch's mean over the valid rows of one big batch.
+        grad_sync() runs after every micro-batch's backward, before the fold (the all-reduce is linear).  Metrics, the
+        frozen-phase feature cache and `after_batch` stay per micro-batch."""
+        k_acc = int(self.gradient_accumulation_steps)
+        if k_acc < 1:
+            raise ValueError(f"gradient_accumulation_steps {self.gradient_accumulation_steps!r}: expected an integer >= 1")
+        if k_acc > 1:
+            return self._train_one_epoch_accumulating(k_acc, after_batch)
         self.model.train()
         classifies = self._classifies()
         correct = torch.zeros((), device=self.device, dtype=torch.long if classifies else
@@ -189,6 +213,50 @@ class FineTuneBase:
         if fc is not None:
             fc["have_train"] = True
         self.loss_fn.check()            # labels outside [0, classes) seen by any step of this epoch raise here
+        return correct, seen
+
+    def _train_one_epoch_accumulating(self, k_acc, after_batch=None):
+        """_train_one_epoch with one optimiser step per group of k_acc micro-batches (its docstring)."""
+        self.model.train()
+        classifies = self._classifies()
+        correct = torch.zeros((), device=self.device, dtype=torch.long if classifies else
+                              torch.float32 if self.problem_type == "regression" else torch.int32)
+        self._batch_loss = torch.zeros((), dtype=torch.float32, device=self.device)
+        dl = self.train_dataloader
+        seen, nb = 0, len(dl)
+        fc = getattr(self, "_feat_cache", None)
+        batches = list(dl.index_batches())
+        k = 0
+        for first in range(0, len(batches), k_acc):
+            group = batches[first:first + k_acc]
+            total = sum(len(idx) for idx in group)
+            for j, idx in enumerate(group):
+                k += 1
+                self.optimizer.zero_grad()
+                if fc is not None and fc["have_train"]:
+                    tb = dl.gather_labels(idx)
+                    logits = self.model.head(fc["train"][self._index(idx)]).logits
+                else:
+                    xb, tb = dl.gather(idx)
+                    logits = self.model(xb).logits
+                    if fc is not None:
+                        fc["train"][self._index(idx)] = self.model.last_features()
+                loss = self.loss_fn(logits, tb)
+                loss.backward()
+                if self.grad_sync is not None:
+                    self.grad_sync()
+                self.optimizer.accumulate(len(idx) / total, last=j == len(group) - 1)
+                if classifies:
+                    correct += (logits.argmax(dim=-1) == tb).sum()
+                    seen += tb.size(0)
+                else:
+                    seen += self._count(logits.detach(), tb, correct, loss.detach())
+                if after_batch is not None:
+                    after_batch(k, nb)
+            self.optimizer.step()
+        if fc is not None:
+            fc["have_train"] = True
+        self.loss_fn.check()
         return correct, seen
 
     def _index(self, idx):

@@ -14,6 +14,10 @@ Parameters that live in one flat buffer (``flatten_parameters``) are updated
 with one launch per run of tensors that share a step count - the frozen and
 unfrozen fine-tuning phases give the head and the backbone different counts
 (SURVEY Q11), and tensors whose ``grad`` is None are skipped like torch does.
+
+Training-loop options (csrc/grad_clip.hip): ``FusedAdam(max_grad_norm=...)`` clips by the global L2 norm inside the
+step, ``FusedAdam.accumulate()`` folds the gradients of several backward passes into an accumulator the next step
+consumes, and ``clip_grad_norm_`` is torch's free function on the same kernels.  Nothing of it reads a value back.
 """
 from __future__ import annotations
 
@@ -61,12 +65,69 @@ def flatten_parameters(module: torch.nn.Module, order=None, pad_after=None):
     return flat, gflat, offsets
 
 
+def _merge_ranges(ranges):
+    """ranges: lists [ptr, other_ptr, numel, slack_bytes] - merged, in address order, where the next range begins less than
+    `slack_bytes` after the end of the previous one at BOTH pointers (flat buffers: the 16-byte alignment padding plus
+    declared zero padding, whose gradient is zero; loose tensors: slack 1, i.e. exactly adjacent)."""
+    merged = []
+    for r in sorted(ranges, key=lambda r: r[0]):
+        if merged:
+            q = merged[-1]
+            gap = r[0] - (q[0] + 4 * q[2])
+            if 0 <= gap < q[3] and r[1] - q[1] == r[0] - q[0]:
+                q[2] = (r[0] - q[0]) // 4 + r[2]
+                q[3] = r[3]
+                continue
+        merged.append(list(r))
+    return merged
+
+
+class _JobTables:
+    """Device job tables ({pointer, element count} rows, include/eav_hip.h) and their fp64 partials, cached by the ranges
+    they describe: a steady-state step finds its tables here and neither allocates nor copies anything to the device."""
+
+    def __init__(self, limit=16):
+        self._cache, self._limit = {}, limit
+
+    def get(self, device, ranges):
+        """ranges: tuple of (ptr, other_ptr, numel).  Returns (table of ptr, table of other_ptr, njobs, nchunks, partials)."""
+        key = (device, ranges)
+        hit = self._cache.get(key)
+        if hit is None:
+            nchunks = sum(int(_lib.plain("eav_grad_nchunks", r[2])) for r in ranges)
+            if len(self._cache) >= self._limit:
+                self._cache.clear()
+            hit = (torch.tensor([[r[0], r[2]] for r in ranges], dtype=torch.int64).to(device),
+                   torch.tensor([[r[1], r[2]] for r in ranges], dtype=torch.int64).to(device),
+                   len(ranges), nchunks, torch.empty(max(nchunks, 1), dtype=torch.float64, device=device))
+            self._cache[key] = hit
+        return hit
+
+
+def _flat_slack(p):
+    return 16 + 4 * getattr(p, "_eav_pad", 0) if getattr(p, "_eav_flat", None) is not None else 1
+
+
 class FusedAdam(torch.optim.Optimizer):
     """Adam (``decoupled=False``) / AdamW (``decoupled=True``) with torch's
-    hyper-parameter names; one ``eav_adam_step`` launch per contiguous run."""
+    hyper-parameter names; one ``eav_adam_step`` launch per contiguous run.
+
+    ``max_grad_norm`` (attribute, may be changed between steps; None: off) clips by the global L2 norm like
+    ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` before the update: step() forms the norm over exactly the
+    gradients it is about to consume - parameters whose ``grad`` is None are left out - in two extra launches however
+    many tensors there are (``eav_grad_sumsq``, ``eav_grad_clip_finish``), and the update launches become
+    ``eav_adam_step_scaled`` with the device-resident coefficient min(1, max_grad_norm / (norm + 1e-6)).  ``p.grad``
+    ITSELF IS LEFT UNSCALED (torch's function scales it in place; the free function ``clip_grad_norm_`` below does that).
+    ``last_grad_norm`` is the 0-dim device tensor holding the norm before clipping, overwritten by every such step and
+    never read back by the library; ``float("inf")`` measures the norm and clips nothing.  Nothing needs a host value,
+    so a capturable optimiser's step() is captured with its clipping.
+
+    ``accumulate(weight)`` folds the current gradients into an accumulator (the models' backward OVERWRITES the flat
+    gradient buffer, so torch's idiom of several backward() calls before one step() cannot work here); the next step()
+    consumes the accumulator instead of ``p.grad``."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
-                 capturable=False):
+                 capturable=False, max_grad_norm=None):
         """capturable=True keeps ONE step count in device memory (incremented by a kernel), so that step()
         can be captured in a hipGraph and replayed; it requires every parameter to receive a gradient on
         every step (true for EEGNet; the two-phase AST/ViT fine-tune uses the default host-side counts)."""
@@ -78,12 +139,110 @@ class FusedAdam(torch.optim.Optimizer):
         # capturable: set by a caller that increments the device step count itself at the start of the step, in a launch
         # it issues anyway (GraphStep: eav_step_begin) - step() then skips its own eav_counter_inc for that one call
         self.step_counted = False
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm = None
+        self._tables = _JobTables()
+        self._norm_out = None           # device [norm, coefficient]
+        self._weights = {}              # fold weights as device scalars, by value
+        self._acc_flat, self._acc_loose = {}, {}
+        self._acc_key, self._acc_folds, self._acc_tables, self._acc_partials = None, 0, None, False
 
-    def _launch(self, p_ptr, g_ptr, m_ptr, v_ptr, n, group, step):
+    def _launch(self, p_ptr, g_ptr, m_ptr, v_ptr, n, group, step, gscale=None):
         b1, b2 = group["betas"]
-        _lib.call("eav_adam_step", p_ptr, g_ptr, m_ptr, v_ptr, n, float(group["lr"]), float(b1), float(b2),
-                  float(group["eps"]), float(group["weight_decay"]), int(step), int(bool(group["decoupled"])),
-                  None if self._dev_step is None else self._dev_step.data_ptr(), _lib.stream_ptr())
+        args = (p_ptr, g_ptr, m_ptr, v_ptr, n, float(group["lr"]), float(b1), float(b2),
+                float(group["eps"]), float(group["weight_decay"]), int(step), int(bool(group["decoupled"])),
+                None if self._dev_step is None else self._dev_step.data_ptr())
+        if gscale is None:
+            _lib.call("eav_adam_step", *args, _lib.stream_ptr())
+        else:
+            _lib.call("eav_adam_step_scaled", *args, gscale, _lib.stream_ptr())
+
+    # ---- gradient accumulation ------------------------------------------------------------------------------------
+    def _checked_grad(self, p):
+        """p.grad as step() and accumulate() consume it: on the device, contiguous, and - for a parameter of a flat model -
+        the model's own view of its flat gradient buffer."""
+        g = p.grad
+        if not p.is_cuda:
+            raise _lib.EavError("FusedAdam needs parameters on a ROCm device (no CPU fallback)")
+        if not g.is_contiguous():
+            g = g.contiguous()
+        fl = getattr(p, "_eav_flat", None)
+        if fl is not None and g.data_ptr() != fl[1].data_ptr() + 4 * fl[2]:
+            # the models return views of their flat gradient buffer, which each backward OVERWRITES; autograd
+            # adopts the view only when p.grad was None - anything else means torch accumulated into a copy
+            # (zero_grad(set_to_none=False), or two backward() calls before one step)
+            raise _lib.EavError("FusedAdam: p.grad is not the model's flat gradient buffer - use "
+                                "optimizer.zero_grad() (set_to_none=True) and one backward() per step; gradient "
+                                "accumulation across backward() calls is not supported (call optimizer.accumulate() "
+                                "after each backward() instead)")
+        return g
+
+    def accumulated_grad(self, p):
+        """p's view of the accumulator (None before the first accumulate() that saw p with a gradient)."""
+        fl = getattr(p, "_eav_flat", None)
+        if fl is not None:
+            acc = self._acc_flat.get(fl[1].data_ptr())
+            return None if acc is None else acc[fl[2]:fl[2] + p.numel()].view(p.shape)
+        return self._acc_loose.get(p)
+
+    def _weight_scalar(self, weight, device):
+        key = (float(weight), device)
+        if key not in self._weights:
+            if len(self._weights) >= 64:
+                self._weights.clear()
+            self._weights[key] = torch.tensor(float(weight), dtype=torch.float32).to(device)
+        return self._weights[key]
+
+    @torch.no_grad()
+    def accumulate(self, weight=1.0, last=False):
+        """acc = weight * grad (first fold since the last step(): the accumulator's old contents are not read) or
+        acc += weight * grad, over every parameter that has a gradient, in one ``eav_grad_fold`` launch.  The next step()
+        updates from the accumulator and empties it.  With weights len(micro-batch) / len(group) the update is that of
+        one batch holding the group's samples.  last=True on the final fold of a group lets that launch produce the
+        sum-of-squares partials ``max_grad_norm`` needs; without it step() runs ``eav_grad_sumsq`` over the accumulator
+        (same bits).  The set of parameters with a gradient must not change inside a group."""
+        if self.capturable:
+            raise _lib.EavError("FusedAdam(capturable=True).accumulate(): a captured step holds one whole optimiser step - "
+                                "gradient accumulation inside a graph is not supported; build the optimiser with "
+                                "capturable=False to accumulate")
+        ps = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        if not ps:
+            raise _lib.EavError("FusedAdam.accumulate(): no parameter has a gradient")
+        key = tuple(id(p) for p in ps)
+        if self._acc_folds and key != self._acc_key:
+            raise _lib.EavError("FusedAdam.accumulate(): the parameters with a gradient differ from those already in the "
+                                "accumulator (requires_grad changed inside an accumulation group?) - step() first")
+        ranges = []
+        for p in ps:
+            g = self._checked_grad(p)
+            fl = getattr(p, "_eav_flat", None)
+            if fl is not None:
+                if fl[1].data_ptr() not in self._acc_flat:
+                    self._acc_flat[fl[1].data_ptr()] = torch.zeros_like(fl[1])
+            elif p not in self._acc_loose:
+                self._acc_loose[p] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            ranges.append([g.data_ptr(), self.accumulated_grad(p).data_ptr(), p.numel(), _flat_slack(p)])
+        dev = ps[0].device
+        tables = self._tables.get(dev, tuple((r[0], r[1], r[2]) for r in _merge_ranges(ranges)))
+        jobs_g, jobs_a, njobs, nchunks, partials = tables
+        want = bool(last) and self.max_grad_norm is not None
+        _lib.call("eav_grad_fold", jobs_g.data_ptr(), jobs_a.data_ptr(), njobs, nchunks,
+                  self._weight_scalar(weight, dev).data_ptr(), int(self._acc_folds == 0),
+                  partials.data_ptr() if want else None, _lib.stream_ptr())
+        self._acc_key, self._acc_tables, self._acc_partials = key, tables, want
+        self._acc_folds += 1
+
+    def _clip(self, device, tables, have_partials):
+        """The norm of the ranges of `tables` and the clipping coefficient, on the device; returns the coefficient's pointer."""
+        _, jobs, njobs, nchunks, partials = tables
+        if self._norm_out is None or self._norm_out.device != device:
+            self._norm_out = torch.zeros(2, dtype=torch.float32, device=device)
+            self.last_grad_norm = self._norm_out[0]
+        if not have_partials:
+            _lib.call("eav_grad_sumsq", jobs.data_ptr(), njobs, nchunks, partials.data_ptr(), _lib.stream_ptr())
+        _lib.call("eav_grad_clip_finish", partials.data_ptr(), nchunks, float(self.max_grad_norm),
+                  self._norm_out.data_ptr(), _lib.stream_ptr())
+        return self._norm_out.data_ptr() + 4
 
     def device_step_counter(self):
         """The device-resident step count of a capturable optimiser (created on first use)."""
@@ -105,27 +264,22 @@ class FusedAdam(torch.optim.Optimizer):
                 self.step_counted = False
             else:
                 _lib.call("eav_counter_inc", self._dev_step.data_ptr(), _lib.stream_ptr())
+        folded = set(self._acc_key) if self._acc_folds else None      # accumulate() was called: consume the accumulator
+        plan = []
         for group in self.param_groups:
             runs = []  # (p_ptr, g_ptr, m_ptr, v_ptr, numel, step) candidates for merging
             touched = {}
             for p in group["params"]:
-                g = p.grad
-                if g is None:
+                if folded is not None:
+                    if id(p) not in folded:
+                        continue
+                    g = self.accumulated_grad(p)
+                elif p.grad is None:
                     if self.capturable:
                         raise _lib.EavError("FusedAdam(capturable=True): every parameter must have a gradient")
                     continue
-                if not p.is_cuda:
-                    raise _lib.EavError("FusedAdam needs parameters on a ROCm device (no CPU fallback)")
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                fl = getattr(p, "_eav_flat", None)
-                if fl is not None and g.data_ptr() != fl[1].data_ptr() + 4 * fl[2]:
-                    # the models return views of their flat gradient buffer, which each backward OVERWRITES; autograd
-                    # adopts the view only when p.grad was None - anything else means torch accumulated into a copy
-                    # (zero_grad(set_to_none=False), or two backward() calls before one step)
-                    raise _lib.EavError("FusedAdam: p.grad is not the model's flat gradient buffer - use "
-                                        "optimizer.zero_grad() (set_to_none=True) and one backward() per step; gradient "
-                                        "accumulation across backward() calls is not supported")
+                else:
+                    g = self._checked_grad(p)
                 st = self.state[p]
                 if getattr(p, "_eav_flat", None) is not None:
                     touched[p._eav_flat[0].data_ptr()] = p._eav_flat[0]
@@ -159,8 +313,19 @@ class FusedAdam(torch.optim.Optimizer):
                         q[7] = r[7]
                         continue
                 merged.append(r)
+            plan.append((group, merged, touched))
+        gscale = None
+        if self.max_grad_norm is not None and any(merged for _, merged, _ in plan):
+            dev = next(r[6].device for _, merged, _ in plan for r in merged)
+            if folded is not None:      # the accumulator's own table: the partials of a last=True fold belong to it
+                gscale = self._clip(dev, self._acc_tables, self._acc_partials)
+            else:
+                ranges = tuple((r[1], r[1], r[4]) for _, merged, _ in plan for r in merged)
+                gscale = self._clip(dev, self._tables.get(dev, ranges), False)
+        self._acc_folds, self._acc_partials = 0, False
+        for group, merged, touched in plan:
             for r in merged:
-                self._launch(r[0], r[1], r[2], r[3], r[4], group, r[5])
+                self._launch(r[0], r[1], r[2], r[3], r[4], group, r[5], gscale)
                 # tell whoever caches derived copies of these parameters (transformer.Encoder's fp16 operand
                 # planes) which byte ranges of the flat buffer just changed
                 # (only flat buffers whose owner registered interest - `_eav_track_dirty` - are tracked, and the list
@@ -174,6 +339,42 @@ class FusedAdam(torch.optim.Optimizer):
                             d = [(min(a for a, _ in d), max(b for _, b in d))]
                         fl._eav_dirty = d
         return loss
+
+
+_CLIP_TABLES = _JobTables()
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False):
+    """``torch.nn.utils.clip_grad_norm_`` on the device: scales every ``p.grad`` in place by
+    min(1, max_norm / (norm + 1e-6)) and returns the global L2 norm before clipping as a 0-dim device tensor - three
+    launches (``eav_grad_sumsq``, ``eav_grad_clip_finish``, ``eav_scale_ranges``), nothing read back.  L2 only; a
+    non-finite norm is handled like torch's default (NaN scales by NaN, infinity by 0)."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError(f"clip_grad_norm_: norm_type {norm_type!r} - only the L2 norm is implemented")
+    if error_if_nonfinite:
+        raise NotImplementedError("clip_grad_norm_: error_if_nonfinite=True needs the norm on the host; read the "
+                                  "returned tensor instead")
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    ps = [p for p in parameters if p.grad is not None]
+    if not ps:
+        raise _lib.EavError("clip_grad_norm_: no parameter has a gradient")
+    ranges = []
+    for p in ps:
+        g = p.grad
+        if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous() or g.device != ps[0].grad.device:
+            raise _lib.EavError("clip_grad_norm_ needs contiguous fp32 gradients on one ROCm device (no CPU fallback)")
+        if g.numel():
+            ranges.append([g.data_ptr(), g.data_ptr(), g.numel(), _flat_slack(p)])
+    dev = ps[0].grad.device
+    _, jobs, njobs, nchunks, partials = _CLIP_TABLES.get(dev, tuple((r[0], r[1], r[2]) for r in _merge_ranges(ranges)))
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    st = _lib.stream_ptr()
+    _lib.call("eav_grad_sumsq", jobs.data_ptr(), njobs, nchunks, partials.data_ptr(), st)
+    _lib.call("eav_grad_clip_finish", partials.data_ptr(), nchunks, float(max_norm), out.data_ptr(), st)
+    _lib.call("eav_scale_ranges", jobs.data_ptr(), njobs, nchunks, out.data_ptr() + 4, st)
+    return out[0]
 
 
 class _CEFn(torch.autograd.Function):

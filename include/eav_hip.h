@@ -278,6 +278,32 @@ int eav_scale_by_scalar(float* v, const float* scalar, int64_t n, void* stream);
  * step_dev (optional, device int64): take the step count from device memory instead (graph-capturable). */
 int eav_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int64_t step, int decoupled, const int64_t* step_dev, void* stream);
+/* eav_adam_step on the gradient g * *gscale (device scalar, e.g. out2 + 1 of eav_grad_clip_finish): the product is rounded to
+ * fp32 first, so p, m, v get the bits eav_adam_step gives a gradient tensor scaled beforehand; g itself is not written. */
+int eav_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int64_t step, int decoupled, const int64_t* step_dev,
+                         const float* gscale, void* stream);
+/* ---- Global-norm gradient clipping and gradient accumulation (csrc/grad_clip.hip) ----
+ * A job table is a device array of njobs rows of 2 int64 {pointer, element count}: fp32 ranges, 4-byte aligned at least.
+ * Every job is cut into chunks of eav_grad_chunk_elems() elements from its own start; the chunks of job 0, job 1, ... are
+ * numbered 0 .. nchunks - 1 with nchunks = the sum over the jobs of eav_grad_nchunks(element count), a host helper like the
+ * other *_nparts (integer arithmetic, no pointer).  Chunk c is handled by one workgroup
+ * and its fp64 sum of squares goes to partials[c] (nchunks doubles): no atomics, results independent of the grid, two runs
+ * give the same bits.  All scalars that change from step to step (weight, scalar, out2) are device memory. */
+int64_t eav_grad_chunk_elems(void);
+int64_t eav_grad_nchunks(int64_t n);
+/* partials[c] = sum over chunk c of (double)g * (double)g */
+int eav_grad_sumsq(const void* jobs, int njobs, int64_t nchunks, double* partials, void* stream);
+/* acc = first ? w g : fma(w, g, acc) with w = *weight, element by element over two tables of equal counts (jobs_g's are
+ * used; first: the old contents of acc are not read).  partials (may be NULL): eav_grad_sumsq of the values just stored,
+ * bit for bit what eav_grad_sumsq over jobs_acc gives afterwards. */
+int eav_grad_fold(const void* jobs_g, const void* jobs_acc, int njobs, int64_t nchunks, const float* weight, int first,
+                  double* partials, void* stream);
+/* out2[0] = (float)sqrt(sum of the partials, fp64, fixed order); out2[1] = min(1, max_norm / (out2[0] + 1e-6f)), formed as
+ * torch.nn.utils.clip_grad_norm_ forms it (NaN norm: NaN; infinite norm: 0).  max_norm > 0 (infinity allowed). */
+int eav_grad_clip_finish(const double* partials, int64_t nchunks, float max_norm, float* out2, void* stream);
+/* g *= *scalar in place over a job table; nothing is written when the scalar is exactly 1. */
+int eav_scale_ranges(const void* jobs, int njobs, int64_t nchunks, const float* scalar, void* stream);
 /* Batch assembly in HBM: out[i,:] = src[idx[i],:] (rows of row_elems floats) / out[i] = src[idx[i]] (labels).
  * Replaces the per-batch host->device copies of the reference loops (EEGNet_tor.py:100-101). */
 int eav_gather_rows(const float* src, const int64_t* idx, float* out, int nrows, int64_t row_elems, void* stream);

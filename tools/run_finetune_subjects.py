@@ -77,8 +77,14 @@ def main():
                     "interpolate_pos_encoding (ImageClassifierTrainer(image_size=N)); default: the processor's size")
     ap.add_argument("--max-length", default=None, help="audio only: N frames or 'auto' (the longest clip's own length) instead "
                     "of the checkpoint's 1024 (AudioModelTrainer(max_length=...)); default: the checkpoint's")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="F", help="clip the gradients' global L2 norm to F "
+                    "inside every optimiser step (trainer.max_grad_norm); default: no clipping, like the reference")
+    ap.add_argument("--grad-accum", type=int, default=1, metavar="K", help="one optimiser step per K micro-batches "
+                    "(trainer.gradient_accumulation_steps): effective batch K x the launch batch")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
+    if args.grad_accum < 1 or (args.max_grad_norm is not None and not args.max_grad_norm > 0):
+        ap.error("--grad-accum takes K >= 1 and --max-grad-norm F > 0")
     audio = args.kind == "audio"
     if audio and args.image_size is not None:
         ap.error("--image-size is a vision option")
@@ -124,6 +130,7 @@ def main():
                 else:
                     tr = ImageClassifierTrainer(data, model_path=path, sub=f"subject_{sub:02d}", num_labels=5, lr=5e-5,
                                                 batch_size=bsz, image_size=args.image_size)
+                tr.max_grad_norm, tr.gradient_accumulation_steps = args.max_grad_norm, args.grad_accum
                 if n > 1:
                     eav_dist.attach(tr, group=groups[sub])
                 tr.train(epochs=args.frozen_epochs, lr=5e-4, freeze=True)
