@@ -113,6 +113,9 @@ SIGNATURES = {
     "eav_attn_dqkv_bound": [_p, _p, _p, _i, _f, _p],
     "eav_attn_fwd": [_p, _p, _p, _i, _i, _i, _i, _f, _p],
     "eav_attn_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
+    "eav_attn_probs": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
+    "eav_attn_probs_sp": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
+    "eav_rollout_step": [_p, _p, _p, _i, _i, _i, _p],
     "eav_attn_fwd_dropout": [_p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _p, _p],
     "eav_attn_bwd_dropout": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _p, _p],
     "eav_attn_fwd_sp_dropout": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _p, _p],

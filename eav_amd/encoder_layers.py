@@ -151,6 +151,7 @@ class Fp32Layers:
             Pv = softmax_forward(m, i, Pm, B * H * N, N, ldn)
             gemm(Pv, qkv + 8 * D, P(ws.ao[j]), N, hd, N, ldn, 3 * D, D, tB=1, batch=B * H, heads=H,
                  sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
+        m._attention_out(i, j, scale, qkv=qkv)
         # (hidden dropout sits between the bias and the residual add: the product leaves without the residual and one
         # element-wise pass forms resid + Dropout(product))
         hd_on = drop.ph > 0.0
@@ -569,6 +570,7 @@ class SplitLayers:
             Pv = softmax_forward(m, i, Pm, ws.B * H * N, N, ldn)
             gemm_f32(m, Pv, qkv + 8 * D, P(ao), N, hd, N, ldn, 3 * D, D, tB=1, batch=ws.B * H, heads=H,
                      sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
+        m._attention_out(i, j, scale, rowp=P(ws.qkvrow[j]) if ws.fused else None, slot=s_qkv)
         if not (ws.fused and fusedp and m.fused_ao) or (ws.fused and ws.drop.pa > 0.0):
             self.to_planes(P(ao), M, D, D, s_ao, ws.aop[j], amax_done=ws.fused)
         wpl, wsl = wp.get(f"o{i}")

@@ -58,8 +58,9 @@ def _set_param(root, dotted, value):
 
 
 class _Out:
-    def __init__(self, logits, loss=None):
+    def __init__(self, logits, loss=None, hidden_states=None, attentions=None):
         self.logits, self.loss = logits, loss
+        self.hidden_states, self.attentions = hidden_states, attentions
 
 
 class _HeadFn(torch.autograd.Function):
@@ -190,6 +191,14 @@ class Encoder(KernelModule):
         # argument, and forward()'s parameter list is HF's.
         self.variable_length = False
         self._active_geo = None       # None: the geometry of cfg
+        # HF's model(..., output_attentions=, output_hidden_states=): these attributes are the defaults of those two keywords
+        # of __call__ (HF: config.output_attentions / config.output_hidden_states; from_pretrained copies them from config.json)
+        self.output_attentions = False
+        self.output_hidden_states = False
+        self._outs = None             # what the forward in flight collects beside the logits (_begin_outputs)
+        self._want_outs = (False, None)   # (hidden states?, "probs" | "mean" | None) of the forward in flight
+        self._rollout = False
+        self._out_flags = (None, None)    # the two keywords of the call in flight (__call__)
         if cfg.hidden % cfg.heads or (cfg.hidden // cfg.heads) % 4 or cfg.hidden % 4 or cfg.hidden > 1024:
             raise NotImplementedError("hidden size must be <= 1024, a multiple of 4, head_dim a multiple of 4")
         if cfg.ntok > MAX_TOKENS:
@@ -202,7 +211,8 @@ class Encoder(KernelModule):
     @classmethod
     def from_pretrained(cls, model_path):
         """HF directory: config.json + model.safetensors (pytorch_model.bin accepted)."""
-        cfg = config_from_hf(json.load(open(os.path.join(model_path, "config.json"))))
+        hf = json.load(open(os.path.join(model_path, "config.json")))
+        cfg = config_from_hf(hf)
         st = os.path.join(model_path, "model.safetensors")
         if os.path.exists(st):
             from safetensors.numpy import load_file
@@ -218,6 +228,8 @@ class Encoder(KernelModule):
             raise KeyError(f"checkpoint lacks {missing[:4]} ...")
         model = cls(cfg, w)
         model.source_dir = str(model_path)
+        model.output_attentions = bool(hf.get("output_attentions", False))
+        model.output_hidden_states = bool(hf.get("output_hidden_states", False))
         return model
 
     def save_pretrained(self, save_directory, max_length=None):
@@ -311,10 +323,36 @@ class Encoder(KernelModule):
         forward in flight."""
         return self._active_geo if self._active_geo is not None else self.cfg
 
+    def __call__(self, *args, output_attentions=None, output_hidden_states=None, **kwargs):
+        """model(x, ..., output_attentions=None, output_hidden_states=None): forward()'s arguments plus HF's two output
+        keywords (forward's own parameter list stays as it is: the two travel beside it; None: the attributes of the same
+        names).  They add `hidden_states` - layers + 1 tensors [B, N, hidden]: the embedding output (after embedding dropout when active), then
+        every layer's output, the last one WITHOUT the final LayerNorm, as HF returns them - and `attentions` - layers tensors
+        [B, heads, N, N], the softmax probabilities - to the result; N is the token count of this forward.  Both are fresh
+        fp32 allocations (one buffer each, returned as per-layer views), written on the model's stream inside the layer loop,
+        and DETACHED from autograd: HF's versions carry gradients, these do not.  The logits, and a backward that follows,
+        are bit for bit those of a forward without the flags.  With head_dim 64 the probabilities come from
+        csrc/attn_probs.hip (the fused attention never stores them), otherwise they are copied out of the softmax buffer."""
+        self._out_flags = (output_attentions, output_hidden_states)
+        try:
+            return super().__call__(*args, **kwargs)
+        finally:
+            self._out_flags = (None, None)
+
     def forward(self, x=None, labels=None, pixel_values=None, input_values=None, interpolate_pos_encoding=None):
         x = x if x is not None else (pixel_values if pixel_values is not None else input_values)
         self._require_gpu(x)
         c = self.cfg
+        output_attentions, output_hidden_states = self._out_flags
+        want_attn = self.output_attentions if output_attentions is None else bool(output_attentions)
+        want_hidden = self.output_hidden_states if output_hidden_states is None else bool(output_hidden_states)
+        if want_attn or want_hidden:
+            if torch.cuda.is_current_stream_capturing():
+                raise NotImplementedError("output_attentions / output_hidden_states allocate their results: not available "
+                                          "while the stream is capturing")
+            if want_attn and self.training and c.attention_dropout > 0.0:
+                raise NotImplementedError("output_attentions in training mode with attention_probs_dropout_prob > 0 is not "
+                                          "implemented: HF returns the dropped probabilities there")
         interp = self.interpolate_pos_encoding if interpolate_pos_encoding is None else bool(interpolate_pos_encoding)
         varlen = bool(self.variable_length)
         geo = None
@@ -347,11 +385,61 @@ class Encoder(KernelModule):
         self._ensure_flat()
         self._want_full = torch.is_grad_enabled() and any(
             p.requires_grad for k, p in self._pmap.items() if not k.startswith("classifier."))
-        logits = KernelFn.apply(x, self, *[self._pmap[k] for k in self._names])
+        # (attention_rollout asks for the head means instead of the probabilities)
+        self._want_outs = (bool(want_hidden), "mean" if self._rollout else ("probs" if want_attn else None))
+        try:
+            logits = KernelFn.apply(x, self, *[self._pmap[k] for k in self._names])
+        finally:
+            self._want_outs = (False, None)
+        outs, self._outs = self._outs, None
         loss = None
         if labels is not None:
             loss = self.criterion(labels)(logits, labels)
-        return _Out(logits, loss)
+        if outs is None:
+            return _Out(logits, loss)
+        attn = outs.probs if outs.probs is not None else outs.mean        # (mean: attention_rollout's forward)
+        return _Out(logits, loss, None if outs.hidden is None else tuple(outs.hidden.unbind(0)),
+                    None if attn is None else tuple(attn.unbind(0)))
+
+    def attention_rollout(self, x, as_grid=False, interpolate_pos_encoding=None):
+        """Attention rollout (Abnar & Zuidema 2020) of the readout tokens, [B, N]: how much of each input token reaches the
+        classifier through the attention layers, heads averaged, the residual stream counted as half of every layer.  From
+        the top layer down r <- r (0.5 A_l + 0.5 I), A_l the head mean of layer l (head_dim 64: written by the
+        attention-probability kernels themselves, no [B, heads, N, N] buffer exists; otherwise summed over the heads' slices
+        of the softmax buffer), starting from the one-hot readout row - CLS for a ViT; CLS and the distillation token for
+        AST, averaged at the end as the pooled feature is their mean.  Runs under no_grad in eval mode (the mode is
+        restored).  as_grid: the patch tokens only, as the forward's patch grid [B, gy, gx]."""
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("attention_rollout allocates its result: not available while the stream is capturing")
+        training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                self._rollout = True
+                try:
+                    mean = self(x, interpolate_pos_encoding=interpolate_pos_encoding, output_attentions=False,
+                                output_hidden_states=False).attentions
+                finally:
+                    self._rollout = False
+                c = self._geo
+                B, N, R = x.shape[0], c.ntok, c.nextra
+                r, r_next = torch.zeros(B, R, N, dtype=torch.float32, device=x.device), torch.empty(B, R, N, device=x.device)
+                for k in range(R):
+                    r[:, k, k].fill_(1.0)
+                st = self._begin()
+                for i in reversed(range(c.layers)):
+                    self._call("eav_rollout_step", _lib.ptr(r), _lib.ptr(mean[i]), _lib.ptr(r_next), B, R, N, st)
+                    r, r_next = r_next, r
+                out = torch.empty(B, N, dtype=torch.float32, device=x.device)
+                if R == 2:
+                    self._call("eav_pair_mean", _lib.ptr(r), _lib.ptr(out), B, N, 0, st)
+                else:
+                    out.copy_(r[:, 0])
+        finally:
+            self.train(training)
+        if as_grid:
+            return out[:, c.nextra:].reshape(B, c.ny, c.nx)
+        return out
 
     def criterion(self, labels=None):
         """The criterion of cfg.problem_type, held on the encoder: CrossEntropyLoss, BCEWithLogitsLoss or MSELoss
@@ -728,6 +816,47 @@ class Encoder(KernelModule):
             self._call("eav_pos_bicubic_bwd", P(ws.dpos_i), gpos, g, c.ny, c.nx, c.hidden, c.nextra,
                        *[P(t) for t in tb["bwd_y"]], tb["nnzy"], *[P(t) for t in tb["bwd_x"]], tb["nnzx"], self._st)
 
+    def _begin_outputs(self, B, dev):
+        """The buffers of what this forward returns beside the logits (the call's output_hidden_states / output_attentions;
+        attention_rollout's head means), fresh for every forward - the workspace is the next forward's to overwrite: hidden
+        [layers + 1, B, N, D], probs [layers, B, H, N, N], mean [layers, B, N, N], each None unless asked for."""
+        hidden, attn = self._want_outs
+        self._outs = None
+        if not hidden and attn is None:
+            return None
+        c = self._geo
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        self._outs = SimpleNamespace(hidden=f(c.layers + 1, B, c.ntok, c.hidden) if hidden else None,
+                                     probs=f(c.layers, B, c.heads, c.ntok, c.ntok) if attn == "probs" else None,
+                                     mean=f(c.layers, B, c.ntok, c.ntok) if attn == "mean" else None)
+        return self._outs
+
+    def _attention_out(self, i, j, scale, qkv=None, rowp=None, slot=None):
+        """Layer i's attention probabilities into the forward's outputs, right after its attention kernel (workspace index
+        j): the fused path launches csrc/attn_probs.hip on the operands that kernel consumed - fp32 `qkv`, or the row planes
+        `rowp` with their scale `slot` - and the lse it wrote; the materialised path copies the softmax output out of ws.P[j]
+        (row stride ldn).  A no-op unless the forward asked for them."""
+        o = self._outs
+        if o is None or (o.probs is None and o.mean is None):
+            return
+        c, ws, P = self._geo, self._ws, _lib.ptr
+        N, H = c.ntok, c.heads
+        probs = None if o.probs is None else P(o.probs[i])
+        mean = None if o.mean is None else P(o.mean[i])
+        if not ws.fused:
+            if o.probs is not None:
+                o.probs[i].view(ws.B * H, N, N).copy_(ws.P[j][:, :, :N])
+            if o.mean is not None:      # the heads of an image are H slices of ws.P[j], N ldn floats apart: summed in head order
+                pad = torch.empty(ws.B, N, ws.ldn, dtype=torch.float32, device=ws.P[j].device)
+                for b in range(ws.B):
+                    self._call("eav_reduce_partials", P(ws.P[j][b * H]), H, N * ws.ldn, N * ws.ldn, 1.0 / H, P(pad[b]),
+                               self._st)
+                o.mean[i].copy_(pad[:, :, :N])
+        elif rowp is not None:
+            self._call("eav_attn_probs_sp", rowp, slot, P(ws.lse[j]), probs, mean, ws.B, H, N, c.hidden // H, scale, self._st)
+        else:
+            self._call("eav_attn_probs", qkv, P(ws.lse[j]), probs, mean, ws.B, H, N, c.hidden // H, scale, self._st)
+
     def _launch_forward(self, x):
         c = self._geo
         P, L, w = _lib.ptr, self._call, self._w
@@ -750,6 +879,9 @@ class Encoder(KernelModule):
           w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None, pos, B, N, D, c.nextra, st)
         if drop.ph > 0.0:
             self._drop_add(P(h0), None, P(h0), ws.M * D, drop.ph, 0, "emb")
+        outs = self._begin_outputs(B, x.device)
+        if outs is not None and outs.hidden is not None:
+            outs.hidden[0].view(ws.M, D).copy_(h0)
         scale = (D // c.heads) ** -0.5
         layer = lay.layer_forward
         for i in range(c.layers):
@@ -757,6 +889,8 @@ class Encoder(KernelModule):
             hin = ws.hs[i] if ws.full else ws.hs[i & 1]
             hout = ws.hs[i + 1] if ws.full else ws.hs[(i + 1) & 1]
             layer(i, j, hin, hout, f"{pre}.layers.{i}", P(ws.st[j]), scale)
+            if outs is not None and outs.hidden is not None:      # (the workspace's copy is the next layer's, or forward's, to reuse)
+                outs.hidden[i + 1].view(ws.M, D).copy_(hout)
         hlast = ws.hs[c.layers] if ws.full else ws.hs[c.layers & 1]
         R = B * c.nextra
         L("eav_token_rows", P(hlast), P(ws.rows), B, N, D, c.nextra, 0, st)

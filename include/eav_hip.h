@@ -522,6 +522,20 @@ int eav_attn_fwd(const float* qkv, float* ao, float* lse, int B, int H, int N, i
  * the forward; delta: scratch [B*H, N]. */
 int eav_attn_bwd(const float* qkv, const float* ao, const float* dout, const float* lse, float* delta, float* dqkv,
                  int B, int H, int N, int head_dim, float scale, void* stream);
+/* The attention probabilities of the fused kernels after the fact (csrc/attn_probs.hip; HF output_attentions=True):
+ * P[b, h, q, k] = exp(scale q.k - lse[b, h, q]) from the operands the layer's attention kernel consumed - qkv [B*N, 3*H*64]
+ * fp32 (eav_attn_fwd), or the row planes and scale slot of eav_attn_sp_prep / the plane-writing q/k/v projection
+ * (eav_attn_fwd_sp) - and the lse [B*H, N] it wrote; the scores are formed as that precision's kernels form them.
+ * probs [B, H, N, N] and probs_mean [B, N, N] (the mean over heads, summed in head order inside one workgroup) are fp32;
+ * either may be NULL, not both.  head_dim must be 64.  Deterministic: the same bits on every run. */
+int eav_attn_probs(const float* qkv, const float* lse, float* probs, float* probs_mean, int B, int H, int N, int head_dim,
+                   float scale, void* stream);
+int eav_attn_probs_sp(const void* rowp, const float* slot, const float* lse, float* probs, float* probs_mean, int B, int H,
+                      int N, int head_dim, float scale, void* stream);
+/* One step of attention rollout (Abnar & Zuidema 2020) for R readout rows: r_out[b, r, k] = 0.5 sum_q r_in[b, r, q]
+ * abar[b, q, k] + 0.5 r_in[b, r, k]; r [B, R, N], abar [B, N, N] (a layer's head mean), fp32, q summed in ascending order.
+ * r_out must not alias r_in. */
+int eav_rollout_step(const float* r_in, const float* abar, float* r_out, int B, int R, int N, void* stream);
 /* The same with attention-probability dropout 0 < drop_p < 1 (HF attention_probs_dropout_prob, training mode): the keep
  * decision of element (b, h, q, key) is a pure function of (seed + 2 * *seed_dev, ((b H + h) N + q) N + key) - or the
  * byte of an explicit uint8 keep-mask [B, H, N, N] - so no mask is stored: the backward kernels regenerate it and must
