@@ -40,8 +40,7 @@ def softmax_forward(m, i, Pm, rows, N, ldn):
     ws = m._ws
     d = ws.drop
     if d.pa > 0.0:
-        m._call("eav_softmax_dropout_fwd", Pm, _lib.ptr(ws.Pd), rows, N, ldn, d.pa, m._site_seed(1 + 3 * i),
-                d.mk(f"attn.{i}"), d.cnt, m._st)
+        m._call("eav_softmax_dropout_fwd", Pm, _lib.ptr(ws.Pd), rows, N, ldn, *d.site("attn", i), m._st)
         return _lib.ptr(ws.Pd)
     m._call("eav_softmax_fwd", Pm, rows, N, ldn, m._st)
     return Pm
@@ -59,8 +58,7 @@ def attention_backward_scores(m, g, i, qkv, dao, dqkv, scale):
     sP, sQ, sO = (H * N * ldn, N * ldn), (N * 3 * D, hd), (N * D, hd)
     if d.pa > 0.0:
         g(dao, qkv + 8 * D, dP, N, N, hd, D, 3 * D, ldn, batch=B * H, heads=H, sA=sO, sB=sQ, sC=sP)
-        m._call("eav_softmax_dropout_bwd", Pm, dP, P(ws.Pd), B * H * N, N, ldn, d.pa, m._site_seed(1 + 3 * i),
-                d.mk(f"attn.{i}"), d.cnt, m._st)
+        m._call("eav_softmax_dropout_bwd", Pm, dP, P(ws.Pd), B * H * N, N, ldn, *d.site("attn", i), m._st)
         g(P(ws.Pd), dao, dqkv + 8 * D, N, hd, N, ldn, D, 3 * D, tA=1, tB=1, batch=B * H, heads=H, sA=sP, sB=sO, sC=sQ)
     else:
         g(Pm, dao, dqkv + 8 * D, N, hd, N, ldn, D, 3 * D, tA=1, tB=1, batch=B * H, heads=H, sA=sP, sB=sO, sC=sQ)
@@ -140,8 +138,7 @@ class Fp32Layers:
         gemm(P(ws.y1[j]), w(f"{Lk}.attention.q_proj.weight"), qkv, M, 3 * D, D, D, D, 3 * D,
              bias=w(f"{Lk}.attention.q_proj.bias"))
         if ws.fused and drop.pa > 0.0:
-            L("eav_attn_fwd_dropout", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, drop.pa,
-              m._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
+            L("eav_attn_fwd_dropout", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, *drop.site("attn", i), st)
         elif ws.fused:
             L("eav_attn_fwd", qkv, P(ws.ao[j]), P(ws.lse[j]), B, H, N, hd, scale, st)
         else:
@@ -151,14 +148,14 @@ class Fp32Layers:
             Pv = softmax_forward(m, i, Pm, B * H * N, N, ldn)
             gemm(Pv, qkv + 8 * D, P(ws.ao[j]), N, hd, N, ldn, 3 * D, D, tB=1, batch=B * H, heads=H,
                  sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
-        m._attention_out(i, j, scale, qkv=qkv)
+        m._outputs.attention(i, j, scale, qkv=qkv)
         # (hidden dropout sits between the bias and the residual add: the product leaves without the residual and one
         # element-wise pass forms resid + Dropout(product))
         hd_on = drop.ph > 0.0
         gemm(P(ws.ao[j]), w(f"{Lk}.attention.o_proj.weight"), P(ws.hmid[j]), M, D, D, D, D, D,
              bias=w(f"{Lk}.attention.o_proj.bias"), resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
         if hd_on:
-            m._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+            m._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, "attn_out", i)
         L("eav_layernorm_fwd", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"), w(f"{Lk}.layernorm_after.bias"),
           P(ws.y2[j]), stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
         gemm(P(ws.y2[j]), w(f"{Lk}.mlp.fc1.weight"), P(ws.act[j]), M, FF, D, D, D, FF,
@@ -166,7 +163,7 @@ class Fp32Layers:
         gemm(P(ws.act[j]), w(f"{Lk}.mlp.fc2.weight"), P(hout), M, D, FF, FF, FF, D,
              bias=w(f"{Lk}.mlp.fc2.bias"), resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
         if hd_on:
-            m._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+            m._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, "mlp_out", i)
 
     def layer_backward(self, i, Lk, stp, scale):
         """Backward of one layer on the exact-fp32 kernels: ws.dh holds the gradient w.r.t. the layer output on entry, the
@@ -183,7 +180,7 @@ class Fp32Layers:
         g_dh = dh
         if drop.ph > 0.0:
             g_dh = P(ws.dhd)
-            m._drop_add(dh, None, g_dh, M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+            m._drop_add(dh, None, g_dh, M * D, "mlp_out", i)
         wgrad(g_dh, P(ws.act[i]), gp(f"{Lk}.mlp.fc2.weight"), D, FF, M, D, FF)
         bias_grad(g_dh, M, D, D, gp(f"{Lk}.mlp.fc2.bias"))
         gemm(g_dh, w(f"{Lk}.mlp.fc2.weight"), dact, M, FF, D, D, FF, FF, tB=1)
@@ -198,7 +195,7 @@ class Fp32Layers:
         m._reduce_ln(ws.part_ln, ws.np_ln, gp(f"{Lk}.layernorm_after.weight"), gp(f"{Lk}.layernorm_after.bias"))
         # o_proj
         if drop.ph > 0.0:
-            m._drop_add(dh, None, g_dh, M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+            m._drop_add(dh, None, g_dh, M * D, "attn_out", i)
         wgrad(g_dh, P(ws.ao[i]), gp(f"{Lk}.attention.o_proj.weight"), D, D, M, D, D)
         bias_grad(g_dh, M, D, D, gp(f"{Lk}.attention.o_proj.bias"))
         gemm(g_dh, w(f"{Lk}.attention.o_proj.weight"), dao, M, D, D, D, D, D, tB=1)
@@ -206,7 +203,7 @@ class Fp32Layers:
         qkv = P(ws.qkv[i])
         if ws.fused and drop.pa > 0.0:
             L("eav_attn_bwd_dropout", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale,
-              drop.pa, m._site_seed(1 + 3 * i), drop.mk(f"attn.{i}"), drop.cnt, st)
+              *drop.site("attn", i), st)
         elif ws.fused:
             L("eav_attn_bwd", qkv, P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, B, H, N, hd, scale, st)
         else:     # materialised scores, batched over (image, head)
@@ -547,7 +544,7 @@ class SplitLayers:
                 # from the conversion pass below) - the plane-writing form's scale |O| <= max|V| assumes rows of P sum to 1
                 ws.delta_from_planes = False
                 L("eav_attn_fwd_sp_dropout", P(ws.qkvrow[j]), s_qkv, P(ao), P(ws.lse[j]), s_ao, ws.B, H, N, hd, scale,
-                  ws.drop.pa, m._site_seed(1 + 3 * i), ws.drop.mk(f"attn.{i}"), ws.drop.cnt, st)
+                  *ws.drop.site("attn", i), st)
             elif fusedp and m.fused_ao:
                 # the attention output leaves as the planes of the o-proj products (scale: qkv's own, |O| <= max|V|); its
                 # fp32 copy is written only when a backward will read it
@@ -570,7 +567,7 @@ class SplitLayers:
             Pv = softmax_forward(m, i, Pm, ws.B * H * N, N, ldn)
             gemm_f32(m, Pv, qkv + 8 * D, P(ao), N, hd, N, ldn, 3 * D, D, tB=1, batch=ws.B * H, heads=H,
                      sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
-        m._attention_out(i, j, scale, rowp=P(ws.qkvrow[j]) if ws.fused else None, slot=s_qkv)
+        m._outputs.attention(i, j, scale, rowp=P(ws.qkvrow[j]) if ws.fused else None, slot=s_qkv)
         if not (ws.fused and fusedp and m.fused_ao) or (ws.fused and ws.drop.pa > 0.0):
             self.to_planes(P(ao), M, D, D, s_ao, ws.aop[j], amax_done=ws.fused)
         wpl, wsl = wp.get(f"o{i}")
@@ -581,7 +578,7 @@ class SplitLayers:
         gemm_sp(P(ws.aop[j]), s_ao, wpl, wsl, P(ws.hmid[j]), M, D, D, D, bias=w(f"{Lk}.attention.o_proj.bias"),
                 resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
         if hd_on:
-            m._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+            m._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, "attn_out", i)
         if fusedp:
             L("eav_layernorm_fwd_planes", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"),
               w(f"{Lk}.layernorm_after.bias"), None, P(ws.y2p[j]), s_y2, stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
@@ -605,7 +602,7 @@ class SplitLayers:
         gemm_sp(P(ws.actp[j]), s_act, wpl, wsl, P(hout), M, D, FF, D, bias=w(f"{Lk}.mlp.fc2.bias"),
                 resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
         if hd_on:
-            m._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+            m._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, "mlp_out", i)
 
     def layer_backward(self, i, Lk, stp, scale):
         """Backward of one layer: dh (gradient w.r.t. the layer output, fp32) in ws.dh on entry, gradient w.r.t. the
@@ -636,7 +633,7 @@ class SplitLayers:
         s_dh2, s_dh1, g_dh = b_dh2, b_dh1, dh
         if hd_on:
             s_dh2, s_dh1, g_dh = ws.dslot[2 * i], ws.dslot[2 * i + 1], P(ws.dhd)
-            m._drop_add(dh, None, g_dh, M * D, drop.ph, 3 + 3 * i, f"mlp_out.{i}")
+            m._drop_add(dh, None, g_dh, M * D, "mlp_out", i)
             L("eav_sp_absmax", g_dh, M, D, D, s_dh2, st)
         # fc2: h_out = h_mid + act.W2^T + b2.  max|dh| is already in b_dh2 (left there by the producer of dh); every
         # conversion pass also yields the bias gradient of its tensor.  (fused_dh: the layer above's LayerNorm backward
@@ -676,7 +673,7 @@ class SplitLayers:
             m._reduce_ln(part, ws.np_ln, gp(f"{Lk}.layernorm_after.weight"), gp(f"{Lk}.layernorm_after.bias"), s.reduce)
             # o_proj
             if hd_on:
-                m._drop_add(dh, None, g_dh, M * D, drop.ph, 2 + 3 * i, f"attn_out.{i}")
+                m._drop_add(dh, None, g_dh, M * D, "attn_out", i)
                 L("eav_sp_absmax", g_dh, M, D, D, s_dh1, st)
             to_planes_bias(g_dh, M, D, s_dh1, ws.dhp2, gp(f"{Lk}.attention.o_proj.bias"))
         wgrad_sp(ws.dhp2, s_dh1, ws.aop[i], s_ao, gp(f"{Lk}.attention.o_proj.weight"), D, D, M)
@@ -702,8 +699,7 @@ class SplitLayers:
             elif drop.pa > 0.0:
                 # (fused_dqkv is off on such a step - delta_from_planes is false: fp32 dqkv, the conversion pass measures it)
                 L("eav_attn_bwd_sp_dropout", P(ws.qkvrow[i]), P(ws.dorow), s_qkv, b_dao, b_ds, P(ws.ao[i]), dao,
-                  P(ws.lse[i]), P(ws.delta), dqkv, b_dqkv, ws.B, H, N, hd, scale, drop.pa, m._site_seed(1 + 3 * i),
-                  drop.mk(f"attn.{i}"), drop.cnt, st)
+                  P(ws.lse[i]), P(ws.delta), dqkv, b_dqkv, ws.B, H, N, hd, scale, *drop.site("attn", i), st)
             else:
                 L("eav_attn_bwd_sp", P(ws.qkvrow[i]), None, P(ws.dorow), None, s_qkv, b_dao, b_ds,
                   P(ws.ao[i]), dao, P(ws.lse[i]), P(ws.delta), dqkv, b_dqkv, ws.B, H, N, hd, scale, st)

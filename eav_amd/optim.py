@@ -412,6 +412,15 @@ def _seeded(dsc, gout):
 HEAD_NARROW_CLASSES = 16
 
 
+def head_is_wide(algo, classes, found):
+    """Whether `classes` classes go to the wide kernels under head_algo `algo`; `found` ("the head has") words the refusal."""
+    if algo not in ("auto", "wide", "narrow"):
+        raise ValueError(f"head_algo {algo!r}: expected 'auto', 'wide' or 'narrow'")
+    if algo == "narrow" and classes > HEAD_NARROW_CLASSES:
+        raise NotImplementedError(f"head_algo 'narrow' takes at most {HEAD_NARROW_CLASSES} classes, {found} {classes}")
+    return algo == "wide" or (algo == "auto" and classes > HEAD_NARROW_CLASSES)
+
+
 def _ce_launch(scratch, scores, targets, loss, dsc, ncorrect, flag):
     """eav_ce_fwd_bwd (scratch None), or eav_ce_wide_fwd_bwd (one wave per row) with its per-row scratch."""
     B, NC = scores.shape
@@ -457,11 +466,7 @@ class CrossEntropyLoss:
         self.head_algo = os.environ.get("EAV_HEAD_ALGO", "auto")
 
     def _wide(self, classes):
-        if self.head_algo not in ("auto", "wide", "narrow"):
-            raise ValueError(f"head_algo {self.head_algo!r}: expected 'auto', 'wide' or 'narrow'")
-        if self.head_algo == "narrow" and classes > HEAD_NARROW_CLASSES:
-            raise NotImplementedError(f"head_algo 'narrow' takes at most {HEAD_NARROW_CLASSES} classes, the scores have {classes}")
-        return self.head_algo == "wide" or (self.head_algo == "auto" and classes > HEAD_NARROW_CLASSES)
+        return head_is_wide(self.head_algo, classes, "the scores have")
 
     def _scratch_for(self, scores):
         """The wide kernel's row terms for this batch size (None: the narrow kernel runs)."""

@@ -21,6 +21,11 @@ Everything is kept resident (288 GB HBM): what a backward needs is saved, nothin
 (split: the fp16 planes of the layer inputs of every GEMM and of q | k | v, the pre-activations of
 the MLP and the attention outputs / log-sum-exps; the fused attention never materialises the
 [B*H, N, N] probabilities - only the reduced test configurations with head_dim != 64 do).
+
+This module is the public model, its loading and saving, the workspace and the two launch sequences.  The rest of the encoder:
+encoder_config (what needs no device), encoder_layers (the two layer schedules), encoder_head (the classification head and
+Encoder.head), encoder_dropout (the dropout sites and generator), encoder_outputs (output_attentions / output_hidden_states /
+attention rollout).
 """
 from __future__ import annotations
 
@@ -36,8 +41,11 @@ from . import _lib, pos_interp, pos_time
 from .encoder_config import (HEAD_MAX_CLASSES, MAX_TOKENS, PROBLEM_TYPES, _check_single_label,  # noqa: F401 (re-exported)
                              ast_length_geometry, config_from_hf, config_to_hf, interpolated_geometry, make_config,
                              normalise_key, param_shapes, rank_dropout_seed, resolve_problem_type)
+from .encoder_dropout import EncoderDropout
+from .encoder_head import EncoderHead, _HeadFn
 from .encoder_layers import Fp32Layers, SplitLayers
-from .optim import HEAD_NARROW_CLASSES, BCEWithLogitsLoss, CrossEntropyLoss, MSELoss, flatten_parameters
+from .encoder_outputs import EncoderOutputs
+from .optim import BCEWithLogitsLoss, CrossEntropyLoss, MSELoss, flatten_parameters
 from .runtime import KernelFn, KernelModule, gather_batch
 
 DEFAULT_PRECISION = "split"
@@ -61,32 +69,6 @@ class _Out:
     def __init__(self, logits, loss=None, hidden_states=None, attentions=None):
         self.logits, self.loss = logits, loss
         self.hidden_states, self.attentions = hidden_states, attentions
-
-
-class _HeadFn(torch.autograd.Function):
-    """The classification head alone on cached backbone features (Encoder.head): the same kernels, in the same order and
-    with the same arguments, as the tail of _launch_forward / the start of _launch_backward."""
-
-    @staticmethod
-    def forward(ctx, feat, model, *params):
-        ctx.model, ctx.B = model, feat.shape[0]
-        hw = model._head_ws(feat.shape[0], feat.device)
-        hw.feat.copy_(feat)
-        model._begin()
-        model._head_forward(hw.feat, hw, feat.shape[0])
-        hw.token = model._token = model._token + 1
-        ctx.token = hw.token
-        return hw.logits.clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        model = ctx.model
-        hw = model._head_ws(ctx.B, dlogits.device)
-        if hw.token != ctx.token:
-            raise _lib.EavError("Encoder.head backward: activations were overwritten by a later head forward")
-        model._begin()
-        model._head_backward(dlogits.contiguous(), hw.feat, hw, ctx.B, False)
-        return (None, None, *model._trained_grads(False))
 
 
 class Encoder(KernelModule):
@@ -122,9 +104,10 @@ class Encoder(KernelModule):
         self.dropout_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
         # GEMM / attention operand precision: "split" (default: fp32-grade on the fp16 matrix cores - every operand as
         # fp16 hi + lo planes, three MFMAs per product, csrc/gemm_sp.hip + attention_sp.hip; measured against float64
-        # it is not worse than the exact-fp32 kernels and it passes the same parity bounds), "fp32" (exact-fp32 MFMA),
-        # "bf16" (bf16 MFMA operands everywhere, fp32 accumulate: ~5e-3 logit drift) or "bf16_bwd" (fp32 forward -
-        # logits unchanged - and bf16 operands for the backward products only).  EAV_ENCODER_PRECISION overrides.
+        # it is not worse than the exact-fp32 kernels and it passes the same parity bounds) or "fp32" (exact-fp32 MFMA).
+        # Comparison only, and only with the extras library: "bf16" (bf16 MFMA operands everywhere, fp32 accumulate: ~5e-3
+        # logit drift) and "bf16_bwd" (fp32 forward - logits unchanged - and bf16 operands for the backward products only).
+        # EAV_ENCODER_PRECISION overrides.
         self.precision = os.environ.get("EAV_ENCODER_PRECISION", DEFAULT_PRECISION)
         # classification Linear: "auto" (default) takes eav_dense_wide_* above HEAD_NARROW_CLASSES classes and
         # eav_dense_softmax_* up to there, "wide" forces the former at any width (tests), "narrow" the latter - it raises
@@ -176,6 +159,8 @@ class Encoder(KernelModule):
         self._main = self._st = None  # the stream of the current launch sequence and its handle (_begin)
         # the two layer schedules (encoder_layers.py); a forward takes the one of `precision`, its backward the same one
         self._fp32, self._split = Fp32Layers(self), SplitLayers(self)
+        # ... and the head, the dropout generator and the extra outputs (encoder_head.py, encoder_dropout.py, encoder_outputs.py)
+        self._head, self._dropgen, self._outputs = EncoderHead(self), EncoderDropout(self), EncoderOutputs(self)
         self._wplanes = None          # split mode: the WeightPlanes of the GEMM weights
         self._phase = "fwd"
         # multi-GPU: called as hook(lo, hi) from inside the backward whenever flat_grad[lo:hi] is final
@@ -195,10 +180,8 @@ class Encoder(KernelModule):
         # of __call__ (HF: config.output_attentions / config.output_hidden_states; from_pretrained copies them from config.json)
         self.output_attentions = False
         self.output_hidden_states = False
-        self._outs = None             # what the forward in flight collects beside the logits (_begin_outputs)
-        self._want_outs = (False, None)   # (hidden states?, "probs" | "mean" | None) of the forward in flight
-        self._rollout = False
         self._out_flags = (None, None)    # the two keywords of the call in flight (__call__)
+        self._outs = None             # the forward in flight: what it is to collect beside the logits (encoder_outputs.Outputs)
         if cfg.hidden % cfg.heads or (cfg.hidden // cfg.heads) % 4 or cfg.hidden % 4 or cfg.hidden > 1024:
             raise NotImplementedError("hidden size must be <= 1024, a multiple of 4, head_dim a multiple of 4")
         if cfg.ntok > MAX_TOKENS:
@@ -277,8 +260,7 @@ class Encoder(KernelModule):
             self.cfg.problem_type = None
         self._inferred_problem_type = None
         self._flat = None
-        self._ws = None
-        self._wss, self._hws = {}, {}
+        self._drop_workspaces()
 
     def head_parameters(self):
         return list(self.classifier.parameters())
@@ -295,10 +277,13 @@ class Encoder(KernelModule):
         self.invalidate_weight_planes()
         return super().load_state_dict(*args, **kwargs)
 
-    def _apply(self, fn, *args, **kwargs):
-        self._wplanes = None
+    def _drop_workspaces(self):
         self._ws = None
         self._wss, self._hws = {}, {}
+
+    def _apply(self, fn, *args, **kwargs):
+        self._wplanes = None
+        self._drop_workspaces()
         return super()._apply(fn, *args, **kwargs)
 
     def head_grad_ranges(self):
@@ -337,22 +322,13 @@ class Encoder(KernelModule):
         try:
             return super().__call__(*args, **kwargs)
         finally:
-            self._out_flags = (None, None)
+            self._out_flags, self._outs = (None, None), None
 
     def forward(self, x=None, labels=None, pixel_values=None, input_values=None, interpolate_pos_encoding=None):
         x = x if x is not None else (pixel_values if pixel_values is not None else input_values)
         self._require_gpu(x)
         c = self.cfg
-        output_attentions, output_hidden_states = self._out_flags
-        want_attn = self.output_attentions if output_attentions is None else bool(output_attentions)
-        want_hidden = self.output_hidden_states if output_hidden_states is None else bool(output_hidden_states)
-        if want_attn or want_hidden:
-            if torch.cuda.is_current_stream_capturing():
-                raise NotImplementedError("output_attentions / output_hidden_states allocate their results: not available "
-                                          "while the stream is capturing")
-            if want_attn and self.training and c.attention_dropout > 0.0:
-                raise NotImplementedError("output_attentions in training mode with attention_probs_dropout_prob > 0 is not "
-                                          "implemented: HF returns the dropped probabilities there")
+        outs = self._outputs.request(*self._out_flags)
         interp = self.interpolate_pos_encoding if interpolate_pos_encoding is None else bool(interpolate_pos_encoding)
         varlen = bool(self.variable_length)
         geo = None
@@ -385,21 +361,13 @@ class Encoder(KernelModule):
         self._ensure_flat()
         self._want_full = torch.is_grad_enabled() and any(
             p.requires_grad for k, p in self._pmap.items() if not k.startswith("classifier."))
-        # (attention_rollout asks for the head means instead of the probabilities)
-        self._want_outs = (bool(want_hidden), "mean" if self._rollout else ("probs" if want_attn else None))
-        try:
-            logits = KernelFn.apply(x, self, *[self._pmap[k] for k in self._names])
-        finally:
-            self._want_outs = (False, None)
-        outs, self._outs = self._outs, None
+        self._outs = outs             # (_launch_forward allocates and fills what it asks for)
+        logits = KernelFn.apply(x, self, *[self._pmap[k] for k in self._names])
+        self._outs = None
         loss = None
         if labels is not None:
             loss = self.criterion(labels)(logits, labels)
-        if outs is None:
-            return _Out(logits, loss)
-        attn = outs.probs if outs.probs is not None else outs.mean        # (mean: attention_rollout's forward)
-        return _Out(logits, loss, None if outs.hidden is None else tuple(outs.hidden.unbind(0)),
-                    None if attn is None else tuple(attn.unbind(0)))
+        return _Out(logits, loss) if outs is None else _Out(logits, loss, *outs.result())
 
     def attention_rollout(self, x, as_grid=False, interpolate_pos_encoding=None):
         """Attention rollout (Abnar & Zuidema 2020) of the readout tokens, [B, N]: how much of each input token reaches the
@@ -409,37 +377,7 @@ class Encoder(KernelModule):
         of the softmax buffer), starting from the one-hot readout row - CLS for a ViT; CLS and the distillation token for
         AST, averaged at the end as the pooled feature is their mean.  Runs under no_grad in eval mode (the mode is
         restored).  as_grid: the patch tokens only, as the forward's patch grid [B, gy, gx]."""
-        if torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("attention_rollout allocates its result: not available while the stream is capturing")
-        training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                self._rollout = True
-                try:
-                    mean = self(x, interpolate_pos_encoding=interpolate_pos_encoding, output_attentions=False,
-                                output_hidden_states=False).attentions
-                finally:
-                    self._rollout = False
-                c = self._geo
-                B, N, R = x.shape[0], c.ntok, c.nextra
-                r, r_next = torch.zeros(B, R, N, dtype=torch.float32, device=x.device), torch.empty(B, R, N, device=x.device)
-                for k in range(R):
-                    r[:, k, k].fill_(1.0)
-                st = self._begin()
-                for i in reversed(range(c.layers)):
-                    self._call("eav_rollout_step", _lib.ptr(r), _lib.ptr(mean[i]), _lib.ptr(r_next), B, R, N, st)
-                    r, r_next = r_next, r
-                out = torch.empty(B, N, dtype=torch.float32, device=x.device)
-                if R == 2:
-                    self._call("eav_pair_mean", _lib.ptr(r), _lib.ptr(out), B, N, 0, st)
-                else:
-                    out.copy_(r[:, 0])
-        finally:
-            self.train(training)
-        if as_grid:
-            return out[:, c.nextra:].reshape(B, c.ny, c.nx)
-        return out
+        return self._outputs.rollout(x, as_grid, interpolate_pos_encoding)
 
     def criterion(self, labels=None):
         """The criterion of cfg.problem_type, held on the encoder: CrossEntropyLoss, BCEWithLogitsLoss or MSELoss
@@ -488,21 +426,7 @@ class Encoder(KernelModule):
         """{site name: (site id, shape, probability)} of the dropout sites that exist for a batch of B, in HF's call order:
         "emb" [B, ntok, D] after tokens + position embeddings; per layer i "attn.i" [B, H, N, N] on the softmax
         probabilities, "attn_out.i" and "mlp_out.i" [B, N, D] on the o_proj / fc2 outputs before their residual adds."""
-        c = self.cfg
-        ph, pa = c.hidden_dropout, c.attention_dropout
-        sites = {}
-        if ph > 0.0:
-            sites["emb"] = (0, (B, c.ntok, c.hidden), ph)
-        for i in range(c.layers):
-            if pa > 0.0:
-                sites[f"attn.{i}"] = (1 + 3 * i, (B, c.heads, c.ntok, c.ntok), pa)
-            if ph > 0.0:
-                sites[f"attn_out.{i}"] = (2 + 3 * i, (B, c.ntok, c.hidden), ph)
-                sites[f"mlp_out.{i}"] = (3 + 3 * i, (B, c.ntok, c.hidden), ph)
-        return sites
-
-    def _site_seed(self, site_id):
-        return (int(self.dropout_seed) + ((site_id + 1) << 40)) & 0xFFFFFFFFFFFFFFFF
+        return self._dropgen.sites(B)
 
     def mix_dropout_rank(self, rank):
         """Data parallelism: give replica `rank` its own dropout stream (rank_dropout_seed)."""
@@ -515,47 +439,11 @@ class Encoder(KernelModule):
     def generated_dropout_masks(self, B, counter, seed=None):
         """The keep-masks the generator draws in the forward whose counter value is `counter` (the value
         forward_counter() returns after that forward), as set_dropout_masks takes them."""
-        dev = next(self.parameters()).device
-        cnt = torch.tensor(int(counter), dtype=torch.int64, device=dev)
-        old = self.dropout_seed
-        if seed is not None:
-            self.dropout_seed = seed
-        out = {}
-        try:
-            for name, (sid, shape, p) in self.dropout_sites(B).items():
-                m = torch.empty(shape, dtype=torch.uint8, device=dev)
-                _lib.call("eav_tf_dropout_mask", m.data_ptr(), m.numel(), float(p), self._site_seed(sid), cnt.data_ptr(),
-                          _lib.stream_ptr())
-                out[name] = m
-        finally:
-            self.dropout_seed = old
-        return out
+        return self._dropgen.generated_masks(B, counter, seed)
 
-    def _begin_dropout(self, ws, B, dev):
-        """Dropout state of this forward, kept on the workspace for its backward: probabilities (0 in eval mode), the
-        explicit masks or the device counter (advanced here, by a launch)."""
-        c = self.cfg
-        ph, pa = (c.hidden_dropout, c.attention_dropout) if self.training else (0.0, 0.0)
-        d = SimpleNamespace(ph=ph, pa=pa, masks=None, cnt=None)
-        if ph > 0.0 or pa > 0.0:
-            if self._dropout_masks is not None:
-                d.masks = dict(self._dropout_masks)
-                for name, (_, shape, _) in self.dropout_sites(B).items():
-                    m = d.masks.get(name)
-                    if not (isinstance(m, torch.Tensor) and m.dtype == torch.uint8 and m.device == dev
-                            and tuple(m.shape) == shape and m.is_contiguous()):
-                        raise _lib.EavError(f"set_dropout_masks: site {name!r} needs a contiguous uint8 mask {shape} on {dev}")
-            else:
-                d.cnt = self._counter(dev).data_ptr()
-                self._call("eav_counter_inc", d.cnt, self._st)
-        d.mk = (lambda name: d.masks[name].data_ptr()) if d.masks is not None else (lambda name: None)
-        ws.drop = d
-        return d
-
-    def _drop_add(self, y, resid, out, n, p, site_id, name):
-        """out = resid + Dropout(y) at a hidden-dropout site (resid None: the gate alone - the site's backward)."""
-        d = self._ws.drop
-        self._call("eav_tf_dropout_add", y, resid, out, n, float(p), self._site_seed(site_id), d.mk(name), d.cnt, self._st)
+    def _drop_add(self, y, resid, out, n, kind, layer=0):
+        """out = resid + Dropout(y) at the hidden-dropout site (kind, layer); resid None: the gate alone, the site's backward."""
+        self._call("eav_tf_dropout_add", y, resid, out, n, *self._ws.drop.site(kind, layer), self._st)
 
     @staticmethod
     def _fitted(c):
@@ -597,9 +485,8 @@ class Encoder(KernelModule):
         ws.st = [f(4, M) for _ in range(nsave)]           # mean1, rstd1, mean2, rstd2
         R = B * c.nextra
         ws.rows, ws.seqr, ws.stf = f(R, D), f(R, D), f(2, R)
-        ws.pooled, ws.hl, ws.sth = f(B, D), f(B, D), f(2, B)
-        ws.logits = f(B, c.num_labels)
-        ws.head_ws = self._head_scratch(B, f)
+        ws.pooled = f(B, D)
+        vars(ws).update(self._head.buffers(B, f, False))  # hl, sth, logits, head_ws
         if full_backward:
             ws.dh, ws.dy, ws.dao = f(M, D), f(M, D), f(M, D)
             ws.dact, ws.dqkv = f(M, FF), f(M, 3 * D)
@@ -616,10 +503,9 @@ class Encoder(KernelModule):
             ws.part_cs = f(ws.np_cs, max(FF, 3 * D))
             shapes = [(D, FF, M), (FF, D, M), (3 * D, D, M), (D, D, M), (D, c.kp, B * c.npatch)]
             ws.splitk = f(max(_lib.plain(lay.SPLITK_PLAN, m, n, k) * m * n for m, n, k in shapes))
-        ws.drows, ws.dseqr = f(R, D), f(R, D)
-        ws.dpooled, ws.dhl = f(B, D), f(B, D)
+        ws.drows = f(R, D)
+        vars(ws).update(self._head.buffers(B, f, True))   # dseqr, dpooled, dhl, part_lnr
         ws.np_lnr = _lib.plain("eav_layernorm_bwd_nparts", R)
-        ws.part_lnr = f(ws.np_lnr, 2 * D)
         return ws
 
     def _weight_keys(self):
@@ -674,79 +560,10 @@ class Encoder(KernelModule):
             self._wplanes.main = self._main
         return self._st
 
-    # ------------------------------------------------------------------ classification head (shared by the full path
-    # and by Encoder.head on cached features: same kernels, same arguments, hence bit-equal logits and gradients)
+    # ------------------------------------------------------------------ classification head (encoder_head.py)
     def _head_wide(self):
         """Whether the classification Linear runs on eav_dense_wide_* (head_algo)."""
-        algo, n = self.head_algo, self.cfg.num_labels
-        if algo not in ("auto", "wide", "narrow"):
-            raise ValueError(f"head_algo {algo!r}: expected 'auto', 'wide' or 'narrow'")
-        if algo == "narrow" and n > HEAD_NARROW_CLASSES:
-            raise NotImplementedError(f"head_algo 'narrow' takes at most {HEAD_NARROW_CLASSES} classes, the head has {n}")
-        return algo == "wide" or (algo == "auto" and n > HEAD_NARROW_CLASSES)
-
-    def _head_scratch(self, B, f):
-        """The wide backward's class slices of d loss / d feat (None where the head kernels need no scratch)."""
-        n = _lib.plain("eav_dense_wide_bwd_ws_floats", B, self.cfg.hidden, self.cfg.num_labels) if self._head_wide() else 0
-        return f(n) if n else None
-
-    def _dense_forward(self, feat, weight, bias, hw, B):
-        c, P = self.cfg, _lib.ptr
-        if self._head_wide():
-            self._call("eav_dense_wide_fwd", P(feat), weight, bias, P(hw.logits), B, c.hidden, c.num_labels, self._st)
-        else:
-            self._call("eav_dense_softmax_fwd", P(feat), weight, bias, P(hw.logits), None, B, c.hidden, c.num_labels,
-                       self._st)
-
-    def _dense_backward(self, dlogits, feat, weight, dweight, dbias, dfeat, hw, B):
-        c, P = self.cfg, _lib.ptr
-        if self._head_wide():
-            self._call("eav_dense_wide_bwd", P(dlogits), P(feat), weight, dweight, dbias, P(dfeat), P(hw.head_ws), B,
-                       c.hidden, c.num_labels, self._st)
-        else:
-            self._call("eav_dense_softmax_bwd", P(dlogits), None, P(feat), weight, dweight, dbias, P(dfeat), B, c.hidden,
-                       c.num_labels, self._st)
-
-    def _head_forward(self, feat, hw, B):
-        """feat [B, D] = the classifier's input (AST: mean of the cls / distillation rows after the final LayerNorm,
-        HF modeling_audio_spectrogram_transformer.py ASTMLPHead; ViT: the cls row after the final LayerNorm)."""
-        c, P, L, st, w = self.cfg, _lib.ptr, self._call, self._st, self._w
-        D = c.hidden
-        if c.kind == "ast":
-            sh = P(hw.sth)
-            L("eav_layernorm_fwd", P(feat), w("classifier.layernorm.weight"), w("classifier.layernorm.bias"),
-              P(hw.hl), sh, sh + 4 * B, B, D, c.eps, st)
-            self._dense_forward(hw.hl, w("classifier.dense.weight"), w("classifier.dense.bias"), hw, B)
-        else:
-            self._dense_forward(feat, w("classifier.weight"), w("classifier.bias"), hw, B)
-
-    def _head_backward(self, dlogits, feat, hw, B, need_dfeat):
-        """Head gradients into the flat gradient buffer; d loss / d feat into hw.dpooled (AST) / hw.dseqr (ViT)."""
-        c, P, L, st, w, gp = self.cfg, _lib.ptr, self._call, self._st, self._w, self._gp
-        D = c.hidden
-        if c.kind == "ast":
-            self._dense_backward(dlogits, hw.hl, w("classifier.dense.weight"), gp("classifier.dense.weight"),
-                                 gp("classifier.dense.bias"), hw.dhl, hw, B)
-            sh = P(hw.sth)
-            L("eav_layernorm_bwd", P(hw.dhl), P(feat), w("classifier.layernorm.weight"), sh, sh + 4 * B,
-              P(hw.dpooled), 0, P(hw.part_lnr), B, D, st)
-            self._reduce_ln(hw.part_lnr, _lib.plain("eav_layernorm_bwd_nparts", B), gp("classifier.layernorm.weight"),
-                            gp("classifier.layernorm.bias"))
-        else:
-            self._dense_backward(dlogits, feat, w("classifier.weight"), gp("classifier.weight"), gp("classifier.bias"),
-                                 hw.dseqr, hw, B)
-
-    def _head_ws(self, B, dev):
-        hw = self._hws.get(B)
-        if hw is None or hw.feat.device != dev or hw.logits.shape[1] != self.cfg.num_labels \
-                or hw.wide != self._head_wide():
-            c, D = self.cfg, self.cfg.hidden
-            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-            hw = self._hws[B] = SimpleNamespace(
-                feat=f(B, D), hl=f(B, D), sth=f(2, B), logits=f(B, c.num_labels), dhl=f(B, D), dpooled=f(B, D),
-                dseqr=f(B, D), part_lnr=f(_lib.plain("eav_layernorm_bwd_nparts", B * c.nextra), 2 * D), token=-1,
-                head_ws=self._head_scratch(B, f), wide=self._head_wide())
-        return hw
+        return self._head.wide()
 
     def last_features(self):
         """The classifier's input of the most recent forward ([B, hidden], a copy): constant per sample while the backbone
@@ -816,47 +633,6 @@ class Encoder(KernelModule):
             self._call("eav_pos_bicubic_bwd", P(ws.dpos_i), gpos, g, c.ny, c.nx, c.hidden, c.nextra,
                        *[P(t) for t in tb["bwd_y"]], tb["nnzy"], *[P(t) for t in tb["bwd_x"]], tb["nnzx"], self._st)
 
-    def _begin_outputs(self, B, dev):
-        """The buffers of what this forward returns beside the logits (the call's output_hidden_states / output_attentions;
-        attention_rollout's head means), fresh for every forward - the workspace is the next forward's to overwrite: hidden
-        [layers + 1, B, N, D], probs [layers, B, H, N, N], mean [layers, B, N, N], each None unless asked for."""
-        hidden, attn = self._want_outs
-        self._outs = None
-        if not hidden and attn is None:
-            return None
-        c = self._geo
-        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-        self._outs = SimpleNamespace(hidden=f(c.layers + 1, B, c.ntok, c.hidden) if hidden else None,
-                                     probs=f(c.layers, B, c.heads, c.ntok, c.ntok) if attn == "probs" else None,
-                                     mean=f(c.layers, B, c.ntok, c.ntok) if attn == "mean" else None)
-        return self._outs
-
-    def _attention_out(self, i, j, scale, qkv=None, rowp=None, slot=None):
-        """Layer i's attention probabilities into the forward's outputs, right after its attention kernel (workspace index
-        j): the fused path launches csrc/attn_probs.hip on the operands that kernel consumed - fp32 `qkv`, or the row planes
-        `rowp` with their scale `slot` - and the lse it wrote; the materialised path copies the softmax output out of ws.P[j]
-        (row stride ldn).  A no-op unless the forward asked for them."""
-        o = self._outs
-        if o is None or (o.probs is None and o.mean is None):
-            return
-        c, ws, P = self._geo, self._ws, _lib.ptr
-        N, H = c.ntok, c.heads
-        probs = None if o.probs is None else P(o.probs[i])
-        mean = None if o.mean is None else P(o.mean[i])
-        if not ws.fused:
-            if o.probs is not None:
-                o.probs[i].view(ws.B * H, N, N).copy_(ws.P[j][:, :, :N])
-            if o.mean is not None:      # the heads of an image are H slices of ws.P[j], N ldn floats apart: summed in head order
-                pad = torch.empty(ws.B, N, ws.ldn, dtype=torch.float32, device=ws.P[j].device)
-                for b in range(ws.B):
-                    self._call("eav_reduce_partials", P(ws.P[j][b * H]), H, N * ws.ldn, N * ws.ldn, 1.0 / H, P(pad[b]),
-                               self._st)
-                o.mean[i].copy_(pad[:, :, :N])
-        elif rowp is not None:
-            self._call("eav_attn_probs_sp", rowp, slot, P(ws.lse[j]), probs, mean, ws.B, H, N, c.hidden // H, scale, self._st)
-        else:
-            self._call("eav_attn_probs", qkv, P(ws.lse[j]), probs, mean, ws.B, H, N, c.hidden // H, scale, self._st)
-
     def _launch_forward(self, x):
         c = self._geo
         P, L, w = _lib.ptr, self._call, self._w
@@ -867,7 +643,7 @@ class Encoder(KernelModule):
         full = self._want_full
         lay = self._split if self.precision == "split" else self._fp32     # (an unknown precision: Fp32Layers.gemm_name raises)
         ws = self._workspace_for(B, x.device, full, lay)
-        drop = self._begin_dropout(ws, B, x.device)
+        drop = self._dropgen.begin(ws, B, x.device)
         lay.begin_forward(ws, x.device, full)
         pre = c.prefix
         # patch embedding: im2col rows x projection weight -> token rows [nextra:], then cls/dist + positions
@@ -878,10 +654,12 @@ class Encoder(KernelModule):
         L("eav_embed_finish", P(h0), w(f"{pre}.embeddings.cls_token"),
           w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None, pos, B, N, D, c.nextra, st)
         if drop.ph > 0.0:
-            self._drop_add(P(h0), None, P(h0), ws.M * D, drop.ph, 0, "emb")
-        outs = self._begin_outputs(B, x.device)
-        if outs is not None and outs.hidden is not None:
-            outs.hidden[0].view(ws.M, D).copy_(h0)
+            self._drop_add(P(h0), None, P(h0), ws.M * D, "emb")
+        outs = self._outs
+        if outs is not None:
+            outs.allocate(c, B, x.device)
+            if outs.hidden is not None:
+                outs.hidden[0].view(ws.M, D).copy_(h0)
         scale = (D // c.heads) ** -0.5
         layer = lay.layer_forward
         for i in range(c.layers):
@@ -899,7 +677,7 @@ class Encoder(KernelModule):
           sf + 4 * R, R, D, c.eps, st)
         if c.kind == "ast":
             L("eav_pair_mean", P(ws.seqr), P(ws.pooled), B, D, 0, st)
-        self._head_forward(ws.pooled if c.kind == "ast" else ws.seqr, ws, B)
+        self._head.forward(ws.pooled if c.kind == "ast" else ws.seqr, ws, B)
         self._token += 1
         self._saved = (self._token, x, full, self._active_geo)
         return self._token
@@ -925,7 +703,7 @@ class Encoder(KernelModule):
         pre = c.prefix
         R = B * c.nextra
         # ---- head
-        self._head_backward(dlogits, ws.pooled if c.kind == "ast" else ws.seqr, ws, B, full)
+        self._head.backward(dlogits, ws.pooled if c.kind == "ast" else ws.seqr, ws, B)
         if c.kind == "ast" and full:
             L("eav_pair_mean", P(ws.dseqr), P(ws.dpooled), B, D, 1, st)
         if full:
@@ -950,7 +728,7 @@ class Encoder(KernelModule):
                     self.grad_ready_hook(offs[f"{Lk}.attention.q_proj.weight"][0], last[0] + last[1])
             # ---- embeddings ("emb" dropout: dh is final here, so its gate runs in place)
             if drop.ph > 0.0:
-                self._drop_add(dh, None, dh, M * D, drop.ph, 0, "emb")
+                self._drop_add(dh, None, dh, M * D, "emb")
             # the position table's gradient: straight into the stored table's, or - the table fitted to this forward's patch
             # grid - into ws.dpos_i and through the adjoint of the fit
             fitted = self._fitted(c) != (None, None)

@@ -53,7 +53,7 @@ def counter(c):
 
 
 def site_seed(k):
-    return (k + 1) << 40    # Encoder._site_seed with dropout_seed 0
+    return (k + 1) << 40    # encoder_dropout.site_seed with dropout_seed 0
 
 
 def dump_mask(n, p, seed, cnt, what="dumped mask"):

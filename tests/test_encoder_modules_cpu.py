@@ -6,7 +6,8 @@ import re
 
 import pytest
 
-from eav_amd import encoder_config as EC, encoder_layers as EL, transformer as T
+from eav_amd import (encoder_config as EC, encoder_dropout as ED, encoder_head as EH, encoder_layers as EL,
+                     encoder_outputs as EO, optim, transformer as T)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MOVED = ("HEAD_MAX_CLASSES", "MAX_TOKENS", "PROBLEM_TYPES", "make_config", "config_from_hf", "config_to_hf", "_check_single_label",
@@ -64,6 +65,12 @@ def test_encoder_keeps_its_attribute_surface_and_deepcopies_its_schedules(monkey
     # both schedules exist from construction on, the precision picks one per forward
     assert isinstance(model._fp32, EL.Fp32Layers) and isinstance(model._split, EL.SplitLayers)
     assert model._fp32.m is model and model._split.m is model and model._split.streams.m is model
+    # ... and so do the head, the dropout generator and the extra outputs
+    assert isinstance(model._head, EH.EncoderHead) and isinstance(model._dropgen, ED.EncoderDropout)
+    assert isinstance(model._outputs, EO.EncoderOutputs)
+    assert model._head.m is model and model._dropgen.m is model and model._outputs.m is model
+    assert model._outs is None and model._out_flags == (None, None)
+    assert not hasattr(model, "_want_outs") and not hasattr(model, "_rollout")
     model.precision = "no such precision"
     with pytest.raises(ValueError, match="unknown precision 'no such precision'"):
         model._fp32.gemm_name()
@@ -77,7 +84,64 @@ def test_encoder_keeps_its_attribute_surface_and_deepcopies_its_schedules(monkey
     twin = copy.deepcopy(fresh)
     assert twin._fp32.m is twin and twin._split.m is twin and twin._split.streams.m is twin
     assert twin._split is not fresh._split and twin._fp32 is not fresh._fp32 and fresh._split.m is fresh
+    assert twin._head.m is twin and twin._dropgen.m is twin and twin._outputs.m is twin
+    assert twin._head is not fresh._head and twin._dropgen is not fresh._dropgen and twin._outputs is not fresh._outputs
+    assert fresh._head.m is fresh and fresh._dropgen.m is fresh and fresh._outputs.m is fresh
     assert twin._wplanes is None and twin._wss == {} and twin._wss is not fresh._wss
     model._wplanes = sentinel = object()
     model.reset_head(model.classifier.weight.detach()[:3], model.classifier.bias.detach()[:3])
     assert model._wplanes is sentinel and model._flat is None and model._ws is None and model._hws == {}
+
+
+def test_dropout_sites_come_from_one_table():
+    cfg = T.make_config("vit", hidden=32, layers=2, heads=2, ff=64, image=32, hidden_dropout=0.1, attention_dropout=0.2)
+    model = T.Encoder(cfg)
+    B, N, D, H = 3, cfg.ntok, 32, 2
+    hid, att = (B, N, D), (B, H, N, N)
+    table = {"emb": (0, hid, 0.1),
+             "attn.0": (1, att, 0.2), "attn_out.0": (2, hid, 0.1), "mlp_out.0": (3, hid, 0.1),
+             "attn.1": (4, att, 0.2), "attn_out.1": (5, hid, 0.1), "mlp_out.1": (6, hid, 0.1)}
+    sites = model.dropout_sites(B)
+    assert sites == table and list(sites) == list(table)                 # (HF's call order)
+    model.cfg.attention_dropout = 0.0
+    assert model.dropout_sites(B) == {k: v for k, v in table.items() if not k.startswith("attn.")}
+    model.cfg.attention_dropout, model.cfg.hidden_dropout = 0.2, 0.0
+    assert model.dropout_sites(B) == {k: v for k, v in table.items() if k.startswith("attn.")}
+    # the kernel arguments of a site: its probability, the seed of its id, no mask, the counter's address
+    for seed in (0, 12345, (1 << 64) - 1):
+        d = ED.DropState(seed, 0.1, 0.2, cnt=4242)
+        for name, (sid, _, p) in table.items():
+            kind, _, layer = name.partition(".")
+            assert ED.site_id(kind, int(layer or 0)) == sid and ED.site_name(kind, int(layer or 0)) == name
+            assert d.site(kind, int(layer or 0)) == (p, (seed + ((sid + 1) << 40)) % (1 << 64), None, 4242), name
+    assert d.site("emb") == d.site("emb", 0)
+
+
+def test_head_routing_is_one_function():
+    """optim.head_is_wide answers, and refuses, as Encoder._head_wide and CrossEntropyLoss._wide did each on their own."""
+    def old(algo, n, last):
+        if algo not in ("auto", "wide", "narrow"):
+            raise ValueError(f"head_algo {algo!r}: expected 'auto', 'wide' or 'narrow'")
+        if algo == "narrow" and n > 16:
+            raise NotImplementedError(f"head_algo 'narrow' takes at most 16 classes, {last} {n}")
+        return algo == "wide" or (algo == "auto" and n > 16)
+
+    def outcome(fn):
+        try:
+            return fn()
+        except (ValueError, NotImplementedError) as e:
+            return type(e), str(e)
+
+    crit = optim.CrossEntropyLoss()
+    for n in (16, 17):
+        enc = T.Encoder(T.make_config("vit", hidden=32, layers=1, heads=2, ff=64, image=32, num_labels=n))
+        for algo in ("auto", "wide", "narrow", "mfma"):
+            enc.head_algo = crit.head_algo = algo
+            for last, caller in (("the head has", enc._head_wide), ("the scores have", lambda: crit._wide(n))):
+                want = outcome(lambda: old(algo, n, last))
+                assert outcome(lambda: optim.head_is_wide(algo, n, last)) == want, (algo, n, last)
+                assert outcome(caller) == want, (algo, n, last)
+    assert optim.head_is_wide("auto", 16, "") is False and optim.head_is_wide("auto", 17, "") is True
+    assert outcome(lambda: optim.head_is_wide("narrow", 17, "the head has")) == (
+        NotImplementedError, "head_algo 'narrow' takes at most 16 classes, the head has 17")
+    assert outcome(lambda: optim.head_is_wide("mfma", 16, "the head has"))[0] is ValueError
