@@ -216,7 +216,10 @@ PLAIN = {
     "eav_grad_chunk_elems": ([], _i64),
     "eav_grad_nchunks": ([_i64], _i64),
     "eav_layernorm_bwd_nparts": ([_i], _i),
+    "eav_gemm_f32_plan": ([_i, _i, _i], _i),
     "eav_gemm_f32_splitk_plan": ([_i, _i, _i], _i),
+    "eav_gemm_f32_splitk_nz": ([_i, _i, _i], _i),
+    "eav_gemm_f32_splitk_reduce": ([_i, _i, _i], _i),
     "eav_colsum_nparts": ([_i], _i),
     "eav_sp_kpad": ([_i], _i),
     "eav_sp_convert_colsum_nparts": ([_i], _i),

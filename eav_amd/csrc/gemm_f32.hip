@@ -273,14 +273,45 @@ int launch_bm(const GemmArgs& g, int batch, hipStream_t st) {
 // 128-row tiles by default; 64-row tiles when the 128-row grid would leave the chip under-filled (e.g. the
 // N = 768 projections at M = 9712: 456 blocks for 768 resident slots) and for outputs of at most 64 rows (the 40 x 160
 // weight gradients of the ShallowConvNet transformer)
+// (the heuristic lives in gemm_tile_bm / gemm_tile_bn alone: eav_gemm_f32_plan reports exactly what is launched)
+int gemm_tile_bn(int N) { return N <= 64 ? 64 : 128; }
+int gemm_tile_bm(int M, int N, int batch) {
+  const int64_t blocks128 = (int64_t)cdiv(M, 128) * cdiv(N, gemm_tile_bn(N)) * batch;
+  return (blocks128 < 640 || M <= 64) ? 64 : 128;
+}
+
 template <int BN, bool TA, bool TB>
 int launch(const GemmArgs& g, int batch, hipStream_t st) {
-  const int64_t blocks128 = (int64_t)cdiv(g.M, 128) * cdiv(g.N, BN) * batch;
-  if (blocks128 < 640 || g.M <= 64) return launch_bm<64, BN, TA, TB>(g, batch, st);
+  if (gemm_tile_bm(g.M, g.N, batch) == 64) return launch_bm<64, BN, TA, TB>(g, batch, st);
   return launch_bm<128, BN, TA, TB>(g, batch, st);
 }
 
+// the eight (BN, TA, TB) forms of launch<>
+int launch_any(const GemmArgs& g, int transA, int transB, int batch, hipStream_t st) {
+  const int v = (gemm_tile_bn(g.N) == 64 ? 4 : 0) | (transA ? 2 : 0) | (transB ? 1 : 0);
+  switch (v) {
+    case 0: return launch<128, false, false>(g, batch, st);
+    case 1: return launch<128, false, true>(g, batch, st);
+    case 2: return launch<128, true, false>(g, batch, st);
+    case 3: return launch<128, true, true>(g, batch, st);
+    case 4: return launch<64, false, false>(g, batch, st);
+    case 5: return launch<64, false, true>(g, batch, st);
+    case 6: return launch<64, true, false>(g, batch, st);
+    default: return launch<64, true, true>(g, batch, st);
+  }
+}
+
+// split-K: slice length (a multiple of BK; 0 = unsplit) and the number of slices actually launched (<= nsplit)
+int splitk_slice(int K, int nsplit) { return nsplit > 1 ? cdiv(cdiv(K, nsplit), BK) * BK : 0; }
+int splitk_nz(int K, int nsplit) { return nsplit > 1 ? cdiv(K, splitk_slice(K, nsplit)) : 1; }
+bool splitk_wide_reduce(int nz, int64_t n) { return nz >= 16 && n <= (1 << 18); }
+
 }  // namespace
+
+extern "C" int eav_gemm_f32_plan(int M, int N, int batch) {
+  if (M <= 0 || N <= 0 || batch <= 0) return 0;
+  return gemm_tile_bm(M, N, batch) * 1000 + gemm_tile_bn(N);
+}
 
 extern "C" int eav_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                             int transA, int transB, int batch, int heads, int64_t sAb, int64_t sAh, int64_t sBb,
@@ -297,19 +328,7 @@ extern "C" int eav_gemm_f32(const float* A, const float* B, float* C, int M, int
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr; g.H = heads;
   g.sAb = sAb; g.sAh = sAh; g.sBb = sBb; g.sBh = sBh; g.sCb = sCb; g.sCh = sCh;
   g.alpha = alpha; g.gelu = gelu; g.accumulate = accumulate; g.ksplit = 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool narrow = N <= 64;
-  const int v = (narrow ? 4 : 0) | (transA ? 2 : 0) | (transB ? 1 : 0);
-  switch (v) {
-    case 0: launch<128, false, false>(g, batch, st); break;
-    case 1: launch<128, false, true>(g, batch, st); break;
-    case 2: launch<128, true, false>(g, batch, st); break;
-    case 3: launch<128, true, true>(g, batch, st); break;
-    case 4: launch<64, false, false>(g, batch, st); break;
-    case 5: launch<64, false, true>(g, batch, st); break;
-    case 6: launch<64, true, false>(g, batch, st); break;
-    default: launch<64, true, true>(g, batch, st); break;
-  }
+  launch_any(g, transA, transB, batch, (hipStream_t)stream);
   EAV_CHECK_LAUNCH("eav_gemm_f32");
   return EAV_OK;
 }
@@ -324,6 +343,19 @@ extern "C" int eav_gemm_f32_splitk_plan(int M, int N, int K) {
   if (ns > maxs) ns = maxs;
   if (ns > 64) ns = 64;
   return ns < 1 ? 1 : ns;
+}
+
+// What eav_gemm_f32_splitk launches for a shape: _nz = the K slices that run (the `batch` of eav_gemm_f32_plan for its
+// tile form; <= the plan's nsplit, which only sizes ws), _reduce = 0 no reduce pass (one slice, written to C directly),
+// 1 splitk_reduce_kernel, 2 splitk_reduce_wide_kernel
+extern "C" int eav_gemm_f32_splitk_nz(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  return splitk_nz(K, eav_gemm_f32_splitk_plan(M, N, K));
+}
+extern "C" int eav_gemm_f32_splitk_reduce(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  if (eav_gemm_f32_splitk_plan(M, N, K) <= 1) return 0;
+  return splitk_wide_reduce(eav_gemm_f32_splitk_nz(M, N, K), (int64_t)M * N) ? 2 : 1;
 }
 
 __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int nsplit, int64_t n, float* __restrict__ out) {
@@ -368,24 +400,14 @@ extern "C" int eav_gemm_f32_splitk(const float* A, const float* B, float* C, flo
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = N; g.ldr = 0; g.H = 1;
   g.sAb = g.sAh = g.sBb = g.sBh = g.sCb = g.sCh = 0;
   g.alpha = 1.f; g.gelu = 0; g.accumulate = 0;
-  g.ksplit = nsplit > 1 ? cdiv(cdiv(K, nsplit), BK) * BK : 0;
-  const int nz = nsplit > 1 ? cdiv(K, g.ksplit) : 1;
+  g.ksplit = splitk_slice(K, nsplit);
+  const int nz = splitk_nz(K, nsplit);
   hipStream_t st = (hipStream_t)stream;
-  const int v = (N <= 64 ? 4 : 0) | (transA ? 2 : 0) | (transB ? 1 : 0);
-  switch (v) {
-    case 0: launch<128, false, false>(g, nz, st); break;
-    case 1: launch<128, false, true>(g, nz, st); break;
-    case 2: launch<128, true, false>(g, nz, st); break;
-    case 3: launch<128, true, true>(g, nz, st); break;
-    case 4: launch<64, false, false>(g, nz, st); break;
-    case 5: launch<64, false, true>(g, nz, st); break;
-    case 6: launch<64, true, false>(g, nz, st); break;
-    default: launch<64, true, true>(g, nz, st); break;
-  }
+  launch_any(g, transA, transB, nz, st);
   EAV_CHECK_LAUNCH("eav_gemm_f32_splitk");
   if (nsplit > 1) {
     const int64_t n = (int64_t)M * N;
-    if (nz >= 16 && n <= (1 << 18))
+    if (splitk_wide_reduce(nz, n))
       hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)cdiv64(n * 2, 256)), dim3(256), 0, st, ws, nz, n, C);
     else
       hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)cdiv64(n, 1024)), dim3(256), 0, st, ws, nz, n, C);

@@ -329,9 +329,17 @@ int eav_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, 
                  int transA, int transB, int batch, int heads, int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh,
                  int64_t sCb, int64_t sCh, float alpha, const float* bias, int gelu, float* pre, const float* resid,
                  int ldr, int accumulate, void* stream);
+/* The tile form eav_gemm_f32 launches for an [M,N] output over `batch` slabs, as BM * 1000 + BN (BM, BN in {64, 128}):
+ * the single statement of the heuristic, shared with the launcher (0 for non-positive arguments). */
+int eav_gemm_f32_plan(int M, int N, int batch);
 /* Split-K form for weight gradients: C[M,N] = opA(A).opB(B) with the contraction cut into
- * eav_gemm_f32_splitk_plan(M,N,K) slices; ws holds [nsplit][M][N] partials, summed in fixed order. */
+ * eav_gemm_f32_splitk_plan(M,N,K) slices; ws holds [nsplit][M][N] partials, summed in fixed order.
+ * eav_gemm_f32_splitk_nz = the slices that actually run (<= nsplit; the tile form is eav_gemm_f32_plan(M, N, nz));
+ * eav_gemm_f32_splitk_reduce = the pass that sums them: 0 none (one slice, written to C), 1 plain, 2 wide (8 lanes per
+ * float4 of a small output with many slices). */
 int eav_gemm_f32_splitk_plan(int M, int N, int K);
+int eav_gemm_f32_splitk_nz(int M, int N, int K);
+int eav_gemm_f32_splitk_reduce(int M, int N, int K);
 int eav_gemm_f32_splitk(const float* A, const float* B, float* C, float* ws, int M, int N, int K, int lda, int ldb,
                         int transA, int transB, void* stream);
 /* fp32-grade GEMM on the fp16 matrix cores with split operands (csrc/gemm_sp.hip) - the same call sites as eav_gemm_f32

@@ -161,6 +161,10 @@ def test_criteria(kind):
     bt = torch.zeros(130, 4097, device="cuda")
     crit(big, bt)                                                          # the scratch of this batch size exists now
     torch.cuda.synchronize()
+    # (device tensors that earlier tests left in reference cycles go now, not at a collection between the two readings:
+    # with more tests in front of this one such a collection fell here and freed 160 MB in the middle)
+    import gc
+    gc.collect()
     before = torch.cuda.memory_allocated()
     with torch.no_grad():
         l0 = crit(big.requires_grad_(True), bt)
