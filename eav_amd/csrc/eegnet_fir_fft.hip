@@ -17,6 +17,8 @@
 //   with D_f = dy_c + i dy_{c+1} of a block (704 samples, zero-padded): Re(conj(D) s') = d_c s'_c + d_{c+1} s'_{c+1}.
 //   The spectra are accumulated per workgroup in registers (wave f owns filter f), written once, summed over the
 //   workgroups in a fixed order and transformed back by a finishing kernel - bit-reproducible run to run.
+// The last block of a row is usually short (144 of 704 outputs at 10000 samples); where two such tails fit into the two
+// halves of one segment they share its transforms (`Units` below).
 //
 // The 1024-point complex FFT runs inside ONE wave, 16 points per lane (element j of lane l = index l + 64 j on input and
 // output), as radix 16 x 16 x 4 with one exchange through a wave-private LDS buffer and one between lanes:
@@ -31,6 +33,7 @@
 // tests/test_fir_fft_layout_cpu.py against the lane groups of MI355X_MICROARCH.md section LDS).  No workgroup barrier
 // inside the transform.
 #include <algorithm>
+#include <type_traits>
 
 #include "eav_common.h"
 #include "../../include/eav_hip.h"
@@ -244,6 +247,78 @@ __device__ __forceinline__ void load_segment(v2f (&v)[16], const float* __restri
   }
 }
 
+// Unit list of both kernels.  A row of S samples is nblk = ceil(S / 704) blocks, the last one with Lt = S - 704 (nblk - 1)
+// outputs.  A tail block needs Lt + klen - 1 input samples; where that is at most 512, TWO tails share one transform: tail
+// A in slots 0 .. 511 (register rows 0 .. 7 of every lane), tail B in slots 512 .. 1023 (rows 8 .. 15).  A's outputs
+// j < Lt read slots j .. j + klen - 1 <= 511 and B's 512 + j .. <= 1023: no wrap and no cross-talk, and in the weight
+// gradient the lags k < klen of IFFT(Z conj(D)) hold A A and B B terms only.  Then the list is
+//   main units   u < nmain = B npair nmb: (sample, pair, block) with block < nmb = nblk - 1, all of them whole blocks
+//   packed units nmain + p, p < npk = ceil(B npair / 2): the tails 2 p and 2 p + 1 of the flattened (sample npair + pair)
+//                index - possibly of two samples; with an odd count the last one stands alone, its upper half empty.
+// Otherwise (10000 samples pack: Lt = 144; 500 or 918 samples at 300 taps do not) nmb = nblk, npk = 0 and the tail is an
+// ordinary ragged unit.
+struct Units {
+  int npair, nmb, nmain, ntail, npk, t0t;      // t0t: first output of a packed tail
+  __host__ __device__ int total() const { return nmain + npk; }
+};
+__host__ __device__ inline Units fft_units(int B, int C, int S, int klen) {
+  Units q;
+  q.npair = (C + 1) / 2;
+  const int nblk = (S + LB - 1) / LB, lt = S - (nblk - 1) * LB;
+  const bool pack = lt + klen - 1 <= NF / 2;
+  q.nmb = pack ? nblk - 1 : nblk;
+  q.nmain = B * q.npair * q.nmb;
+  q.ntail = pack ? B * q.npair : 0;
+  q.npk = (q.ntail + 1) / 2;
+  q.t0t = q.nmb * LB;
+  return q;
+}
+// the two tails of packed unit p: (sample, first electrode) of each; the second may be missing
+struct Tails {
+  int b0, c0, b1, c1;
+  bool ex1;
+};
+__device__ __forceinline__ Tails decode_tails(const Units& q, int p) {
+  Tails t;
+  const int pr0 = (2 * p) % q.npair;
+  t.b0 = (2 * p) / q.npair;
+  t.c0 = 2 * pr0;
+  t.ex1 = 2 * p + 1 < q.ntail;
+  const bool wrap = pr0 + 1 == q.npair;
+  t.b1 = wrap ? t.b0 + 1 : t.b0;
+  t.c1 = wrap ? 0 : 2 * (pr0 + 1);
+  return t;
+}
+// one half of a packed segment: rows j0 .. j0 + 7 = 512 slots of one tail's electrode pair, zero outside [0, S)
+__device__ __forceinline__ void load_half(v2f (&v)[16], int j0, const float* __restrict__ xrow, bool ex, bool has1, int S,
+                                          int tbase, int lane) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int t = tbase + lane + 64 * j;
+    const bool ok = ex && t >= 0 && t < S;
+    v[j0 + j].x = ok ? xrow[t] : 0.f;
+    v[j0 + j].y = (ok && has1) ? xrow[S + t] : 0.f;
+  }
+}
+
+// rows J0 .. J0 + NR - 1 of a ragged block or of one half of a packed unit: the outputs tl + 64 j < S of electrode c0 (and
+// of c0 + 1 where the pair has one) are stored, and only they enter the BatchNorm sums
+template <bool STATS, int J0, int NR>
+__device__ __forceinline__ void store_rows(const v2f (&v)[16], float* __restrict__ dst, int tl, int S, bool has1, float& a1,
+                                           float& a2) {
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    if (tl + 64 * j < S) {
+      EAV_STG(dst + 64 * j, v[J0 + j].x);
+      if (STATS) a1 += v[J0 + j].x, a2 += v[J0 + j].x * v[J0 + j].x;
+      if (has1) {
+        EAV_STG(dst + S + 64 * j, v[J0 + j].y);
+        if (STATS) a1 += v[J0 + j].y, a2 += v[J0 + j].y * v[J0 + j].y;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ fwd
 // Work unit = (sample b, electrode pair, block of 704 outputs), one wave each; the NWF = 12 waves of a workgroup (3 per
 // SIMD) share the 8 filter spectra H_f = conj(FFT(w_f)) / 1024, computed by the workgroup itself (wave f < 8 transforms
@@ -256,7 +331,7 @@ template <bool STATS>
 __global__ __launch_bounds__(64 * NWF, 1) void fir_fft_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ xidx,
                                                                   const float* __restrict__ w1, float* __restrict__ y1,
                                                                   float* __restrict__ part, int C, int S, int klen, int padl,
-                                                                  int npair, int nblk, int nunits) {
+                                                                  Units q, int nrows) {
   __shared__ v2f smem[F1 * HB + NWF * WBUF + TWSZ];
   v2f* Hs = smem;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave id as a scalar
@@ -277,92 +352,111 @@ __global__ __launch_bounds__(64 * NWF, 1) void fir_fft_fwd_kernel(const float* _
   }
   __syncthreads();
   float sacc = 0.f;      // lane f: sum of filter f's outputs, lane 8 + f: sum of their squares (this wave's share)
-  const int wgid = blockIdx.x * NWF + wave, nwaves = gridDim.x * NWF;
-  // the NEXT unit's input segment is fetched into registers before the eight inverse transforms of the current one
-  v2f nx[16];
-  auto fetch = [&](int u, v2f (&dst)[16]) {
-    const int blk = u % nblk, pr = (u / nblk) % npair, b = u / (nblk * npair);
-    const int c0 = 2 * pr;
-    const float* xrow = x + ((xidx ? xidx[b] : (int64_t)b) * C + c0) * S;
-    load_segment(dst, xrow, c0 + 1 < C, S, blk * LB - padl, lane);
-  };
-  if (wgid < nunits) fetch(wgid, nx);
-  for (int u = wgid; u < nunits; u += nwaves) {
-    const int blk = u % nblk, pr = (u / nblk) % npair, b = u / (nblk * npair);
-    const int c0 = 2 * pr, t0 = blk * LB;
-    const bool has1 = c0 + 1 < C;
+  const int wgid = blockIdx.x * NWF + wave, nwaves = gridDim.x * NWF, nunits = q.total();
+  // The deal: nunits / nwaves full rounds (round r: unit r nwaves + wgid), then the remainder slot by slot - extra e goes
+  // to workgroup e % gridDim.x, wave slot e / gridDim.x.  Consecutive wave slots of a workgroup sit on consecutive SIMDs,
+  // so the extras of a CU spread over its four SIMDs: 13920 units on 256 x 12 waves are 4 rounds + 1632 extras = 12 + at
+  // most 2 per SIMD (dealt wave after wave, the extras would fill three waves of ONE SIMD first).
+  const int rounds = nunits / nwaves, xunit = rounds * nwaves + wave * (int)gridDim.x + (int)blockIdx.x;
+  const int cnt = rounds + (xunit < nunits ? 1 : 0);
+  auto unit_of = [&](int i) { return i < rounds ? i * nwaves + wgid : xunit; };
+  // Units ascend along a wave's list and the packed tails end the unit list, so a wave runs its main units, then its packed
+  // ones, in a loop of their own: the loop of whole and ragged blocks stays what it was, and the registers are the larger
+  // of the two loops, not their sum (one loop with both kinds of unit took 166 VGPRs and spilled).
+  int nmine = 0;
+  while (nmine < cnt && unit_of(nmine) < q.nmain) ++nmine;
+  auto run = [&](auto pk, int i0, int i1) {
+    constexpr bool PK = decltype(pk)::value;
+    const int tbt = q.t0t - padl;      // packed tails: slot 0 of each half
+    // the NEXT main unit's input segment is fetched into registers before the eight inverse transforms of the current one
+    v2f nx[16];
+    auto fetch = [&](int u, v2f (&dst)[16]) {
+      if (!PK) {
+        const int blk = u % q.nmb, pr = (u / q.nmb) % q.npair, b = u / (q.nmb * q.npair);
+        const int c0 = 2 * pr;
+        const float* xrow = x + ((xidx ? xidx[b] : (int64_t)b) * C + c0) * S;
+        load_segment(dst, xrow, c0 + 1 < C, S, blk * LB - padl, lane);
+      } else {
+        const Tails tl = decode_tails(q, u - q.nmain);
+        const int b1 = tl.ex1 ? tl.b1 : tl.b0;      // (a missing tail reads nothing: any valid row will do)
+        load_half(dst, 0, x + ((xidx ? xidx[tl.b0] : (int64_t)tl.b0) * C + tl.c0) * S, true, tl.c0 + 1 < C, S, tbt, lane);
+        load_half(dst, 8, x + ((xidx ? xidx[b1] : (int64_t)b1) * C + tl.c1) * S, tl.ex1, tl.c1 + 1 < C, S, tbt, lane);
+      }
+    };
+    if (!PK && i0 < i1) fetch(unit_of(i0), nx);
+    for (int i = i0; i < i1; ++i) {
+      const int u = unit_of(i);
+      int b, c0, t0;
+      Tails tl = {0, 0, 0, 0, false};
+      if (!PK) {
+        const int blk = u % q.nmb, pr = (u / q.nmb) % q.npair;
+        b = u / (q.nmb * q.npair), c0 = 2 * pr, t0 = blk * LB;
+      } else {
+        tl = decode_tails(q, u - q.nmain);
+        b = tl.b0, c0 = tl.c0, t0 = q.t0t;
+      }
+      const bool has1 = c0 + 1 < C;
+      if (PK) {      // (a wave has one packed unit, seldom two: loaded where it is needed, no registers held for the next)
+        fetch(u, v);
+      } else {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = nx[j];
-    if (u + nwaves < nunits) fetch(u + nwaves, nx);
-    fft1024<false>(v, xb, lane, tw);
-    v2f z[16];
+        for (int j = 0; j < 16; ++j) v[j] = nx[j];
+        if (i + 1 < i1) fetch(unit_of(i + 1), nx);
+      }
+      fft1024<false>(v, xb, lane, tw);
+      v2f z[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) z[j] = v[j];
+      for (int j = 0; j < 16; ++j) z[j] = v[j];
 #pragma unroll 1
-    for (int f = 0; f < F1; ++f) {
-      const v2f* hp = Hs + f * HB + lane;       // bins lane + 64 j, j < 8
-      const v2f* hm = Hs + f * HB - lane;       // bins 1024 - (lane + 64 j), j >= 8: the conjugates
+      for (int f = 0; f < F1; ++f) {
+        const v2f* hp = Hs + f * HB + lane;       // bins lane + 64 j, j < 8
+        const v2f* hm = Hs + f * HB - lane;       // bins 1024 - (lane + 64 j), j >= 8: the conjugates
 #pragma unroll
-      for (int j = 0; j < 8; j += 2) cmul2<false>(z[j], lds_ld(hp + 64 * j), z[j + 1], lds_ld(hp + 64 * j + 64), v[j], v[j + 1]);
+        for (int j = 0; j < 8; j += 2)
+          cmul2<false>(z[j], lds_ld(hp + 64 * j), z[j + 1], lds_ld(hp + 64 * j + 64), v[j], v[j + 1]);
 #pragma unroll
-      for (int j = 8; j < 16; j += 2)
-        cmul2<true>(z[j], lds_ld(hm + (NF - 64 * j)), z[j + 1], lds_ld(hm + (NF - 64 * j - 64)), v[j], v[j + 1]);
-      fft1024<true>(v, xb, lane, tw);
-      float* dst = y1 + (((int64_t)b * F1 + f) * C + c0) * S + t0 + lane;
-      float a1, a2;
-      if (!STATS) {      // firstBN in eval mode: no batch statistics to collect (STATS = false: stat_part is not written)
-        a1 = a2 = 0.f;
-        if (has1 && t0 + LB <= S) {
+        for (int j = 8; j < 16; j += 2)
+          cmul2<true>(z[j], lds_ld(hm + (NF - 64 * j)), z[j + 1], lds_ld(hm + (NF - 64 * j - 64)), v[j], v[j + 1]);
+        fft1024<true>(v, xb, lane, tw);
+        float* dst = y1 + (((int64_t)b * F1 + f) * C + c0) * S + t0 + lane;
+        float a1 = 0.f, a2 = 0.f;
+        if (PK) {      // two tails: rows 0 .. 7 are A's outputs, rows 8 .. 15 B's (those at or past S are not outputs)
+          store_rows<STATS, 0, 8>(v, dst, t0 + lane, S, has1, a1, a2);
+          if (tl.ex1)
+            store_rows<STATS, 8, 8>(v, y1 + (((int64_t)tl.b1 * F1 + f) * C + tl.c1) * S + t0 + lane, t0 + lane, S,
+                                    tl.c1 + 1 < C, a1, a2);
+        } else if (has1 && t0 + LB <= S) {      // a whole block of a full pair (14 of 15, or every main unit): no predicates
+          v2f s1 = (v2f){0.f, 0.f}, s2 = (v2f){0.f, 0.f};
 #pragma unroll
           for (int j = 0; j < NROW; ++j) {
             EAV_STG(dst + 64 * j, v[j].x);
             EAV_STG(dst + S + 64 * j, v[j].y);
+            if (STATS) {
+              s1 += v[j];
+              s2 = fma2(v[j], v[j], s2);
+            }
           }
+          a1 = s1.x + s1.y;
+          a2 = s2.x + s2.y;
         } else {
-#pragma unroll
-          for (int j = 0; j < NROW; ++j) {
-            if (t0 + lane + 64 * j < S) {
-              EAV_STG(dst + 64 * j, v[j].x);
-              if (has1) EAV_STG(dst + S + 64 * j, v[j].y);
-            }
-          }
+          store_rows<STATS, 0, NROW>(v, dst, t0 + lane, S, has1, a1, a2);
         }
-        continue;
+        if (!STATS) continue;      // firstBN in eval mode: no batch statistics to collect (stat_part is not written)
+        a1 = wave_total_dpp(a1);
+        a2 = wave_total_dpp(a2);
+        if (lane == f) sacc += a1;
+        if (lane == 8 + f) sacc += a2;
       }
-      if (has1 && t0 + LB <= S) {      // a whole block of a full pair (14 of 15): no predicates
-        v2f s1 = (v2f){0.f, 0.f}, s2 = (v2f){0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < NROW; ++j) {
-          EAV_STG(dst + 64 * j, v[j].x);
-          EAV_STG(dst + S + 64 * j, v[j].y);
-          s1 += v[j];
-          s2 = fma2(v[j], v[j], s2);
-        }
-        a1 = s1.x + s1.y;
-        a2 = s2.x + s2.y;
-      } else {
-        a1 = 0.f, a2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NROW; ++j) {
-          if (t0 + lane + 64 * j < S) {
-            EAV_STG(dst + 64 * j, v[j].x);
-            a1 += v[j].x;
-            a2 += v[j].x * v[j].x;
-            if (has1) {
-              EAV_STG(dst + S + 64 * j, v[j].y);
-              a1 += v[j].y;
-              a2 += v[j].y * v[j].y;
-            }
-          }
-        }
-      }
-      a1 = wave_total_dpp(a1);
-      a2 = wave_total_dpp(a2);
-      if (lane == f) sacc += a1;
-      if (lane == 8 + f) sacc += a2;
     }
+  };
+  run(std::false_type{}, 0, nmine);
+  run(std::true_type{}, nmine, cnt);
+  // (a wave without units writes its zeros; so do the rows behind the grid's own, which the sizing export counts because it
+  // does not know klen and hence not whether the tails pack)
+  if (STATS && lane < 16) {
+    part[wgid * 16 + lane] = sacc;
+    for (int r = wgid + nwaves; r < nrows; r += nwaves) part[r * 16 + lane] = 0.f;
   }
-  if (STATS && lane < 16) part[wgid * 16 + lane] = sacc;      // (a wave without units writes its zeros)
 }
 
 // ---------------------------------------------------------------------------------------------------------------- wgrad
@@ -373,7 +467,7 @@ template <bool PLAIN>
 __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __restrict__ x, const int64_t* __restrict__ xidx,
                                                                const float* __restrict__ y1, const float* __restrict__ g1,
                                                                const float* __restrict__ bnp, float* __restrict__ spec,
-                                                               int C, int S, int padl, int npair, int nblk, int nunits) {
+                                                               int C, int S, int padl, Units q) {
   __shared__ v2f smem[8 * NF + 8 * WBUF + TWSZ];
   v2f* zb = smem;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = wave;
@@ -385,7 +479,10 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
 #pragma unroll
   for (int j = 0; j < 16; ++j) acc[j] = (v2f){0.f, 0.f};
   v2f v[16];
-  const int ngroups = (nunits + 7) >> 3;
+  // main units first, in groups of 8; the packed tails follow in groups of their own (no mixed group: the unit body is a
+  // compile-time variant).  A workgroup walks the groups blockIdx.x, + gridDim.x, ... of the joint list.
+  const int nunits = q.nmain, nblk = q.nmb, npair = q.npair;
+  const int ngroups = (nunits + 7) >> 3, ngpk = (q.npk + 7) >> 3;
   // raw g1 (and y1) rows of a unit for this wave's filter: .x = electrode c0, .y = electrode c0 + 1 (0 outside)
   v2f cg[NROW], cy[NROW];
   // (block, pair, sample) of a unit: one set of integer divisions per GROUP (they compile to ~60 scalar instructions each);
@@ -422,8 +519,11 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
       }
     }
   };
-  Pos cur = decode(blockIdx.x * 8);      // the unit whose rows are in cg / cy
-  if (blockIdx.x * 8 < nunits) fetch_raw(cur, cg, cy);
+  Pos cur = {0, 0, 0};      // the unit whose rows are in cg / cy
+  if (blockIdx.x * 8 < nunits) {
+    cur = decode(blockIdx.x * 8);
+    fetch_raw(cur, cg, cy);
+  }
   // input segment of this wave's unit of a group: fetched one group ahead, so that the Z transforms that open a group
   // find their data in registers (the loads travel under the previous group's eight dy transforms)
   v2f nx[16];
@@ -456,7 +556,7 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
       v2f ng[NROW], ny[NROW];
       const int nu = (uu + 1 < 8) ? u + 1 : (g + (int)gridDim.x) * 8;
       if (uu + 1 < 8) advance(cur);
-      else cur = decode(nu);
+      else if (nu < nunits) cur = decode(nu);
       if (nu < nunits) fetch_raw(cur, ng, ny);
 #pragma unroll
       for (int j = 0; j < NROW; ++j) {
@@ -486,6 +586,81 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
       }
     }
     __syncthreads();
+  }
+  // Groups of packed tails: the same walk with both halves of a unit - dy rows 0 .. 7 from tail A's g1 / y1, rows 8 .. 15
+  // from tail B's, zero at and past S.  All 16 rows can be live (a short filter packs tails of up to 7 rows), so the rows
+  // of the next unit go straight into pg / py once the current ones are consumed; cg / cy and their copies are dead here.
+  int gp = (int)blockIdx.x - ngroups;
+  if (gp < 0) gp += (-gp + (int)gridDim.x - 1) / (int)gridDim.x * (int)gridDim.x;
+  if (gp < ngpk) {
+    const int tbt = q.t0t - padl;
+    v2f pg[16], py[16];
+    auto half_raw = [&](int j0, int b, int c0, bool ex, v2f (&gr)[16], v2f (&yr)[16]) {
+      const bool has1 = c0 + 1 < C;
+      const int64_t off = (((int64_t)b * F1 + f) * C + c0) * S + q.t0t + lane;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool ok = ex && q.t0t + lane + 64 * j < S;
+        gr[j0 + j].x = ok ? EAV_LDG(g1 + off + 64 * j) : 0.f;
+        gr[j0 + j].y = (ok && has1) ? EAV_LDG(g1 + off + S + 64 * j) : 0.f;
+        if (!PLAIN) {
+          yr[j0 + j].x = ok ? EAV_LDG(y1 + off + 64 * j) : 0.f;
+          yr[j0 + j].y = (ok && has1) ? EAV_LDG(y1 + off + S + 64 * j) : 0.f;
+        }
+      }
+    };
+    auto fetch_raw_pk = [&](int p, v2f (&gr)[16], v2f (&yr)[16]) {
+      const Tails tl = decode_tails(q, p);
+      half_raw(0, tl.b0, tl.c0, true, gr, yr);
+      half_raw(8, tl.ex1 ? tl.b1 : tl.b0, tl.c1, tl.ex1, gr, yr);
+    };
+    auto fetch_x_pk = [&](int p, v2f (&dst)[16]) {
+      const Tails tl = decode_tails(q, p);
+      const int b1 = tl.ex1 ? tl.b1 : tl.b0;
+      load_half(dst, 0, x + ((xidx ? xidx[tl.b0] : (int64_t)tl.b0) * C + tl.c0) * S, true, tl.c0 + 1 < C, S, tbt, lane);
+      load_half(dst, 8, x + ((xidx ? xidx[b1] : (int64_t)b1) * C + tl.c1) * S, tl.ex1, tl.c1 + 1 < C, S, tbt, lane);
+    };
+    fetch_raw_pk(gp * 8, pg, py);
+    if (gp * 8 + wave < q.npk) fetch_x_pk(gp * 8 + wave, nx);
+    for (; gp < ngpk; gp += gridDim.x) {
+      if (gp * 8 + wave < q.npk) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = nx[j];
+        const int pn = (gp + (int)gridDim.x) * 8 + wave;
+        if (pn < q.npk) fetch_x_pk(pn, nx);
+        fft1024<false>(v, xb, lane, tw);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) zb[wave * NF + j * 64 + lane] = v[j];
+      }
+      __syncthreads();
+#pragma unroll 1
+      for (int uu = 0; uu < 8; ++uu) {
+        const int p = gp * 8 + uu;
+        if (p >= q.npk) break;
+        const Tails tl = decode_tails(q, p);
+        const bool has0 = tl.c0 + 1 < C, has1 = tl.c1 + 1 < C;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          if (PLAIN) {
+            v[j] = sc * pg[j];
+          } else {
+            v[j] = sc * (pg[j] - m1 - (py[j] - mean) * invstd * m2);
+          }
+          // zero what is no output: past S, the missing electrode of an odd count, the upper half of a tail that stands alone
+          const bool ok = q.t0t + lane + 64 * (j & 7) < S && (j < 8 || tl.ex1);
+          if (!ok) v[j] = (v2f){0.f, 0.f};
+          if (!(j < 8 ? has0 : has1)) v[j].y = 0.f;
+        }
+        const int np = (uu + 1 < 8) ? p + 1 : (gp + (int)gridDim.x) * 8;
+        if (np < q.npk) fetch_raw_pk(np, pg, py);
+        fft1024<false>(v, xb, lane, tw);
+        const v2f* zp = zb + uu * NF + lane;
+#pragma unroll
+        for (int j = 0; j < 16; j += 2)
+          cmacc2_conj(lds_ld(zp + 64 * j), v[j], lds_ld(zp + 64 * j + 64), v[j + 1], acc[j], acc[j + 1]);
+      }
+      __syncthreads();
+    }
   }
   float* out = spec + ((int64_t)blockIdx.x * F1 + f) * (2 * NF);
 #pragma unroll
@@ -534,30 +709,29 @@ __global__ __launch_bounds__(64) void fir_fft_wgrad_finish_kernel(const float* _
   }
 }
 
-int fft_units(int B, int C, int S, int* npair, int* nblk) {
-  *npair = (C + 1) / 2;
-  *nblk = cdiv(S, LB);
-  return B * *npair * *nblk;
-}
-
-// workgroups of 8 waves, at most one per CU; `items` work items of `per_wg` per round: the smallest grid that needs no
-// more rounds than 256 workgroups would (14400 units = 1800 rounds-of-8: 225 workgroups x 8 rounds, no partial round)
-int fft_grid(int nunits, int per_wg) {
-  const int items = cdiv(nunits, per_wg);
+// weight gradient: workgroups of 8 waves, at most one per CU, over `items` groups of 8 units: the smallest grid that needs
+// no more rounds than 256 workgroups would (13920 units = 1680 + 60 groups: 249 workgroups x 7 rounds; unpacked, 1800
+// groups took 8 rounds on 225)
+int fft_grid(int items) {
   if (items <= 256) return std::max(1, items);
   const int rounds = cdiv(items, 256);
   return cdiv(items, rounds);
 }
+int wgrad_groups(const Units& q) { return cdiv(q.nmain, 8) + cdiv(q.npk, 8); }
+// forward: one workgroup of NWF waves per CU while the units last (the kernel deals them round by round, then slot by slot)
+int fwd_grid(const Units& q) { return std::min(256, std::max(1, cdiv(q.total(), NWF))); }
+// The sizing exports do not know klen, hence not whether the tails pack: they take the larger of the two lists (klen = 1
+// packs whenever any filter does, klen = NF never).
+constexpr int K_PACKS = 1, K_NEVER = NF;
 
 }  // namespace
 
 extern "C" int eav_eegnet_fir_fft_max_taps(void) { return MAXK; }
 
-// stat_part rows (16 floats each: 8 sums, 8 sums of squares) the forward writes - one per wave
+// stat_part rows (16 floats each: 8 sums, 8 sums of squares) the forward writes - one per wave, and zeros in those a
+// shorter unit list leaves without a wave
 extern "C" int eav_eegnet_fir_fwd_fft_nparts(int B, int C, int S) {
-  int npair, nblk;
-  const int nunits = fft_units(B, C, S, &npair, &nblk);
-  return fft_grid(nunits, NWF) * NWF;
+  return std::max(fwd_grid(fft_units(B, C, S, K_PACKS)), fwd_grid(fft_units(B, C, S, K_NEVER))) * NWF;
 }
 
 // y1 [B,8,C,S] = firstConv(x) for the batch x[xidx[0..B)] (xidx NULL: x itself), 'same' padding, klen <= 321 taps;
@@ -567,23 +741,22 @@ extern "C" int eav_eegnet_fir_fwd_fft(const float* x, const int64_t* xidx, const
                                       int B, int C, int S, int klen, void* stream) {
   EAV_REQUIRE(x && w1 && y1 && B > 0 && C > 0 && S > 0, "eav_eegnet_fir_fwd_fft: bad arguments");
   EAV_REQUIRE(klen >= 1 && klen <= MAXK, "eav_eegnet_fir_fwd_fft: kernLength %d outside [1,%d]", klen, MAXK);
-  int npair, nblk;
-  const int nunits = fft_units(B, C, S, &npair, &nblk);
+  const Units q = fft_units(B, C, S, klen);
+  const int grid = fwd_grid(q), nrows = eav_eegnet_fir_fwd_fft_nparts(B, C, S);
   if (stat_part)
-    hipLaunchKernelGGL(fir_fft_fwd_kernel<true>, dim3(fft_grid(nunits, NWF)), dim3(64 * NWF), 0, (hipStream_t)stream, x, xidx,
-                       w1, y1, stat_part, C, S, klen, (klen - 1) / 2, npair, nblk, nunits);
+    hipLaunchKernelGGL(fir_fft_fwd_kernel<true>, dim3(grid), dim3(64 * NWF), 0, (hipStream_t)stream, x, xidx, w1, y1,
+                       stat_part, C, S, klen, (klen - 1) / 2, q, nrows);
   else      // firstBN in eval mode: running statistics, nothing to collect
-    hipLaunchKernelGGL(fir_fft_fwd_kernel<false>, dim3(fft_grid(nunits, NWF)), dim3(64 * NWF), 0, (hipStream_t)stream, x, xidx,
-                       w1, y1, stat_part, C, S, klen, (klen - 1) / 2, npair, nblk, nunits);
+    hipLaunchKernelGGL(fir_fft_fwd_kernel<false>, dim3(grid), dim3(64 * NWF), 0, (hipStream_t)stream, x, xidx, w1, y1,
+                       stat_part, C, S, klen, (klen - 1) / 2, q, nrows);
   EAV_CHECK_LAUNCH("eav_eegnet_fir_fwd_fft");
   return EAV_OK;
 }
 
-// floats of the spectrum workspace of eav_eegnet_fir_wgrad_fft
+// floats of the spectrum workspace of eav_eegnet_fir_wgrad_fft: one row per workgroup + one, the sum of the others
 extern "C" int64_t eav_eegnet_fir_wgrad_fft_ws_floats(int B, int C, int S) {
-  int npair, nblk;
-  const int nunits = fft_units(B, C, S, &npair, &nblk);
-  return ((int64_t)fft_grid(cdiv(nunits, 8), 1) + 1) * F1 * 2 * NF;      // + one row: the sum of the others
+  const int gp = fft_grid(wgrad_groups(fft_units(B, C, S, K_PACKS))), gn = fft_grid(wgrad_groups(fft_units(B, C, S, K_NEVER)));
+  return ((int64_t)std::max(gp, gn) + 1) * F1 * 2 * NF;      // (fewer groups can mean MORE workgroups: 1740 -> 249, 1800 -> 225)
 }
 
 // dW [8, klen] = d loss / d firstConv.weight (written, not accumulated).  g1 = d loss / d(firstBN output) [B,8,C,S];
@@ -594,16 +767,15 @@ extern "C" int eav_eegnet_fir_wgrad_fft(const float* x, const int64_t* xidx, con
                                         void* stream) {
   EAV_REQUIRE(x && g1 && bn_params && ws && dW && B > 0 && C > 0 && S > 0, "eav_eegnet_fir_wgrad_fft: bad arguments");
   EAV_REQUIRE(klen >= 1 && klen <= MAXK, "eav_eegnet_fir_wgrad_fft: kernLength %d outside [1,%d]", klen, MAXK);
-  int npair, nblk;
-  const int nunits = fft_units(B, C, S, &npair, &nblk);
-  const int grid = fft_grid(cdiv(nunits, 8), 1);
+  const Units q = fft_units(B, C, S, klen);
+  const int grid = fft_grid(wgrad_groups(q));
   hipStream_t st = (hipStream_t)stream;
   if (y1)
     hipLaunchKernelGGL(fir_fft_wgrad_kernel<false>, dim3(grid), dim3(512), 0, st, x, xidx, y1, g1, bn_params, ws, C, S,
-                       (klen - 1) / 2, npair, nblk, nunits);
+                       (klen - 1) / 2, q);
   else
     hipLaunchKernelGGL(fir_fft_wgrad_kernel<true>, dim3(grid), dim3(512), 0, st, x, xidx, y1, g1, bn_params, ws, C, S,
-                       (klen - 1) / 2, npair, nblk, nunits);
+                       (klen - 1) / 2, q);
   EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad_fft");
   hipLaunchKernelGGL(fir_fft_wgrad_sum_kernel, dim3(F1 * 32), dim3(512), 0, st, ws, grid);
   EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad_fft(sum)");

@@ -81,7 +81,8 @@ int eav_eegnet_fir_wgrad(const float* x, const float* y1, const float* g1, const
  * weight gradient of it, CNN_torch/EEGNet_tor.py:24,51,109) in ~13 x fewer flops - HBM-bound instead of MFMA-bound; up to
  * eav_eegnet_fir_fft_max_taps() = 321 taps, any C / S.  xidx (optional): the batch is x[xidx[0..B)].
  * fwd: stat_part [eav_eegnet_fir_fwd_fft_nparts(B,C,S)][16] (8 sums, 8 sums of squares per row) for eav_bn_finalize; NULL:
- * no statistics are collected (firstBN in eval mode uses its running statistics).
+ * no statistics are collected (firstBN in eval mode uses its running statistics).  Both sizes hold for every klen (short
+ * row tails share a transform where klen lets them, which changes the grids); EVERY stat_part row is written.
  * wgrad: dW [8, klen] is WRITTEN (no partials to reduce); ws: eav_eegnet_fir_wgrad_fft_ws_floats(B,C,S) floats;
  * y1 = NULL selects BatchNorm in eval mode (dy = scale g).  Bit-reproducible run to run. */
 int eav_eegnet_fir_fft_max_taps(void);
