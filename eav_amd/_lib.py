@@ -43,6 +43,8 @@ SIGNATURES = {
     "eav_eegnet_fir_fwd_fft": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_eegnet_fir_wgrad_fft": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_eegnet_fir_wgrad_indexed": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "eav_eegnet_fir_xtab_build": [_p, _i, _i, _i, _i, _p, _p],
+    "eav_eegnet_fir_wgrad_fft_xtab": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_eegnet_dw_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     "eav_eegnet_dw_fwd_pool_eval": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "eav_eegnet_dw_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
@@ -196,6 +198,8 @@ PLAIN = {
     "eav_eegnet_fir_fwd_fft_nparts": ([_i, _i, _i], _i),
     "eav_eegnet_fir_wgrad_fft_ws_floats": ([_i, _i, _i], _i64),
     "eav_eegnet_fir_fft_max_taps": ([], _i),
+    "eav_eegnet_fir_xtab_floats": ([_i, _i], _i64),
+    "eav_eegnet_fir_wgrad_fft_xtab_ws_floats": ([_i, _i, _i, _i], _i64),
     "eav_eegnet_fir_wgrad_nparts": ([_i, _i, _i], _i),
     "eav_conv64_ntiles": ([_i], _i),
     "eav_tconv_fwd_nparts": ([_i, _i, _i, _i, _i], _i),

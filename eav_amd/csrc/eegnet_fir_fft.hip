@@ -463,7 +463,9 @@ __global__ __launch_bounds__(64 * NWF, 1) void fir_fft_fwd_kernel(const float* _
 // Workgroup = 8 waves, wave f owns filter f's spectrum accumulator.  Per group of 8 units: wave w transforms the input
 // segment of unit w into LDS (register layout), then every wave walks the 8 units, forms its filter's dy block, transforms
 // it and accumulates Z conj(D).  PLAIN: BatchNorm in eval mode (dy = scale g, y1 is not read).
-template <bool PLAIN>
+// UNIT (with PLAIN): dy = g, no scale and no BatchNorm parameters read (bnp and y1 NULL) - the G term of the table form
+// further down.
+template <bool PLAIN, bool UNIT = false>
 __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __restrict__ x, const int64_t* __restrict__ xidx,
                                                                const float* __restrict__ y1, const float* __restrict__ g1,
                                                                const float* __restrict__ bnp, float* __restrict__ spec,
@@ -474,7 +476,8 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
   v2f* xb = smem + 8 * NF + wave * WBUF;
   const v2f* tw = smem + 8 * NF + 8 * WBUF;
   make_twiddles(smem + 8 * NF + 8 * WBUF);
-  const float mean = bnp[f], invstd = bnp[8 + f], sc = bnp[16 + f], m1 = bnp[32 + f], m2 = bnp[40 + f];
+  const float mean = UNIT ? 0.f : bnp[f], invstd = UNIT ? 0.f : bnp[8 + f], sc = UNIT ? 1.f : bnp[16 + f],
+              m1 = UNIT ? 0.f : bnp[32 + f], m2 = UNIT ? 0.f : bnp[40 + f];
   v2f acc[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) acc[j] = (v2f){0.f, 0.f};
@@ -560,7 +563,9 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
       if (nu < nunits) fetch_raw(cur, ng, ny);
 #pragma unroll
       for (int j = 0; j < NROW; ++j) {
-        if (PLAIN) {
+        if (UNIT) {
+          v[j] = cg[j];
+        } else if (PLAIN) {
           v[j] = sc * cg[j];
         } else {
           v[j] = sc * (cg[j] - m1 - (cy[j] - mean) * invstd * m2);
@@ -641,7 +646,9 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
         const bool has0 = tl.c0 + 1 < C, has1 = tl.c1 + 1 < C;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-          if (PLAIN) {
+          if (UNIT) {
+            v[j] = pg[j];
+          } else if (PLAIN) {
             v[j] = sc * pg[j];
           } else {
             v[j] = sc * (pg[j] - m1 - (py[j] - mean) * invstd * m2);
@@ -672,8 +679,7 @@ __global__ __launch_bounds__(512, 1) void fir_fft_wgrad_kernel(const float* __re
 // 16 group sums are added as a fixed tree - bit-reproducible - and the total goes to row `nparts` of the workspace.
 // (2) One wave per filter transforms the total back and keeps the real parts of lags 0 .. klen - 1.  (One workgroup per
 // filter doing both took 30 us at 225 partials; 64 workgroups of 4 groups 16.6 us: a chain of 56 loads per thread.)
-__global__ __launch_bounds__(512) void fir_fft_wgrad_sum_kernel(float* __restrict__ spec, int nparts) {
-  __shared__ v2f red[512];
+__device__ __forceinline__ void wgrad_spec_sum(float* __restrict__ spec, int nparts, v2f* __restrict__ red) {
   const int f = blockIdx.x >> 5, bin = (blockIdx.x & 31) * 32 + (threadIdx.x & 31), grp = threadIdx.x >> 5;
   const v2f* src = reinterpret_cast<const v2f*>(spec) + (int64_t)f * NF + bin;
   v2f a = (v2f){0.f, 0.f};
@@ -691,6 +697,10 @@ __global__ __launch_bounds__(512) void fir_fft_wgrad_sum_kernel(float* __restric
     reinterpret_cast<v2f*>(spec)[((int64_t)nparts * F1 + f) * NF + bin] = a;
   }
 }
+__global__ __launch_bounds__(512) void fir_fft_wgrad_sum_kernel(float* __restrict__ spec, int nparts) {
+  __shared__ v2f red[512];
+  wgrad_spec_sum(spec, nparts, red);
+}
 
 __global__ __launch_bounds__(64) void fir_fft_wgrad_finish_kernel(const float* __restrict__ spec, int nparts,
                                                                   float* __restrict__ dW, int klen) {
@@ -706,6 +716,147 @@ __global__ __launch_bounds__(64) void fir_fft_wgrad_finish_kernel(const float* _
   for (int j = 0; j < 16; ++j) {
     const int n = lane + 64 * j;
     if (n < klen) dW[f * klen + n] = v[j].x * (1.0f / NF);
+  }
+}
+
+// ----------------------------------------------------------------------------------------- wgrad from per-trial input tables
+// The train-mode weight gradient reads y1 only to form dy = scale (g - m1 - (y1 - mean) invstd m2) while loading.  y1 is
+// firstConv(x), so its share of dW is a function of x and w alone.  With xp = the row zero-padded by (left, K - 1 - left):
+//   dW[f,k] = scale_f ( G[f,k] - (m1_f - mean_f invstd_f m2_f) X1[k] - invstd_f m2_f Y[f,k] )
+//   G[f,k]  = sum_{b,c,t<S} g1[b,f,c,t] xp[b,c,t+k]          the PLAIN walk on the raw g1 (fir_fft_wgrad_kernel<true, true>)
+//   X1[k]   = sum_b X1_b[k],  X1_b[k]   = sum_c sum_{t<S} xp[t+k]
+//   Y[f,k]  = sum_j w[f,j] A[j,k],  A = sum_b A_b,  A_b[j,k] = sum_c sum_{t<S} xp[t+j] xp[t+k]      (symmetric, K x K)
+// A_b and X1_b depend on trial b of the data set alone: a table of K K + K floats per trial (A_b row-major, then X1_b), built
+// once per data set by fir_xtab_build_kernel; a step sums the rows of its batch.  Every sum below is formed in float64 in
+// a fixed order and rounded once.
+__host__ __device__ inline int64_t xtab_stride(int klen) { return (int64_t)klen * klen + klen; }
+
+// xp[u] of a row of S samples
+__device__ __forceinline__ double xpad(const float* __restrict__ row, int S, int left, int u) {
+  const int t = u - left;
+  return (t >= 0 && t < S) ? (double)row[t] : 0.0;
+}
+// a[tid] = sum of the 256 entries of a, as a fixed tree
+__device__ __forceinline__ double block_sum256(double* a, int tid) {
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) a[tid] += a[tid + s];
+    __syncthreads();
+  }
+  return a[0];
+}
+
+// Workgroup = (trial b, lag d): the diagonal A_b[j, j + d], j < K - d, of the table, its mirror, and X1_b[d].  With
+// R = sum_c sum_{u<S} xp[u] xp[u+d] (one autocorrelation lag per row) the diagonal is R less the products of the first j
+// samples plus those of the j samples from S on:
+//   A_b[j, j+d] = sum_{u=j}^{S+j-1} xp[u] xp[u+d] = R - sum_{u<j} xp[u] xp[u+d] + sum_{S<=u<S+j} xp[u] xp[u+d]
+// (u + d <= S + K - 2 throughout: j + d <= K - 1).
+__global__ __launch_bounds__(256) void fir_xtab_build_kernel(const float* __restrict__ x, float* __restrict__ tab, int C, int S,
+                                                             int klen) {
+  __shared__ double ra[256], rb[256], hs[MAXK];
+  const int d = blockIdx.x % klen, b = blockIdx.x / klen, tid = threadIdx.x, left = (klen - 1) / 2;
+  const float* xb = x + (int64_t)b * C * S;
+  float* A = tab + (int64_t)b * xtab_stride(klen);
+  double r = 0.0, s1 = 0.0;
+  for (int c = 0; c < C; ++c) {
+    const float* row = xb + (int64_t)c * S;
+    for (int u = tid; u < S; u += 256) {
+      const double q = xpad(row, S, left, u + d);
+      r = fma(xpad(row, S, left, u), q, r);
+      s1 += q;
+    }
+  }
+  ra[tid] = r;
+  rb[tid] = s1;
+  const double R = block_sum256(ra, tid), X1 = block_sum256(rb, tid);
+  const int nj = klen - d;
+  // hs[j] = (products of the j-th sample from S on) - (products of the j-th sample), over the rows
+  for (int j = tid; j < nj; j += 256) {
+    double h = 0.0, t = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const float* row = xb + (int64_t)c * S;
+      h = fma(xpad(row, S, left, j), xpad(row, S, left, j + d), h);
+      t = fma(xpad(row, S, left, S + j), xpad(row, S, left, S + j + d), t);
+    }
+    hs[j] = t - h;
+  }
+  __syncthreads();
+  if (tid == 0) {      // hs[j] <- A_b[j, j + d]: the running sum, in order
+    double a = R;
+    for (int j = 0; j < nj; ++j) {
+      const double nxt = a + hs[j];
+      hs[j] = a;
+      a = nxt;
+    }
+    A[(int64_t)klen * klen + d] = (float)X1;
+  }
+  __syncthreads();
+  for (int j = tid; j < nj; j += 256) {
+    const float a = (float)hs[j];
+    A[j * klen + j + d] = a;
+    A[(j + d) * klen + j] = a;
+  }
+}
+
+// The first finishing launch with the batch's tables riding in it: acc[0 .. K K) = A = sum_b A_{xidx[b]}, acc[K K .. + K) = X1,
+// in float64, b = 0 .. B - 1 in order.  A is symmetric: the upper triangle is read, both halves are written.
+__global__ __launch_bounds__(512) void fir_fft_wgrad_sum_tab_kernel(float* __restrict__ spec, int nparts,
+                                                                    const float* __restrict__ tab,
+                                                                    const int64_t* __restrict__ xidx, int B, int klen,
+                                                                    double* __restrict__ acc) {
+  __shared__ v2f red[512];
+  wgrad_spec_sum(spec, nparts, red);
+  const int64_t stride = xtab_stride(klen);
+  const int n = (int)stride;
+  for (int e = blockIdx.x * 512 + threadIdx.x; e < n; e += gridDim.x * 512) {
+    const int j = e / klen, k = e - j * klen;      // j == klen: the X1 row
+    if (j < klen && k < j) continue;
+    double a = 0.0;
+#pragma unroll 16
+    for (int b = 0; b < B; ++b) a += (double)tab[(xidx ? xidx[b] : (int64_t)b) * stride + e];
+    acc[e] = a;
+    if (j < klen && k > j) acc[k * klen + j] = a;
+  }
+}
+
+// The second: workgroup = (filter f, 64 lags k).  Wave 0 transforms the summed spectrum back (G, as
+// fir_fft_wgrad_finish_kernel) while each of the 16 waves forms its slice of Y[f,k] = sum_j w[f,j] A[j,k]; the slices are
+// added in order and the combination above is rounded to fp32 once.
+__global__ __launch_bounds__(1024) void fir_fft_wgrad_finish_tab_kernel(const float* __restrict__ spec, int nparts,
+                                                                        const double* __restrict__ acc,
+                                                                        const float* __restrict__ w1,
+                                                                        const float* __restrict__ bnp, float* __restrict__ dW,
+                                                                        int klen) {
+  __shared__ v2f smem[WBUF + TWSZ];
+  __shared__ double ys[16][64];
+  __shared__ float gs[64];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = blockIdx.x;
+  const int kb = blockIdx.y, k = kb * 64 + lane;
+  make_twiddles(smem + WBUF);
+  const int jn = (klen + 15) / 16, j0 = wave * jn, j1 = min(klen, j0 + jn);
+  double y = 0.0;
+  if (k < klen)
+    for (int j = j0; j < j1; ++j) y = fma((double)w1[f * klen + j], acc[j * klen + k], y);
+  ys[wave][lane] = y;
+  if (wave == 0) {
+    v2f v[16];
+    const v2f* src = reinterpret_cast<const v2f*>(spec) + ((int64_t)nparts * F1 + f) * NF + lane;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = src[64 * j];
+    fft1024<true>(v, smem, lane, smem + WBUF);
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (j == kb) gs[lane] = v[j].x;      // lag lane + 64 j
+  }
+  __syncthreads();
+  if (wave == 0 && k < klen) {
+    double Y = 0.0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) Y += ys[w][lane];
+    const double mean = bnp[f], invstd = bnp[8 + f], sc = bnp[16 + f], m1 = bnp[32 + f], m2 = bnp[40 + f];
+    const double G = (double)gs[lane] * (1.0 / NF), X1 = acc[klen * klen + k];
+    dW[f * klen + k] = (float)(sc * (G - (m1 - mean * invstd * m2) * X1 - invstd * m2 * Y));
   }
 }
 
@@ -781,5 +932,52 @@ extern "C" int eav_eegnet_fir_wgrad_fft(const float* x, const int64_t* xidx, con
   EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad_fft(sum)");
   hipLaunchKernelGGL(fir_fft_wgrad_finish_kernel, dim3(F1), dim3(64), 0, st, ws, grid, dW, klen);
   EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad_fft(finish)");
+  return EAV_OK;
+}
+
+// floats of the input tables of N trials: per trial A_b [klen][klen] row-major, then X1_b [klen]
+extern "C" int64_t eav_eegnet_fir_xtab_floats(int N, int klen) { return (int64_t)N * xtab_stride(klen); }
+
+// tab [N][klen klen + klen] = the tables of the trials x [N,C,S] (float64 sums, rounded once; deterministic).  Once per data
+// set - and again whenever x changes - never inside a step.
+extern "C" int eav_eegnet_fir_xtab_build(const float* x, int N, int C, int S, int klen, float* tab, void* stream) {
+  EAV_REQUIRE(x && tab && N > 0 && C > 0 && S > 0, "eav_eegnet_fir_xtab_build: bad arguments");
+  EAV_REQUIRE(klen >= 1 && klen <= MAXK, "eav_eegnet_fir_xtab_build: kernLength %d outside [1,%d]", klen, MAXK);
+  EAV_REQUIRE((int64_t)N * klen < (int64_t)1 << 31, "eav_eegnet_fir_xtab_build: %d trials are too many", N);
+  hipLaunchKernelGGL(fir_xtab_build_kernel, dim3(N * klen), dim3(256), 0, (hipStream_t)stream, x, tab, C, S, klen);
+  EAV_CHECK_LAUNCH("eav_eegnet_fir_xtab_build");
+  return EAV_OK;
+}
+
+// workspace of eav_eegnet_fir_wgrad_fft_xtab: that of eav_eegnet_fir_wgrad_fft, then klen klen + klen doubles (A and X1)
+extern "C" int64_t eav_eegnet_fir_wgrad_fft_xtab_ws_floats(int B, int C, int S, int klen) {
+  return eav_eegnet_fir_wgrad_fft_ws_floats(B, C, S) + 2 * xtab_stride(klen);
+}
+
+// The train-mode dW of eav_eegnet_fir_wgrad_fft without its y1 read, for y1 = firstConv(x; w1): the main kernel walks the
+// raw g1 as in eval mode, the share of y1 comes from the tables tab (eav_eegnet_fir_xtab_build of the array x points to; row
+// xidx[b], or b, is the table of sample b of the batch - repeated indices count as often as they occur) in the two finishing
+// launches.  ws: eav_eegnet_fir_wgrad_fft_xtab_ws_floats floats, 8-byte aligned.  Agrees with eav_eegnet_fir_wgrad_fft to
+// rounding, not bit for bit; bit-reproducible run to run.
+extern "C" int eav_eegnet_fir_wgrad_fft_xtab(const float* x, const int64_t* xidx, const float* tab, const float* w1,
+                                             const float* g1, const float* bn_params, float* ws, float* dW, int B, int C,
+                                             int S, int klen, void* stream) {
+  EAV_REQUIRE(x && tab && w1 && g1 && bn_params && ws && dW && B > 0 && C > 0 && S > 0,
+              "eav_eegnet_fir_wgrad_fft_xtab: bad arguments");
+  EAV_REQUIRE(klen >= 1 && klen <= MAXK, "eav_eegnet_fir_wgrad_fft_xtab: kernLength %d outside [1,%d]", klen, MAXK);
+  EAV_REQUIRE(((uintptr_t)ws & 7) == 0, "eav_eegnet_fir_wgrad_fft_xtab: ws is not 8-byte aligned");
+  const Units q = fft_units(B, C, S, klen);
+  const int grid = fft_grid(wgrad_groups(q));
+  double* acc = reinterpret_cast<double*>(ws + eav_eegnet_fir_wgrad_fft_ws_floats(B, C, S));
+  hipStream_t st = (hipStream_t)stream;
+  const float* none = nullptr;
+  hipLaunchKernelGGL((fir_fft_wgrad_kernel<true, true>), dim3(grid), dim3(512), 0, st, x, xidx, none, g1, none, ws, C, S,
+                     (klen - 1) / 2, q);
+  EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad_fft_xtab");
+  hipLaunchKernelGGL(fir_fft_wgrad_sum_tab_kernel, dim3(F1 * 32), dim3(512), 0, st, ws, grid, tab, xidx, B, klen, acc);
+  EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad_fft_xtab(sum)");
+  hipLaunchKernelGGL(fir_fft_wgrad_finish_tab_kernel, dim3(F1, cdiv(klen, 64)), dim3(1024), 0, st, ws, grid, acc, w1,
+                     bn_params, dW, klen);
+  EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad_fft_xtab(finish)");
   return EAV_OK;
 }

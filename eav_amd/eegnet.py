@@ -107,6 +107,16 @@ class EEGNet_tor(KernelModule):
         # training step - forms du3 from dp3 / u3 while it loads (eav_conv64_fft_bwd: no eav_bn_elu_pool_bwd_apply launch, no
         # du3 tensor, one pack launch less); False / EAV_CONV_FUSE=0: the separate launches (bit-identical results)
         self.conv_fuse = os.environ.get("EAV_CONV_FUSE", "1") != "0"
+        # Train-mode GraphStep steps on the FFT FIR path: the weight gradient takes y1's share of dW from per-trial tables of
+        # the HBM-resident data set (eegnet_paths.InputTables, built on the first eager step) instead of reading y1 back.
+        # False / EAV_FIR_XTAB=0: the y1-reading kernel, as forward() and forward_indexed() always use it.  The tables cost
+        # 4 (K K + K) bytes per trial (72 MB for 200 trials at 300 taps); a data set whose tables would exceed
+        # `fir_xtab_budget` bytes (1 GiB: ~2900 trials at 300 taps) keeps the y1-reading kernel.  They follow in-place torch
+        # writes to the data set (GraphStep.run compares its _version); a write that bypasses torch (a raw kernel, a
+        # DLPack alias) needs refresh_input_tables(xs).
+        self.fir_xtab = os.environ.get("EAV_FIR_XTAB", "1") != "0"
+        self.fir_xtab_budget = 1 << 30
+        self._xtabs = {}                       # InputTables by data set, for the life of the model (FastPath.input_tables)
         self._infer = False                    # set per call: no-grad eval-mode forward
         # validate()'s forward with block 1 as ONE kernel (eav_eegnet_block1_infer: y1 / z never written).  Opt-in: at the
         # benchmark shape [64,1,30,10000] it measures 1.35 ms against 1.30 ms for the training kernels in eval mode - with its
@@ -132,6 +142,16 @@ class EEGNet_tor(KernelModule):
             raise ValueError(f"expected input [B,1,{self.Chans},{self.Samples}], got {tuple(x.shape)}")
         return self._run(x.contiguous().float())
 
+    def refresh_input_tables(self, xs=None, force=True):
+        """Rebuild, in place, the InputTables of the data set `xs` (None: of every data set) - after a write to it that
+        torch does not see.  force=False: only those whose data._version has moved on (GraphStep.run)."""
+        for t in self._xtabs.values():
+            if (xs is None or t.data.data_ptr() == xs.data_ptr()) and (force or t.version != t.data._version):
+                t.build()
+
+    def refresh_batch_tables(self, xs):
+        self.refresh_input_tables(xs, force=False)
+
     def _indexed(self, data, idx, step_begin=None):
         if data.dim() != 4 or data.shape[1] != 1 or data.shape[2] != self.Chans or data.shape[3] != self.Samples or \
                 not data.is_cuda or data.dtype != torch.float32 or not data.is_contiguous():
@@ -154,7 +174,9 @@ class EEGNet_tor(KernelModule):
             return super().forward_batch(xs, ys, idx, optimizer)
         targets = torch.empty(idx.numel(), dtype=torch.long, device=xs.device)
         optimizer.step_counted = False       # (a step that failed between its two halves must not leave the flag set)
+        # (the data set of a GraphStep stays put: a train-mode step takes y1's share of the firstConv gradient from its tables)
         batch = self._indexed(xs, idx, self._path.step_begin_args(optimizer, ys, idx, targets))
+        batch.xtab = self._path.input_tables(xs)
         scores = self._run(batch)
         optimizer.step_counted = batch.merged
         if not batch.merged:

@@ -9,8 +9,8 @@
 
 Each owns its workspace class and its forward / backward sequence: `forward(x) -> token`, `backward(dprobs) -> grads`.  The
 model (`m`) keeps what both read: the parameters and their flat gradients, the workspace cache (`_ws` / `_wss`), the token and
-the saved forward (`_saved`), the dropout state and the user-visible switches (`fir_algo`, `conv_algo`, `conv_fuse`,
-`fused_eval`, `apply_max_norm`).  Plain objects, not nn.Modules: they register nothing with the model.
+the saved forward (`_saved`), the dropout state, the input tables of its data sets (`_xtabs`) and the user-visible switches
+(`fir_algo`, `fir_xtab`, `conv_algo`, `conv_fuse`, `fused_eval`, `apply_max_norm`).  Plain objects, not nn.Modules: they register nothing with the model.
 """
 from __future__ import annotations
 
@@ -35,13 +35,36 @@ class IndexedBatch:
     kernels - the only readers of the network input - take the index vector, so no gathered copy of the batch is made.
     `step_begin` (EEGNet_tor.forward_batch): the arguments of eav_step_begin behind the counters - (optimiser step counter,
     labels, idx, targets, batch) as raw pointers - for a forward that can issue them with its own counter launch; that
-    forward sets `merged`."""
+    forward sets `merged`.  `xtab` (EEGNet_tor.forward_batch): the InputTables of `data`, or None."""
 
-    def __init__(self, data, idx, step_begin=None):
+    def __init__(self, data, idx, step_begin=None, xtab=None):
         self.data, self.idx = data, idx
         self.shape = (idx.numel(),) + tuple(data.shape[1:])
         self.device = data.device
         self.step_begin, self.merged = step_begin, False
+        self.xtab = xtab
+
+
+class InputTables:
+    """What the train-mode FFT weight gradient needs of y1 = firstConv(x), as a function of x alone: per trial of the
+    HBM-resident data set `data` [N,1,C,S] the K x K matrix A_b[j,k] = sum_c sum_t xp[t+j] xp[t+k] and the K window sums X1_b
+    (eav_eegnet_fir_xtab_build; 4 (K K + K) bytes per trial: 361 KB at 300 taps, 72 MB for 200 trials).  With them
+    eav_eegnet_fir_wgrad_fft_xtab skips the 614 MB read of y1.  Built once per data set, outside any step; `version` is
+    data._version at build time.  build() rewrites `tab` IN PLACE: a captured step keeps its pointer."""
+
+    def __init__(self, data, klen):
+        self.data, self.klen = data, klen
+        self.tab = torch.empty(self.floats(data.shape[0], klen), dtype=torch.float32, device=data.device)
+        self.build()
+
+    @staticmethod
+    def floats(N, klen):
+        return _lib.plain("eav_eegnet_fir_xtab_floats", N, klen)
+
+    def build(self):
+        N, _, C, S = self.data.shape
+        _lib.call("eav_eegnet_fir_xtab_build", _lib.ptr(self.data), N, C, S, self.klen, _lib.ptr(self.tab), _lib.stream_ptr())
+        self.version = self.data._version
 
 
 class BnBwdJob(NamedTuple):
@@ -68,6 +91,10 @@ class _Path:
         if isinstance(x, IndexedBatch):
             return _lib.ptr(x.data), _lib.ptr(x.idx), x.shape[0]
         return _lib.ptr(x), None, x.shape[0]
+
+    def input_tables(self, xs):
+        """The InputTables a GraphStep batch of the data set `xs` carries (FastPath), or None."""
+        return None
 
     def dropout_args(self, dev, training):
         """(counter pointer, block-1 and block-2 dropout arguments (rate, seed, mask pointer, counter pointer), mk)."""
@@ -152,6 +179,25 @@ class FastPath(_Path):
     def step_begin_args(self, optimizer, ys, idx, targets):
         """What EEGNet_tor.forward_batch hands to the forward's counter launch (IndexedBatch.step_begin)."""
         return (optimizer.device_step_counter().data_ptr(), ys.data_ptr(), idx.data_ptr(), targets.data_ptr(), idx.numel())
+
+    def input_tables(self, xs):
+        """Train-mode step on the FFT FIR path with m.fir_xtab on: the InputTables of the data set `xs`, kept in m._xtabs
+        for the life of the model (a captured step holds their pointer).  Built here on first use and rebuilt in place when
+        xs._version has moved on - never during capture, where only tables that exist are used.  None (the y1-reading weight
+        gradient) for any other step, and when the tables would exceed m.fir_xtab_budget bytes."""
+        m = self.m
+        if not (m.fir_xtab and m.training and self.use_fft()):
+            return None
+        key = (xs.data_ptr(), tuple(xs.shape), m.kernLength)
+        t = m._xtabs.get(key)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if t is None:
+            if capturing or 4 * InputTables.floats(xs.shape[0], m.kernLength) > m.fir_xtab_budget:
+                return None
+            t = m._xtabs[key] = InputTables(xs, m.kernLength)
+        elif t.version != xs._version and not capturing:
+            t.build()
+        return t
 
     # ------------------------------------------------------------------ forward
     def forward(self, x):
@@ -352,10 +398,17 @@ class FastPath(_Path):
         # eval-mode step (every epoch after the first, Q4): BatchNorm backward is a plain scale, y1 is not needed
         y1 = P(ws.y1) if s.training else None
         if self.use_fft():
-            if ws.fft_ws is None:
-                ws.fft_ws = torch.empty(_lib.plain("eav_eegnet_fir_wgrad_fft_ws_floats", B, C, S), dtype=torch.float32,
+            if ws.fft_ws is None:       # (the table form's size: the other one + K K + K doubles)
+                ws.fft_ws = torch.empty(_lib.plain("eav_eegnet_fir_wgrad_fft_xtab_ws_floats", B, C, S, K), dtype=torch.float32,
                                         device=ws.y1.device)
-            L("eav_eegnet_fir_wgrad_fft", xp, xidx, y1, P(ws.g1), P(ws.bn1), P(ws.fft_ws), gw1, B, C, S, K, st)
+            xtab = getattr(s.x, "xtab", None) if s.training else None
+            if xtab is not None:
+                # a GraphStep batch of a data set with InputTables: y1's share of dW comes from them, in the same three
+                # launches - y1 (614 MB at the bench shape) is not read.  Agrees with the other branch to rounding.
+                L("eav_eegnet_fir_wgrad_fft_xtab", xp, xidx, P(xtab.tab), P(m.firstConv.weight), P(ws.g1), P(ws.bn1),
+                  P(ws.fft_ws), gw1, B, C, S, K, st)
+            else:
+                L("eav_eegnet_fir_wgrad_fft", xp, xidx, y1, P(ws.g1), P(ws.bn1), P(ws.fft_ws), gw1, B, C, S, K, st)
         else:
             if xidx is None:
                 L("eav_eegnet_fir_wgrad", xp, y1, P(ws.g1), P(ws.bn1), P(ws.part_fw), B, C, S, K, st)

@@ -200,6 +200,10 @@ class KernelModule(nn.Module):
         data, targets = gather_batch(xs, ys, idx)
         return self(data), targets
 
+    def refresh_batch_tables(self, xs):
+        """GraphStep.run saw the data set `xs` change (xs._version): a model that keeps anything derived from it rebuilds
+        that IN PLACE - a captured step holds the pointers.  (EEGNet_tor: the InputTables of its FFT weight gradient.)"""
+
     def _pin_workspace(self):
         """A hipGraph was just captured over the current workspace and holds its raw pointers (cached_workspace)."""
         if self._ws is not None:
@@ -253,6 +257,10 @@ class GraphStep:
             raise _lib.EavError("GraphStep needs a KernelModule")
         self.model, self.batch, self.grad_sync = model, batch, grad_sync
         self.idx = torch.zeros(batch, dtype=torch.long, device=xs.device)
+        # The data set is assumed to stay put; what a model derives from it once (KernelModule.refresh_batch_tables) follows
+        # in-place torch writes through the version counter.  Writes torch does not see (a raw kernel, a DLPack alias) need
+        # the model's own refresh (EEGNet_tor.refresh_input_tables).
+        self.xs, self._xs_version = xs, xs._version
 
         def compute():       # batch gather + forward + loss + backward
             scores, targets = model.forward_batch(xs, ys, self.idx, optimizer)
@@ -283,6 +291,9 @@ class GraphStep:
         steps), the third is captured, later ones are replays.  Under data parallelism (grad_sync) the collective is
         not captured: replay(compute) -> all-reduce on the live stream -> replay(update)."""
         self.idx.copy_(torch.as_tensor(idx, dtype=torch.long))     # pageable source: staged, no host race
+        if self.xs._version != self._xs_version:
+            self._xs_version = self.xs._version
+            self.model.refresh_batch_tables(self.xs)
         if self.graph is None:
             if self.warm_steps < 2:
                 self.warm_steps += 1

@@ -92,6 +92,20 @@ int eav_eegnet_fir_fwd_fft(const float* x, const int64_t* xidx, const float* w1,
 int64_t eav_eegnet_fir_wgrad_fft_ws_floats(int B, int C, int S);
 int eav_eegnet_fir_wgrad_fft(const float* x, const int64_t* xidx, const float* y1, const float* g1, const float* bn_params,
                              float* ws, float* dW, int B, int C, int S, int klen, void* stream);
+/* The train-mode weight gradient without its y1 read, for a data set that stays in HBM.  y1 = firstConv(x; w1), so its share
+ * of dW is a function of x and w1:  dW[f,k] = scale_f (G[f,k] - (m1_f - mean_f invstd_f m2_f) X1[k] - invstd_f m2_f
+ * sum_j w1[f,j] A[j,k]),  G = the eval-mode walk on the raw g1,  A = sum_b A_b,  X1 = sum_b X1_b,
+ * A_b[j,k] = sum_c sum_{t<S} xp[t+j] xp[t+k],  X1_b[k] = sum_c sum_{t<S} xp[t+k]  (xp: the row padded as the convolution pads it).
+ * xtab_build writes the tables of the N trials of x once per data set (tab: eav_eegnet_fir_xtab_floats(N, klen) floats; per
+ * trial A_b [klen][klen], then X1_b [klen]; float64 sums rounded once, deterministic; about 361 KB per trial at 300 taps).
+ * wgrad_fft_xtab: tab belongs to the array x points to - row xidx[b] (xidx NULL: b) is the table of sample b, repeated indices
+ * count as often as they occur; ws: eav_eegnet_fir_wgrad_fft_xtab_ws_floats floats, 8-byte aligned.  Same number of launches
+ * as eav_eegnet_fir_wgrad_fft; agrees with it to rounding (not bit for bit); bit-reproducible run to run. */
+int64_t eav_eegnet_fir_xtab_floats(int N, int klen);
+int eav_eegnet_fir_xtab_build(const float* x, int N, int C, int S, int klen, float* tab, void* stream);
+int64_t eav_eegnet_fir_wgrad_fft_xtab_ws_floats(int B, int C, int S, int klen);
+int eav_eegnet_fir_wgrad_fft_xtab(const float* x, const int64_t* xidx, const float* tab, const float* w1, const float* g1,
+                                  const float* bn_params, float* ws, float* dW, int B, int C, int S, int klen, void* stream);
 int eav_eegnet_fir_fwd_indexed(const float* x, const int64_t* xidx, const float* w1, float* y1, float* stat_part, int B,
                                int C, int S, int klen, void* stream);
 int eav_eegnet_fir_wgrad_indexed(const float* x, const int64_t* xidx, const float* y1, const float* g1,

@@ -45,6 +45,9 @@ def configurations():
     for conv in ("fft", "mfma"):
         for mode in ("train", "eval"):
             out.append((f"S1408-graphstep-conv{conv}-{mode}", dict(FAST, Samples=1408), dict(conv_algo=conv), "graph-" + mode))
+    # (a train-mode GraphStep on the FFT FIR path takes the weight gradient from the input tables; this one reads y1)
+    out.append(("S1408-graphstep-convfft-train-xtab-off", dict(FAST, Samples=1408), dict(conv_algo="fft", fir_xtab=False),
+                "graph-train"))
     for mode in ("train", "eval"):       # the MFMA FIR pair's indexed entry points
         out.append((f"S500-graphstep-{mode}", dict(FAST, Samples=500), {}, "graph-" + mode))
     out.append(("generic-train", GENERIC, {}, "train"))

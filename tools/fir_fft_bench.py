@@ -53,6 +53,24 @@ def main():
         t_m = timeit(mf)
         print(f"wgrad {name} fft {t_f:.3f} ms   mfma {t_m:.3f} ms   max |diff| / max |dW| "
               f"{float((d_f - d_m).abs().max() / d_m.abs().max()):.2e}")
+    # train-mode weight gradient from the per-trial input tables (no y1 read): y1 must be firstConv(x), so it is compared
+    # with the y1-reading kernel on the FFT forward's output; the builder is timed for a whole subject of N trials
+    N = int(sys.argv[5]) if len(sys.argv) > 5 else 200
+    xs = torch.randn(N, C, S, device="cuda")
+    tab = torch.empty(L.plain("eav_eegnet_fir_xtab_floats", N, K), device="cuda")
+    t_b = timeit(lambda: L.call("eav_eegnet_fir_xtab_build", P(xs), N, C, S, K, P(tab), None), reps=3)
+    print(f"xtab build, {N} trials: {t_b:.2f} ms, {tab.numel() * 4 / 1e6:.1f} MB")
+    idx = torch.randperm(N, device="cuda")[:B].contiguous()
+    L.call("eav_eegnet_fir_fwd_fft", P(xs), P(idx), P(w), P(y_f), P(pf), B, C, S, K, None)
+    ws2 = torch.empty(L.plain("eav_eegnet_fir_wgrad_fft_xtab_ws_floats", B, C, S, K), device="cuda")
+    d_t = torch.empty(8, K, device="cuda")
+    t_o = timeit(lambda: L.call("eav_eegnet_fir_wgrad_fft", P(xs), P(idx), P(y_f), P(g1), P(bn), P(ws), P(d_f), B, C, S, K, None))
+    t_e = timeit(lambda: L.call("eav_eegnet_fir_wgrad_fft", P(xs), P(idx), None, P(g1), P(bn), P(ws), P(d_m), B, C, S, K, None))
+    t_t = timeit(lambda: L.call("eav_eegnet_fir_wgrad_fft_xtab", P(xs), P(idx), P(tab), P(w), P(g1), P(bn), P(ws2), P(d_t),
+                                B, C, S, K, None))
+    L.call("eav_eegnet_fir_wgrad_fft", P(xs), P(idx), P(y_f), P(g1), P(bn), P(ws), P(d_f), B, C, S, K, None)
+    print(f"wgrad train, indexed: y1-reading {t_o:.3f} ms   tables {t_t:.3f} ms   (eval {t_e:.3f} ms)   max |diff| / max |dW| "
+          f"{float((d_t - d_f).abs().max() / d_f.abs().max()):.2e}")
 
 
 if __name__ == "__main__":
