@@ -66,6 +66,7 @@ SIGNATURES = {
     "eav_dense_wide_fwd": [_p, _p, _p, _p, _i, _i, _i, _p],
     "eav_dense_wide_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "eav_ce_wide_fwd_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p],
+    "eav_ce_general_fwd_bwd": [_p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _i, _p],
     "eav_bce_logits_fwd_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p],
     "eav_mse_fwd_bwd": [_p, _p, _p, _p, _p, _i, _i, _p],
     "eav_scale_by_scalar": [_p, _p, _i64, _p],
@@ -80,6 +81,7 @@ SIGNATURES = {
     "eav_step_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "eav_gather_rows": [_p, _p, _p, _i, _i64, _p],
     "eav_gather_i64": [_p, _p, _p, _i, _p],
+    "eav_augment_gather": [_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p],
     "eav_gemm_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _f, _p,
                      _i, _p, _p, _i, _i, _p],
     "eav_gemm_f32_splitk": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
@@ -216,6 +218,7 @@ PLAIN = {
     "eav_conv64_wgrad_nparts": ([_i, _i], _i),
     "eav_dense_wide_bwd_ws_floats": ([_i, _i, _i], _i64),
     "eav_ce_wide_ws_floats": ([_i], _i64),
+    "eav_ce_general_ws_floats": ([_i], _i64),
     "eav_head_loss_ws_floats": ([_i], _i64),
     "eav_grad_chunk_elems": ([], _i64),
     "eav_grad_nchunks": ([_i64], _i64),

@@ -44,6 +44,13 @@ def _longest_clip(x):
 
 
 class AudioModelTrainer(FineTuneBase):
+    # SpecAugment-style masking of the log-mel features in unfrozen epochs, set between construction and train() like
+    # FineTuneBase's regularisers: up to two bands of < time_mask frames and two of < freq_mask mel bins per clip are set
+    # to mask_fill - 0.0, the mean of the normalised features (torchaudio's TimeMasking / FrequencyMasking, AST's recipe)
+    time_mask = 0
+    freq_mask = 0
+    mask_fill = 0.0
+
     def __init__(self, DATA, model_path, sub='', num_classes=5, weight_decay=1e-5, lr=0.001, batch_size=128, *,
                  problem_type=None, max_length=None):
         device = require_gpu("AudioModelTrainer")

@@ -16,9 +16,21 @@ import numpy as np
 import torch
 
 from . import _lib
+from .augment import BatchAugment, EpochPlan
 from .optim import BCEWithLogitsLoss, CrossEntropyLoss, FusedAdam, MSELoss
 from .runtime import DeviceLoader
 from .transformer import PROBLEM_TYPES, Encoder
+
+
+def balanced_class_weights(labels, n_classes):
+    """n / (n_classes * count_c) over the valid labels, float64 [n_classes]: sklearn's compute_class_weight("balanced")
+    for the classes 0 .. n_classes - 1; a class without a sample gets 0 (it is never a target)."""
+    y = np.asarray(labels).reshape(-1)
+    y = y[(y >= 0) & (y < n_classes)].astype(np.int64)
+    counts = np.bincount(y, minlength=n_classes).astype(np.float64)
+    w = np.zeros(n_classes, dtype=np.float64)
+    w[counts > 0] = len(y) / (n_classes * counts[counts > 0])
+    return w
 
 
 def require_gpu(who):
@@ -54,6 +66,25 @@ class FineTuneBase:
     max_grad_norm = None
     gradient_accumulation_steps = 1
 
+    # Regularisers, set the same way (single-label classification only, except the masks and the flip):
+    #   label_smoothing   HF TrainingArguments' label_smoothing_factor: CrossEntropyLoss(label_smoothing=...)
+    #   class_weights     None, one weight per class, or "balanced": n / (classes * count_c) over the training labels
+    #                     (sklearn's compute_class_weight; a class without a training sample gets 0)
+    #   mixup_alpha       > 0: mixup with lambda ~ Beta(alpha, alpha), the partner drawn from the sample's own micro-batch,
+    #                     the loss taken on the mixed soft targets
+    #   augment_seed      seeds the augmentation draws (with the count of augmented epochs: augment.BatchAugment.plan_epoch)
+    # AudioModelTrainer adds time_mask / freq_mask, ImageClassifierTrainer hflip.  The criterion options hold in every
+    # phase; the inputs are augmented only in epochs with freeze=False and never in _evaluate - the frozen phase keeps its
+    # feature cache.  Training accuracy counts against the primary (first) label of a mixed sample.  With every option
+    # at its default nothing of this is entered: the trainers launch what they always did.
+    label_smoothing = 0.0
+    class_weights = None
+    mixup_alpha = 0.0
+    augment_seed = 0
+    _criterion_key = (0.0, None)        # (label_smoothing, class weights) loss_fn was built with
+    _augmented_epochs = 0               # epochs planned so far: the `epoch` of BatchAugment.plan_epoch
+    _augment = None                     # the phase's BatchAugment (None: batches are plain gathers)
+
     def _build(self, model_path, n_classes, lr, device, problem_type=None):
         """The reference's order (Transformer_Audio.py:22-24, Transformer_Vision.py:29-30): load the checkpoint with the
         head its config.json describes - 527 AudioSet or 1000 ImageNet classes for the stock downloads - then replace
@@ -79,6 +110,68 @@ class FineTuneBase:
     def _classifies(self):
         """Integer class labels and cross-entropy (the reference's schedule)."""
         return self.problem_type in (None, "single_label_classification")
+
+    def _resolved_class_weights(self):
+        """class_weights as a tuple of floats (None: unweighted)."""
+        cw = self.class_weights
+        if cw is None:
+            return None
+        n_classes = self.model.cfg.num_labels
+        if isinstance(cw, str):
+            if cw != "balanced":
+                raise ValueError(f'class_weights {cw!r}: expected None, a sequence or "balanced"')
+            return tuple(balanced_class_weights(self.train_dataloader.y.cpu().numpy(), n_classes).tolist())
+        cw = tuple(float(v) for v in np.asarray(cw, dtype=np.float64).reshape(-1))
+        if len(cw) != n_classes:
+            raise ValueError(f"class_weights: {len(cw)} weights for {n_classes} classes")
+        return cw
+
+    def _apply_regularisers(self, freeze):
+        """The criterion of this phase (rebuilt when label_smoothing / class_weights changed since it was built) and the
+        phase's BatchAugment (None: batches are plain gathers)."""
+        smoothing, mixup = float(self.label_smoothing), float(self.mixup_alpha)
+        if not self._classifies() and (smoothing != 0.0 or self.class_weights is not None or mixup != 0.0):
+            raise ValueError(f"label_smoothing, class_weights and mixup_alpha need single-label classification, not "
+                             f"problem_type {self.problem_type!r}")
+        if mixup < 0.0:
+            raise ValueError(f"mixup_alpha {self.mixup_alpha!r} must be >= 0")
+        if self._classifies():
+            key = (smoothing, self._resolved_class_weights())
+            if key != self._criterion_key:
+                self.loss_fn = CrossEntropyLoss(weight=key[1], label_smoothing=smoothing)
+                self._criterion_key = key
+        aug = BatchAugment(mixup, getattr(self, "time_mask", 0), getattr(self, "freq_mask", 0),
+                           getattr(self, "hflip", False), self.augment_seed)
+        aug.fill = float(getattr(self, "mask_fill", 0.0))
+        self._augment = aug if aug.active and not freeze else None
+
+    def _epoch_plan(self, batches):
+        """The augmentation plan of a training epoch over `batches` (None: plain gathers)."""
+        aug = self._augment
+        if aug is None:
+            return None
+        plan = EpochPlan(aug, self.train_dataloader, batches, self._augmented_epochs,
+                         soft=self._classifies() and aug.mixup_alpha > 0.0, num_classes=self.model.cfg.num_labels)
+        self._augmented_epochs += 1
+        return plan
+
+    def _train_batch(self, dl, idx, fc, plan):
+        """(logits, targets, primary labels) of one training micro-batch: the head on cached features, or the model on the
+        gathered - under a plan: augmented - inputs.  The primary labels are what accuracy counts against; they differ
+        from the targets only under mixup, whose targets are class probabilities."""
+        if fc is not None and fc["have_train"]:       # cached features: only the labels of the batch are gathered
+            tb = dl.gather_labels(idx)
+            return self.model.head(fc["train"][self._index(idx)]).logits, tb, tb
+        if plan is not None:
+            xb, tb = plan.next(len(idx))
+            primary = dl.gather_labels(idx) if plan.soft else tb
+        else:
+            xb, tb = dl.gather(idx)
+            primary = tb
+        logits = self.model(xb).logits
+        if fc is not None:
+            fc["train"][self._index(idx)] = self.model.last_features()
+        return logits, tb, primary
 
     def _loader(self, x, y, shuffle):
         if self._classifies():
@@ -130,6 +223,7 @@ class FineTuneBase:
             p.requires_grad = (not freeze) or (id(p) in trainable_head)
         if self.grad_sync is not None:       # frozen phase: only the head's gradients cross the xGMI links
             self.grad_sync.set_active(self.model.head_grad_ranges() if freeze else None)
+        self._apply_regularisers(freeze)
         self._begin_phase_cache(freeze)
         return lr
 
@@ -188,23 +282,18 @@ class FineTuneBase:
         dl = self.train_dataloader
         seen, nb = 0, len(dl)
         fc = getattr(self, "_feat_cache", None)
-        for k, idx in enumerate(dl.index_batches(), start=1):
+        batches = dl.index_batches()
+        plan = self._epoch_plan(batches)
+        for k, idx in enumerate(batches, start=1):
             self.optimizer.zero_grad()
-            if fc is not None and fc["have_train"]:       # cached features: only the labels of the batch are gathered
-                tb = dl.gather_labels(idx)
-                logits = self.model.head(fc["train"][self._index(idx)]).logits
-            else:
-                xb, tb = dl.gather(idx)
-                logits = self.model(xb).logits
-                if fc is not None:
-                    fc["train"][self._index(idx)] = self.model.last_features()
+            logits, tb, primary = self._train_batch(dl, idx, fc, plan)
             loss = self.loss_fn(logits, tb)
             loss.backward()
             if self.grad_sync is not None:
                 self.grad_sync()
             self.optimizer.step()
             if classifies:
-                correct += (logits.argmax(dim=-1) == tb).sum()
+                correct += (logits.argmax(dim=-1) == primary).sum()
                 seen += tb.size(0)
             else:
                 seen += self._count(logits.detach(), tb, correct, loss.detach())
@@ -226,6 +315,7 @@ class FineTuneBase:
         seen, nb = 0, len(dl)
         fc = getattr(self, "_feat_cache", None)
         batches = list(dl.index_batches())
+        plan = self._epoch_plan(batches)        # partners come from the micro-batch, never from the rest of the group
         k = 0
         for first in range(0, len(batches), k_acc):
             group = batches[first:first + k_acc]
@@ -233,21 +323,14 @@ class FineTuneBase:
             for j, idx in enumerate(group):
                 k += 1
                 self.optimizer.zero_grad()
-                if fc is not None and fc["have_train"]:
-                    tb = dl.gather_labels(idx)
-                    logits = self.model.head(fc["train"][self._index(idx)]).logits
-                else:
-                    xb, tb = dl.gather(idx)
-                    logits = self.model(xb).logits
-                    if fc is not None:
-                        fc["train"][self._index(idx)] = self.model.last_features()
+                logits, tb, primary = self._train_batch(dl, idx, fc, plan)
                 loss = self.loss_fn(logits, tb)
                 loss.backward()
                 if self.grad_sync is not None:
                     self.grad_sync()
                 self.optimizer.accumulate(len(idx) / total, last=j == len(group) - 1)
                 if classifies:
-                    correct += (logits.argmax(dim=-1) == tb).sum()
+                    correct += (logits.argmax(dim=-1) == primary).sum()
                     seen += tb.size(0)
                 else:
                     seen += self._count(logits.detach(), tb, correct, loss.detach())

@@ -9,7 +9,8 @@ Host-side mirrors of what the reference trainers construct:
   * ``nn.BCEWithLogitsLoss()`` / ``nn.MSELoss()``      the other two losses HF's classification models pick by
     ``config.problem_type`` (transformers/loss/loss_utils.py, ForSequenceClassificationLoss)
 
-The arithmetic runs in libeav_hip.so (``eav_adam_step`` / ``eav_ce_fwd_bwd`` / ``eav_bce_logits_fwd_bwd`` / ``eav_mse_fwd_bwd``).
+The arithmetic runs in libeav_hip.so (``eav_adam_step`` / ``eav_ce_fwd_bwd`` / ``eav_bce_logits_fwd_bwd`` / ``eav_mse_fwd_bwd``;
+``eav_ce_general_fwd_bwd`` for ``CrossEntropyLoss(weight=..., label_smoothing=...)`` and class-probability targets).
 Parameters that live in one flat buffer (``flatten_parameters``) are updated
 with one launch per run of tensors that share a step count - the frozen and
 unfrozen fine-tuning phases give the head and the backbone different counts
@@ -379,18 +380,18 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
 
 class _CEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, scores, targets, flag, scratch=None):
+    def forward(ctx, scores, targets, flag, scratch=None, general=None):
         B, NC = scores.shape
         loss = torch.empty((), dtype=torch.float32, device=scores.device)
         need_grad = ctx.needs_input_grad[0]
         dsc = torch.empty_like(scores) if need_grad else None      # no gradient buffer under no_grad (validate())
-        _ce_launch(scratch, scores, targets, loss, dsc, None, flag)
+        _ce_launch(scratch, scores, targets, loss, dsc, None, flag, general)
         ctx.dsc = dsc
         return loss
 
     @staticmethod
     def backward(ctx, gout):
-        return _seeded(ctx.dsc, gout), None, None, None
+        return _seeded(ctx.dsc, gout), None, None, None, None
 
 
 def _seeded(dsc, gout):
@@ -421,10 +422,17 @@ def head_is_wide(algo, classes, found):
     return algo == "wide" or (algo == "auto" and classes > HEAD_NARROW_CLASSES)
 
 
-def _ce_launch(scratch, scores, targets, loss, dsc, ncorrect, flag):
-    """eav_ce_fwd_bwd (scratch None), or eav_ce_wide_fwd_bwd (one wave per row) with its per-row scratch."""
+def _ce_launch(scratch, scores, targets, loss, dsc, ncorrect, flag, general=None):
+    """eav_ce_fwd_bwd (scratch None), or eav_ce_wide_fwd_bwd (one wave per row) with its per-row scratch; with `general` =
+    (class weights or None, label smoothing), eav_ce_general_fwd_bwd on int64 labels or fp32 class probabilities."""
     B, NC = scores.shape
-    if scratch is not None:
+    if general is not None:
+        weight, smoothing = general
+        soft = targets.dtype == torch.float32
+        _lib.call("eav_ce_general_fwd_bwd", scores.data_ptr(), None if soft else targets.data_ptr(),
+                  targets.data_ptr() if soft else None, _lib.ptr(weight), float(smoothing), loss.data_ptr(), _lib.ptr(dsc),
+                  _lib.ptr(ncorrect), flag.data_ptr(), scratch.data_ptr(), B, NC, _lib.stream_ptr())
+    elif scratch is not None:
         _lib.call("eav_ce_wide_fwd_bwd", scores.data_ptr(), targets.data_ptr(), loss.data_ptr(), _lib.ptr(dsc),
                   _lib.ptr(ncorrect), flag.data_ptr(), scratch.data_ptr(), B, NC, _lib.stream_ptr())
     else:
@@ -458,12 +466,33 @@ class CrossEntropyLoss:
     ``head_algo`` routes by the class count like ``Encoder.head_algo``: "auto" (default; EAV_HEAD_ALGO overrides) takes
     eav_ce_wide_fwd_bwd above 16 classes and eav_ce_fwd_bwd up to there, "wide" forces the former at any width and
     "narrow" the latter, which raises above 16 classes as the Encoder's does.  The wide kernel's per-row scratch is kept
-    on the criterion, one buffer per (batch, device): nothing is allocated for it in the launch path."""
+    on the criterion, one buffer per (batch, device): nothing is allocated for it in the launch path.
 
-    def __init__(self):
+    ``weight`` (per-class weights, anything torch.as_tensor takes) and ``label_smoothing`` (0 <= eps <= 1) are torch's
+    arguments of those names, keyword-only and fixed at construction - read-only attributes: a captured step has the
+    scalar baked in, a later change could silently not apply.  Targets may also be fp32 class probabilities
+    [batch, classes] (mixup's soft targets).  The defaults on class indices launch what they always did; anything else
+    goes to eav_ce_general_fwd_bwd (csrc/head_ce_soft.hip) at every width - ``head_algo`` does not apply there - with
+    its own per-(batch, device) scratch.  The weights are kept as an fp32 tensor and moved to the device of the first
+    scores; a length other than the class count raises.  With class indices the mean is over the weights of the valid
+    labels (torch's rule); labels whose weights add up to 0 give a NaN loss like an all-ignored batch."""
+
+    def __init__(self, *, weight=None, label_smoothing=0.0):
+        smoothing = float(label_smoothing)
+        if not 0.0 <= smoothing <= 1.0:
+            raise ValueError(f"CrossEntropyLoss: label_smoothing {label_smoothing!r} is outside [0, 1]")
+        if weight is not None:
+            weight = torch.as_tensor(weight).detach().to(torch.float32).reshape(-1).contiguous().clone()
+            if weight.numel() < 1:
+                raise ValueError("CrossEntropyLoss: weight is empty")
+        self._weight, self._smoothing = weight, smoothing
         self._flag = None
         self._scratch = {}
+        self._general_scratch = {}
         self.head_algo = os.environ.get("EAV_HEAD_ALGO", "auto")
+
+    weight = property(lambda self: self._weight, doc="per-class weights (fp32 tensor) or None; fixed at construction")
+    label_smoothing = property(lambda self: self._smoothing, doc="the smoothing factor; fixed at construction")
 
     def _wide(self, classes):
         return head_is_wide(self.head_algo, classes, "the scores have")
@@ -477,6 +506,38 @@ class CrossEntropyLoss:
         if key not in self._scratch:
             self._scratch[key] = torch.empty(_lib.plain("eav_ce_wide_ws_floats", B), dtype=torch.float32, device=scores.device)
         return self._scratch[key]
+
+    def _route(self, scores, targets):
+        """(scratch, general) of _ce_launch: the default criterion on class indices keeps its two kernels, everything else
+        takes the general one with the weights on the scores' device."""
+        if targets.dim() == 1 and self._weight is None and self._smoothing == 0.0:
+            return self._scratch_for(scores), None
+        B, NC = scores.shape
+        if self._weight is not None:
+            if self._weight.numel() != NC:
+                raise ValueError(f"CrossEntropyLoss: {self._weight.numel()} class weights for {NC} classes")
+            if self._weight.device != scores.device:
+                self._weight = self._weight.to(scores.device)
+        key = (B, scores.device)
+        if key not in self._general_scratch:
+            self._general_scratch[key] = torch.empty(_lib.plain("eav_ce_general_ws_floats", B), dtype=torch.float32,
+                                                     device=scores.device)
+        return self._general_scratch[key], (self._weight, self._smoothing)
+
+    @staticmethod
+    def _targets(scores, targets, who):
+        """int64 [B] class indices or fp32 [B, NC] class probabilities, contiguous."""
+        if targets.dim() == 2:
+            if tuple(targets.shape) != tuple(scores.shape):
+                raise _lib.EavError(f"{who}: class-probability targets {tuple(targets.shape)} for scores {tuple(scores.shape)}")
+            if targets.dtype != torch.float32:
+                targets = targets.float()
+            return targets.contiguous()
+        if targets.dim() != 1 or targets.numel() != scores.shape[0]:
+            raise _lib.EavError(f"{who}: {targets.numel()} targets for {scores.shape[0]} rows of scores")
+        if targets.dtype != torch.int64:
+            targets = targets.long()
+        return targets.contiguous()
 
     def check(self):
         if self._flag is not None:
@@ -493,8 +554,12 @@ class CrossEntropyLoss:
         if not scores.is_cuda or scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
             raise _lib.EavError("CrossEntropyLoss.accumulate: scores must be a contiguous fp32 [batch, classes] device tensor")
         # every operand goes to the kernel as a raw pointer: a host tensor would be dereferenced on the GPU
-        if not isinstance(targets, torch.Tensor) or targets.device != scores.device or targets.dim() != 1 \
-                or targets.numel() != scores.shape[0]:
+        soft = isinstance(targets, torch.Tensor) and targets.dim() == 2
+        if soft and not targets.is_floating_point():
+            raise TypeError(f"CrossEntropyLoss.accumulate: [batch, classes] targets are class probabilities, got {targets.dtype}")
+        if not isinstance(targets, torch.Tensor) or targets.device != scores.device \
+                or (tuple(targets.shape) != tuple(scores.shape) if soft else
+                    targets.dim() != 1 or targets.numel() != scores.shape[0]):
             raise _lib.EavError(f"CrossEntropyLoss.accumulate: targets must be {scores.shape[0]} labels on {scores.device} "
                                 "(no CPU fallback: move the loader's tensors to the device)")
         if not isinstance(loss_out, torch.Tensor) or loss_out.device != scores.device or loss_out.dtype != torch.float32 \
@@ -503,25 +568,25 @@ class CrossEntropyLoss:
         if not isinstance(ncorrect, torch.Tensor) or ncorrect.device != scores.device or ncorrect.dtype != torch.int32 \
                 or ncorrect.numel() < 1:
             raise _lib.EavError(f"CrossEntropyLoss.accumulate: ncorrect must be an int32 tensor on {scores.device}")
-        if targets.dtype != torch.int64:
-            targets = targets.long()
+        targets = self._targets(scores, targets, "CrossEntropyLoss.accumulate")
         if self._flag is None or self._flag.device != scores.device:
             self._flag = torch.zeros((), dtype=torch.int32, device=scores.device)
-        _ce_launch(self._scratch_for(scores), scores, targets.contiguous(), loss_out, None, ncorrect, self._flag)
+        scratch, general = self._route(scores, targets)
+        _ce_launch(scratch, scores, targets, loss_out, None, ncorrect, self._flag, general)
 
     def __call__(self, scores, targets):
+        if isinstance(targets, torch.Tensor) and targets.dim() == 2 and not targets.is_floating_point():
+            raise TypeError(f"CrossEntropyLoss: [batch, classes] targets are class probabilities, got {targets.dtype}")
         if not isinstance(scores, torch.Tensor) or not scores.is_cuda or not targets.is_cuda:
             raise _lib.EavError("CrossEntropyLoss needs device tensors (no CPU fallback)")
         if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
             raise _lib.EavError(f"CrossEntropyLoss: scores must be a contiguous fp32 [batch, classes] tensor, got "
                                 f"{tuple(scores.shape)} {scores.dtype}")
-        if targets.dim() != 1 or targets.numel() != scores.shape[0]:
-            raise _lib.EavError(f"CrossEntropyLoss: {targets.numel()} targets for {scores.shape[0]} rows of scores")
-        if targets.dtype != torch.int64:
-            targets = targets.long()
+        targets = self._targets(scores, targets, "CrossEntropyLoss")
         if self._flag is None or self._flag.device != scores.device:
             self._flag = torch.zeros((), dtype=torch.int32, device=scores.device)
-        return _CEFn.apply(scores, targets.contiguous(), self._flag, self._scratch_for(scores))
+        scratch, general = self._route(scores, targets)
+        return _CEFn.apply(scores, targets, self._flag, scratch, general)
 
 
 class _ElementLossFn(torch.autograd.Function):

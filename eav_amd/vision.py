@@ -46,6 +46,10 @@ def _load_processor(model_path):
 
 
 class ImageClassifierTrainer(FineTuneBase):
+    # Set between construction and train() like FineTuneBase's regularisers: in unfrozen epochs every frame is mirrored
+    # left-right with probability 0.5
+    hflip = False
+
     def __init__(self, DATA, model_path, sub='', num_labels=5, lr=5e-5, batch_size=128, *, problem_type=None,
                  image_size=None):
         device = require_gpu("ImageClassifierTrainer")

@@ -287,6 +287,22 @@ int eav_bce_logits_fwd_bwd(const float* logits, const float* targets, float* los
                            int B, int NC, void* stream);
 int eav_mse_fwd_bwd(const float* logits, const float* targets, float* loss, float* dlogits, float* ws, int B, int NC,
                     void* stream);
+/* torch.nn.functional.cross_entropy(in, target, weight=weight, label_smoothing=eps), mean reduction (csrc/head_ce_soft.hip),
+ * laid out like eav_ce_wide_fwd_bwd: one wave per row, row terms in ws (eav_ce_general_ws_floats(B) floats) added in row order,
+ * no atomics, two runs give the same bits.  Exactly one of y (class indices [B]) and t (fp32 class probabilities [B,NC], not
+ * validated) is non-NULL; weight [NC] may be NULL (all 1); 0 <= label_smoothing <= 1; loss, din, ncorrect and bad_label may
+ * each be NULL; 1 <= NC <= EAV_HEAD_MAX_CLASSES, B * NC < 2^31.  With W = sum_c w_c and logp = log-softmax(in):
+ *   y:  D = sum over the valid rows (0 <= y < NC) of w[y_b];
+ *       loss = [(1 - eps) sum_b w[y_b] (-logp[b,y_b]) + (eps / NC) sum_b sum_c w_c (-logp[b,c])] / D over the valid rows,
+ *       din[b,j] = [(1 - eps) w[y_b] (p_j - [j == y_b]) + (eps / NC) (p_j W - w_j)] / D; -100 is ignored, any other label
+ *       outside [0,NC) is treated the same way and reported through *bad_label (eav_ce_fwd_bwd's encoding); D == 0 (every row
+ *       ignored, or labels whose weights add up to 0): NaN loss, zero din.
+ *   t:  t' = (1 - eps) t + eps / NC;  loss = -sum_b sum_c w_c t'[b,c] logp[b,c] / B;
+ *       din[b,j] = [p_j sum_c w_c t'_c - w_j t'_j] / B.
+ * *ncorrect += the rows whose first arg-maximum of `in` is the label (y) / the first arg-maximum of the row of t. */
+int64_t eav_ce_general_ws_floats(int B);
+int eav_ce_general_fwd_bwd(const float* in, const int64_t* y, const float* t, const float* weight, float label_smoothing,
+                           float* loss, float* din, int* ncorrect, int* bad_label, float* ws, int B, int NC, void* stream);
 /* v[i] *= *scalar (device scalar): the upstream gradient applied to the stored d loss / d scores. */
 int eav_scale_by_scalar(float* v, const float* scalar, int64_t n, void* stream);
 /* torch.optim.Adam (decoupled=0) / AdamW (decoupled=1) update of one flat tensor; step >= 1.
@@ -323,6 +339,17 @@ int eav_scale_ranges(const void* jobs, int njobs, int64_t nchunks, const float* 
  * Replaces the per-batch host->device copies of the reference loops (EEGNet_tor.py:100-101). */
 int eav_gather_rows(const float* src, const int64_t* idx, float* out, int nrows, int64_t row_elems, void* stream);
 int eav_gather_i64(const int64_t* src, const int64_t* idx, int64_t* out, int n, void* stream);
+/* Batch assembly with augmentation (csrc/augment.hip): x is the split [N,R,C] (C contiguous; an AST clip is [time, mel], a
+ * ViT frame [3,H,W] is [3 H, W]); record b of `table` (EAV_AUGMENT_RECORD_INTS int32 words: source i, partner j, the bits of
+ * the fp32 lambda, flip flag, two row bands [r0,r1), two column bands [c0,c1)) describes out[b]:
+ *   out[b,r,c] = fill inside any band, else lambda x[i,r,c'] + (1 - lambda) x[j,r,c'], c' = flip ? C - 1 - c : c.
+ * lambda == 1 never reads the partner and hands the source's bits through (a record (i, *, 1.0, 0, empty bands) is
+ * eav_gather_rows); empty, full-range and overlapping bands are legal; i and j are trusted like eav_gather_rows' indices.
+ * tout [B,NC] (may be NULL; needs y, the split's int64 labels) = lambda onehot(y[i]) + (1 - lambda) onehot(y[j]), 1 where the
+ * labels coincide.  16-byte accesses when C % 4 == 0, the grid sized by the batch's elements, no atomics. */
+#define EAV_AUGMENT_RECORD_INTS 12
+int eav_augment_gather(const float* x, const int64_t* y, const int32_t* table, float fill, float* out, float* tout, int B,
+                       int R, int C, int NC, void* stream);
 /* *counter += 1 on the stream (device-resident step counters for hipGraph replay). */
 int eav_counter_inc(int64_t* counter, void* stream);
 int eav_counter_inc4(int64_t* c0, int64_t* c1, int64_t* c2, int64_t* c3, void* stream);   /* distinct counters; NULL = skip */

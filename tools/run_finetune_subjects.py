@@ -8,6 +8,8 @@
     python tools/run_finetune_subjects.py audio --max-length auto     (clips at their own length, not padded to 1024 frames:
                                                                        5 s -> 506 frames, 602 tokens instead of 1214)
     python tools/run_finetune_subjects.py audio --audio-root Datasets/EAV      (the dataset folder, Dataload_audio.py:87-93)
+    python tools/run_finetune_subjects.py audio --label-smoothing 0.1 --mixup-alpha 0.4 --time-mask 48 --freq-mask 24
+                                                     (the regularisers of finetune.FineTuneBase; vision: --hflip)
     python -m torch.distributed.run --nproc-per-node 8 tools/run_finetune_subjects.py audio ...
 
 Every subject is one `AudioModelTrainer` / `ImageClassifierTrainer` run with the reference's hyper-parameters
@@ -81,11 +83,30 @@ def main():
                     "inside every optimiser step (trainer.max_grad_norm); default: no clipping, like the reference")
     ap.add_argument("--grad-accum", type=int, default=1, metavar="K", help="one optimiser step per K micro-batches "
                     "(trainer.gradient_accumulation_steps): effective batch K x the launch batch")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="E", help="cross-entropy label smoothing in [0, 1] "
+                    "(trainer.label_smoothing, HF's label_smoothing_factor)")
+    ap.add_argument("--class-weights", choices=("balanced",), default=None, help="weight the classes by n / (classes x "
+                    "count) over the training labels (trainer.class_weights)")
+    ap.add_argument("--mixup-alpha", type=float, default=0.0, metavar="A", help="mixup with lambda ~ Beta(A, A) in the unfrozen "
+                    "epochs (trainer.mixup_alpha)")
+    ap.add_argument("--time-mask", type=int, default=0, metavar="T", help="audio only: two bands of < T frames masked per clip "
+                    "in the unfrozen epochs (trainer.time_mask)")
+    ap.add_argument("--freq-mask", type=int, default=0, metavar="F", help="audio only: two bands of < F mel bins masked per "
+                    "clip in the unfrozen epochs (trainer.freq_mask)")
+    ap.add_argument("--hflip", action="store_true", help="vision only: mirror every frame left-right with probability 0.5 in "
+                    "the unfrozen epochs (trainer.hflip)")
+    ap.add_argument("--augment-seed", type=int, default=0, help="seed of the augmentation draws (trainer.augment_seed)")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     if args.grad_accum < 1 or (args.max_grad_norm is not None and not args.max_grad_norm > 0):
         ap.error("--grad-accum takes K >= 1 and --max-grad-norm F > 0")
+    if not 0.0 <= args.label_smoothing <= 1.0 or not args.mixup_alpha >= 0.0 or args.time_mask < 0 or args.freq_mask < 0:
+        ap.error("--label-smoothing takes E in [0, 1], --mixup-alpha A >= 0, --time-mask / --freq-mask integers >= 0")
     audio = args.kind == "audio"
+    if audio and args.hflip:
+        ap.error("--hflip is a vision option")
+    if not audio and (args.time_mask or args.freq_mask):
+        ap.error("--time-mask and --freq-mask are audio options")
     if audio and args.image_size is not None:
         ap.error("--image-size is a vision option")
     if not audio and args.max_length is not None:
@@ -131,6 +152,12 @@ def main():
                     tr = ImageClassifierTrainer(data, model_path=path, sub=f"subject_{sub:02d}", num_labels=5, lr=5e-5,
                                                 batch_size=bsz, image_size=args.image_size)
                 tr.max_grad_norm, tr.gradient_accumulation_steps = args.max_grad_norm, args.grad_accum
+                tr.label_smoothing, tr.class_weights = args.label_smoothing, args.class_weights
+                tr.mixup_alpha, tr.augment_seed = args.mixup_alpha, args.augment_seed
+                if audio:
+                    tr.time_mask, tr.freq_mask = args.time_mask, args.freq_mask
+                else:
+                    tr.hflip = args.hflip
                 if n > 1:
                     eav_dist.attach(tr, group=groups[sub])
                 tr.train(epochs=args.frozen_epochs, lr=5e-4, freeze=True)
