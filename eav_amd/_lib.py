@@ -203,6 +203,10 @@ PLAIN = {
     "eav_eegnet_fir_xtab_floats": ([_i, _i], _i64),
     "eav_eegnet_fir_wgrad_fft_xtab_ws_floats": ([_i, _i, _i, _i], _i64),
     "eav_eegnet_fir_wgrad_nparts": ([_i, _i, _i], _i),
+    "eav_eegnet_fir_plan": ([_i, _i, _i], _i),
+    "eav_eegnet_block1_infer_nblocks": ([_i, _i], _i),
+    "eav_eegnet_dw_plan": ([_i], _i),
+    "eav_conv64_plan": ([_i, _i], _i),
     "eav_conv64_ntiles": ([_i], _i),
     "eav_tconv_fwd_nparts": ([_i, _i, _i, _i, _i], _i),
     "eav_shallow_embed_nparts": ([_i, _i], _i),

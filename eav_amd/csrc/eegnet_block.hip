@@ -467,13 +467,20 @@ __global__ __launch_bounds__(NT, DWB_WPE) void dw_bwd_kernel(const float* __rest
 
 }  // namespace
 
+// Thread geometry of dw_fwd / dw_bwd_fused for a row length, as CG * 1000 + NT (channel groups, threads): the one statement
+// of the rule, read by both launchers and by eav_eegnet_dw_plan
+static int dw_geometry(int S) { return S <= 256 ? 4256 : (S <= 512 ? 4512 : 1256); }
+
+extern "C" int eav_eegnet_dw_plan(int S) { return S > 0 ? dw_geometry(S) : 0; }
+
 static int dw_fwd_launch(const float* y1, const float* bn1, const float* w2, float* z, float* stat_part, int B, int C,
                          int S, const float* bn2, float* p2, void* stream) {
   dim3 grid(cdiv(S, 1024), F1, B);
-  if (S <= 256)         // short rows: channel groups (see the kernel)
+  const int geo = dw_geometry(S);
+  if (geo == 4256)      // short rows: channel groups (see the kernel)
     hipLaunchKernelGGL((dw_fwd_kernel<4, 256>), grid, dim3(256), 0, (hipStream_t)stream, y1, bn1, w2, z, stat_part, C, S,
                        bn2, p2);
-  else if (S <= 512)
+  else if (geo == 4512)
     hipLaunchKernelGGL((dw_fwd_kernel<4, 512>), grid, dim3(512), 0, (hipStream_t)stream, y1, bn1, w2, z, stat_part, C, S,
                        bn2, p2);
   else
@@ -528,13 +535,14 @@ static int dw_bwd_fused_launch(const char* name, const float* y1, const float* z
 #define DWB_LAUNCH(CG, NT, SUMS)                                                                                        \
   hipLaunchKernelGGL((dw_bwd_kernel<true, CG, NT, SUMS>), grid, dim3(NT), 0, (hipStream_t)stream, y1, nullptr, bn1, w2, g1, \
                      stat_part, w_part, C, S, fu)
+  const int geo = dw_geometry(S);
   if (bn2_part) {
-    if (S <= 256) DWB_LAUNCH(4, 256, true);
-    else if (S <= 512) DWB_LAUNCH(4, 512, true);
+    if (geo == 4256) DWB_LAUNCH(4, 256, true);
+    else if (geo == 4512) DWB_LAUNCH(4, 512, true);
     else DWB_LAUNCH(1, 256, true);
   } else {
-    if (S <= 256) DWB_LAUNCH(4, 256, false);
-    else if (S <= 512) DWB_LAUNCH(4, 512, false);
+    if (geo == 4256) DWB_LAUNCH(4, 256, false);
+    else if (geo == 4512) DWB_LAUNCH(4, 512, false);
     else DWB_LAUNCH(1, 256, false);
   }
 #undef DWB_LAUNCH
@@ -583,6 +591,7 @@ extern "C" int eav_bn_elu_pool_bwd_reduce(const float* dp, const float* u, const
                                           const uint64_t* seed_dev, void* stream) {
   EAV_REQUIRE(dp && u && bn && part && B > 0 && CH > 0 && T >= P, "eav_bn_elu_pool_bwd_reduce: bad arguments");
   EAV_REQUIRE(P == 4 || P == 8, "eav_bn_elu_pool_bwd_reduce: pool %d not in {4,8}", P);
+  EAV_REQUIRE(drop_p > -1.f && drop_p < 1.f, "eav_bn_elu_pool_bwd_reduce: dropout %f outside (-1,1)", drop_p);
   if (P == 4)
     hipLaunchKernelGGL(pool_bwd_reduce_kernel<4>, dim3(B * CH), dim3(256), 0, (hipStream_t)stream, dp, u, bn, part,
                        CH, T, drop_p, seed, mask, seed_dev);
@@ -598,6 +607,7 @@ static int pool_bwd_apply_launch(const char* name, const float* dp, const float*
                                  const uint8_t* mask, const uint64_t* seed_dev, void* stream) {
   EAV_REQUIRE(dp && u && bn && (m12 || part) && du && B > 0 && CH > 0 && T >= P, "%s: bad arguments", name);
   EAV_REQUIRE(P == 4 || P == 8, "%s: pool %d not in {4,8}", name, P);
+  EAV_REQUIRE(drop_p > -1.f && drop_p < 1.f, "%s: dropout %f outside (-1,1)", name, drop_p);
   if (P == 4)
     hipLaunchKernelGGL(pool_bwd_apply_kernel<4>, dim3(B * CH), dim3(256), 0, (hipStream_t)stream, dp, u, bn, m12, du,
                        CH, T, drop_p, seed, mask, seed_dev, part);

@@ -242,16 +242,22 @@ extern "C" int eav_conv64_ntiles(int T) { return cdiv(T, TT); }
 // few 128-sample items -> 32-sample items (4x the blocks; every block still keeps its weight slabs in registers)
 static bool conv64_small(int B, int T) { return B * cdiv(T, TT) < 128; }
 
+// output samples per work item of eav_conv64_fwd (32 / 128): what the launcher below instantiates
+extern "C" int eav_conv64_plan(int B, int T) {
+  if (B <= 0 || T <= 0) return 0;
+  return conv64_small(B, T) ? 32 : TT;
+}
+
 // number of statistics partials eav_conv64_fwd writes ([nparts][128])
 extern "C" int eav_conv64_fwd_nparts(int B, int T) {
-  const int nitems = conv64_small(B, T) ? B * cdiv(T, 32) : B * cdiv(T, TT);
+  const int nitems = B * cdiv(T, eav_conv64_plan(B, T));
   return nitems < 256 ? nitems : 256;
 }
 
 extern "C" int eav_conv64_fwd(const float* in, const float* wT, float* out, float* stat_part, int B, int T, int padl,
                               void* stream) {
   EAV_REQUIRE(in && wT && out && B > 0 && T > 0 && padl >= 0 && padl <= 15, "eav_conv64_fwd: bad arguments");
-  if (conv64_small(B, T))
+  if (eav_conv64_plan(B, T) == 32)
     hipLaunchKernelGGL(conv64_fwd_kernel<32>, dim3(eav_conv64_fwd_nparts(B, T)), dim3(V2_THREADS), 0,
                        (hipStream_t)stream, in, wT, out, stat_part, B, T, padl, cdiv(T, 32));
   else

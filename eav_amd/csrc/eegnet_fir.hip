@@ -464,10 +464,15 @@ __global__ __launch_bounds__(256, 1) void fir_dw_infer_kernel(const float* __res
 
 static int fir_grid(int64_t nwork) { return nwork < 512 ? (int)nwork : 512; }
 static int wgrad_grid(int64_t nwork) { return nwork < 768 ? (int)nwork : 768; }
+static int infer_grid(int64_t nwork) { return nwork < 256 ? (int)nwork : 256; }
+// The selection rules, stated once: the launchers and eav_eegnet_fir_plan both read them.
+static int fir_nstep(int klen) { return klen <= 65 ? 34 : (klen <= 129 ? 66 : 152); }     // fir_fwd / fir_dw_infer NSTEP
+static int wgrad_nt(int klen) { return klen <= 64 ? 2 : (klen <= 128 ? 4 : 10); }          // fir_wgrad WG_NT
+static int fir_nseg(int S) { return cdiv(cdiv(S, TILE), TPS); }                            // fir_fwd items per (b, c) row
+static int infer_nseg(int S) { return cdiv(cdiv(S, TILE), 4); }                            // fir_dw_infer items per sample
 
 extern "C" int eav_eegnet_fir_fwd_nparts(int B, int C, int S) {
-  int ntiles = cdiv(S, TILE), nseg = cdiv(ntiles, TPS);
-  return fir_grid((int64_t)B * C * nseg);
+  return fir_grid((int64_t)B * C * fir_nseg(S));
 }
 
 extern "C" int eav_eegnet_fir_fwd_indexed(const float* x, const int64_t* xidx, const float* w1, float* y1,
@@ -483,13 +488,14 @@ extern "C" int eav_eegnet_fir_fwd_indexed(const float* x, const int64_t* xidx, c
                                           float* stat_part, int B, int C, int S, int klen, void* stream) {
   EAV_REQUIRE(x && w1 && y1 && stat_part && B > 0 && C > 0 && S > 0, "eav_eegnet_fir_fwd: bad arguments");
   EAV_REQUIRE(klen >= 1 && klen <= 300, "eav_eegnet_fir_fwd: kernLength %d outside [1,300]", klen);
-  const int ntiles = cdiv(S, TILE), nseg = cdiv(ntiles, TPS);
+  const int ntiles = cdiv(S, TILE), nseg = fir_nseg(S);
   const int nwork = B * C * nseg;
 #define EAV_FIR_FWD(NS)                                                                                         \
   hipLaunchKernelGGL(fir_fwd_kernel<NS>, dim3(fir_grid(nwork)), dim3(256), 0, (hipStream_t)stream, x, w1, y1,  \
                      stat_part, B * C, C, S, klen, (klen - 1) / 2, nseg, ntiles, xidx)
-  if (klen <= 65) EAV_FIR_FWD(34);
-  else if (klen <= 129) EAV_FIR_FWD(66);
+  const int nstep = fir_nstep(klen);
+  if (nstep == 34) EAV_FIR_FWD(34);
+  else if (nstep == 66) EAV_FIR_FWD(66);
   else EAV_FIR_FWD(152);
 #undef EAV_FIR_FWD
   EAV_CHECK_LAUNCH("eav_eegnet_fir_fwd");
@@ -507,6 +513,27 @@ extern "C" int eav_eegnet_fir_wgrad_nparts(int B, int C, int S) {
   int nchunk, CH;
   wgrad_geometry(S, &nchunk, &CH);
   return wgrad_grid((int64_t)B * C * nchunk);
+}
+
+extern "C" int eav_eegnet_block1_infer_nblocks(int B, int S) {
+  if (B <= 0 || S <= 0) return 0;
+  return infer_grid((int64_t)B * infer_nseg(S));
+}
+
+// What the three launchers of this file run for a row length and a kernel length (0 for arguments they reject)
+extern "C" int eav_eegnet_fir_plan(int S, int klen, int what) {
+  if (S <= 0 || klen < 1 || klen > 300) return 0;
+  int nchunk, CH;
+  wgrad_geometry(S, &nchunk, &CH);
+  switch (what) {
+    case EAV_FIR_PLAN_FWD_NSTEP: return fir_nstep(klen);
+    case EAV_FIR_PLAN_FWD_NSEG: return fir_nseg(S);
+    case EAV_FIR_PLAN_WGRAD_NCHUNK: return nchunk;
+    case EAV_FIR_PLAN_WGRAD_CH: return CH;
+    case EAV_FIR_PLAN_WGRAD_NT: return wgrad_nt(klen);
+    case EAV_FIR_PLAN_INFER_NSEG: return infer_nseg(S);
+  }
+  return 0;
 }
 
 // part: [nparts][8][klen] floats; sum over parts = dL/d(firstConv.weight)
@@ -537,8 +564,9 @@ extern "C" int eav_eegnet_fir_wgrad_indexed(const float* x, const int64_t* xidx,
       hipLaunchKernelGGL((fir_wgrad_kernel<NT, true>), dim3(wgrad_grid(nwork)), dim3(256), 0, (hipStream_t)stream, x, \
                          y1, g1, bn_params, part, B * C, C, S, klen, (klen - 1) / 2, nchunk, CH, xidx);               \
   } while (0)
-  if (klen <= 64) EAV_FIR_WG(2);
-  else if (klen <= 128) EAV_FIR_WG(4);
+  const int nt = wgrad_nt(klen);
+  if (nt == 2) EAV_FIR_WG(2);
+  else if (nt == 4) EAV_FIR_WG(4);
   else EAV_FIR_WG(10);
 #undef EAV_FIR_WG
   EAV_CHECK_LAUNCH("eav_eegnet_fir_wgrad");
@@ -554,14 +582,14 @@ extern "C" int eav_eegnet_block1_infer(const float* x, const int64_t* xidx, cons
   EAV_REQUIRE(x && w1 && bn1 && w2 && bn2 && p2 && B > 0 && C > 0 && C <= 32 && S >= 4 && (S & 3) == 0,
               "eav_eegnet_block1_infer: bad arguments (need C <= 32, S %% 4 == 0)");
   EAV_REQUIRE(klen >= 1 && klen <= 300, "eav_eegnet_block1_infer: kernLength %d outside [1,300]", klen);
-  const int ntiles = cdiv(S, TILE), nseg = cdiv(ntiles, 4);
-  const int64_t nwork = (int64_t)B * nseg;
-  const int grid = nwork < 256 ? (int)nwork : 256;
+  const int nseg = infer_nseg(S);
+  const int grid = infer_grid((int64_t)B * nseg);
 #define EAV_FIR_INF(NS)                                                                                          \
   hipLaunchKernelGGL(fir_dw_infer_kernel<NS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w1, bn1, w2, bn2, p2, \
                      B, C, S, klen, (klen - 1) / 2, nseg, xidx)
-  if (klen <= 65) EAV_FIR_INF(34);
-  else if (klen <= 129) EAV_FIR_INF(66);
+  const int nstep = fir_nstep(klen);
+  if (nstep == 34) EAV_FIR_INF(34);
+  else if (nstep == 66) EAV_FIR_INF(66);
   else EAV_FIR_INF(152);
 #undef EAV_FIR_INF
   EAV_CHECK_LAUNCH("eav_eegnet_block1_infer");

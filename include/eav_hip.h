@@ -110,6 +110,18 @@ int eav_eegnet_fir_fwd_indexed(const float* x, const int64_t* xidx, const float*
                                int C, int S, int klen, void* stream);
 int eav_eegnet_fir_wgrad_indexed(const float* x, const int64_t* xidx, const float* y1, const float* g1,
                                  const float* bn_params, float* part, int B, int C, int S, int klen, void* stream);
+/* What eav_eegnet_fir_fwd / _wgrad / eav_eegnet_block1_infer (and their indexed forms) launch for rows of S samples and a
+ * klen-tap kernel - the single statement of each selection rule, shared with the launchers (0 for arguments they reject):
+ * FWD_NSTEP the MFMA K-steps of the forward / inference instantiation (34 / 66 / 152), FWD_NSEG the forward's work items per
+ * (sample, electrode) row, WGRAD_NCHUNK / WGRAD_CH the weight gradient's items per row and their length, WGRAD_NT its
+ * column tiles (2 / 4 / 10), INFER_NSEG the inference kernel's items per sample.  eav_eegnet_block1_infer_nblocks = its grid. */
+enum { EAV_FIR_PLAN_FWD_NSTEP = 0, EAV_FIR_PLAN_FWD_NSEG = 1, EAV_FIR_PLAN_WGRAD_NCHUNK = 2, EAV_FIR_PLAN_WGRAD_CH = 3,
+       EAV_FIR_PLAN_WGRAD_NT = 4, EAV_FIR_PLAN_INFER_NSEG = 5 };
+int eav_eegnet_fir_plan(int S, int klen, int what);
+int eav_eegnet_block1_infer_nblocks(int B, int S);
+/* Thread geometry of eav_eegnet_dw_fwd(_pool_eval) and eav_eegnet_dw_bwd_fused(_eval) for rows of S samples, as CG * 1000 + NT
+ * (channel groups x threads per block: 4256, 4512 or 1256; eav_eegnet_dw_bwd always runs 1256). */
+int eav_eegnet_dw_plan(int S);
 /* firstBN -> ELU -> depthwiseConv (EEGNet_tor.py:52-54): y1 -> z [B,64,S];
  * stat_part [B*ceil(S/1024)][128]. */
 int eav_eegnet_dw_fwd(const float* y1, const float* bn1, const float* w2, float* z, float* stat_part, int B, int C,
@@ -171,6 +183,8 @@ int eav_eegnet_step_prologue(const float* w, float* wT_fwd, float* wT_bwd, int64
 int eav_conv64_ntiles(int T);
 /* out[b,o,t] = sum wT[(i*16+k)][o]*in[b,i,t+k-padl]; stat_part (may be NULL) [eav_conv64_fwd_nparts()][128]. */
 int eav_conv64_fwd_nparts(int B, int T);
+/* output samples per work item of eav_conv64_fwd for this shape (32 or 128): the instantiation the launcher takes */
+int eav_conv64_plan(int B, int T);
 int eav_conv64_fwd(const float* in, const float* wT, float* out, float* stat_part, int B, int T, int padl,
                    void* stream);
 /* separableConv and its data gradient in the frequency domain (csrc/eegnet_conv64_fft.hip): the same exact-fp32 linear maps
