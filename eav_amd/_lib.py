@@ -76,6 +76,8 @@ SIGNATURES = {
     "eav_grad_fold": [_p, _p, _i, _i64, _p, _i, _p, _p],
     "eav_grad_clip_finish": [_p, _i64, _f, _p, _p],
     "eav_scale_ranges": [_p, _i, _i64, _p, _p],
+    "eav_adam_jobs_begin": [_p, _i, _p, _i, _p, _i, _i64, _i64, _d, _d, _f, _f, _p],
+    "eav_adam_step_jobs": [_p, _i, _i64, _f, _f, _f, _i, _p, _p],
     "eav_counter_inc": [_p, _p],
     "eav_counter_inc4": [_p, _p, _p, _p, _p],
     "eav_step_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
@@ -226,6 +228,7 @@ PLAIN = {
     "eav_head_loss_ws_floats": ([_i], _i64),
     "eav_grad_chunk_elems": ([], _i64),
     "eav_grad_nchunks": ([_i64], _i64),
+    "eav_adam_jobs_nchunks": ([_i64], _i64),
     "eav_layernorm_bwd_nparts": ([_i], _i),
     "eav_gemm_f32_plan": ([_i, _i, _i], _i),
     "eav_gemm_f32_splitk_plan": ([_i, _i, _i], _i),
@@ -242,6 +245,10 @@ PLAIN = {
 }
 
 EXPORTS = sorted(list(SIGNATURES) + list(PLAIN))
+
+# int64 words of a job row of eav_adam_step_jobs and of its schedule record (EAV_ADAM_JOB_WORDS, EAV_ADAM_SCHED_WORDS)
+JOB_WORDS = 10
+SCHED_WORDS = 4
 
 # test / tuning overrides (include/eav_hip_tuning.h): process-global, never called by the package
 TUNING = {"eav_gemm_sp_set_tile": [_i], "eav_gemm_sp_set_splitk": [_i], "eav_sp_set_convert_blocks": [_i],

@@ -99,22 +99,24 @@ class AudioModelTrainer(FineTuneBase):
         return ASTFeatureExtractor(**T)(x, sampling_rate=16000, padding='max_length', return_tensors='pt')['input_values']
 
     def train(self, epochs=20, lr=None, freeze=True):
-        self._enter_phase(lr, freeze)
+        self._enter_phase(lr, freeze, epochs)
         for epoch in range(epochs):
             correct, seen = self._train_one_epoch()
             if not self._classifies():
                 train_metric = float(correct.item()) / seen
+                lr_text = self._lr_text()
                 rows = self._evaluate()
                 test_metric = self._metric_text(sum(r[1] for r in rows) / sum(r[2] for r in rows))
                 self._keep_outputs(rows, epoch == epochs - 1, freeze)
-                print(f"Epoch {epoch + 1}/{epochs}, Training {self._metric_text(train_metric)}, Test {test_metric}")
+                print(f"Epoch {epoch + 1}/{epochs}, Training {self._metric_text(train_metric)}, Test {test_metric}{lr_text}")
                 with open('training_performance_audio.txt', 'a') as f:
                     f.write(f"{self.sub}, Epoch {epoch + 1}, Test {test_metric}\n")
                 continue
             train_accuracy = int(correct.item()) / seen
+            lr_text = self._lr_text()
             rows = self._evaluate()
             test_accuracy = sum(r[1] for r in rows) / sum(r[2] for r in rows)      # sample-weighted (:92-97)
             self._keep_outputs(rows, epoch == epochs - 1, freeze)
-            print(f"Epoch {epoch + 1}/{epochs}, Training Accuracy: {train_accuracy * 100:.2f}%, Test Accuracy: {test_accuracy * 100:.2f}%")
+            print(f"Epoch {epoch + 1}/{epochs}, Training Accuracy: {train_accuracy * 100:.2f}%, Test Accuracy: {test_accuracy * 100:.2f}%{lr_text}")
             with open('training_performance_audio.txt', 'a') as f:
                 f.write(f"{self.sub}, Epoch {epoch + 1}, Test Accuracy: {test_accuracy * 100:.2f}%\n")

@@ -18,7 +18,7 @@ ASAN_TARGET = ../libeav_hip_asan.so
 .PHONY: asan
 asan: $(ASAN_TARGET)
 
-$(ASAN_DIR)/%.o: %.hip eav_common.h ../../include/eav_hip.h
+$(ASAN_DIR)/%.o: %.hip eav_common.h job_table.h ../../include/eav_hip.h
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -c $< -o $@
 

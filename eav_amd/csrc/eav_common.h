@@ -145,6 +145,37 @@ __device__ __forceinline__ void st4(float* p, int i, int n, bool vec, const floa
   }
 }
 
+// One element of torch.optim.Adam / AdamW (foreach/fused semantics, fp32 state) - the arithmetic of adam_kernel
+// (head_optim.hip) and adam_jobs_kernel (adam_jobs.hip), in one place so that both give the same bits:
+//   adamw: p *= 1 - lr*wd;  adam: g += wd*p
+//   m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// SCALED: the gradient is gv * gs, rounded to fp32 before anything else uses it - the update is the one a gradient tensor
+// scaled beforehand gets.  pv, mv, vv come in as the stored values and leave as the values to store.
+// The contraction is written out - it is the one hipcc chose for the stand-alone adam_kernel: 1 - lr*wd, g + wd*p and the
+// final p - (lr/bc1) q are one fma each, the moments are products and sums rounded one by one - so that every kernel that
+// calls this gives the same bits, whatever the vectoriser makes of its surroundings.
+template <bool SCALED>
+__device__ __forceinline__ void adam_update(float& pv, float gv, float& mv, float& vv, float gs, float lr, float b1, float b2,
+                                            float eps, float wd, float bc1, float bc2_sqrt, int decoupled) {
+#pragma clang fp contract(off)
+  if (SCALED) {
+    gv *= gs;
+    asm volatile("" : "+v"(gv));      // the rounded product is a value of its own: never one half of a later fma
+  }
+  if (wd != 0.f) {
+    if (decoupled) pv *= __builtin_fmaf(-lr, wd, 1.f); else gv = __builtin_fmaf(wd, pv, gv);
+  }
+  mv = b1 * mv + (1.f - b1) * gv;
+  vv = b2 * vv + (1.f - b2) * gv * gv;
+  const float denom = sqrtf(vv) / bc2_sqrt + eps;
+  pv = __builtin_fmaf(-(lr / bc1), mv / denom, pv);
+}
+// the bias corrections of step count st as the capturable kernels form them from a device-resident count
+__device__ __forceinline__ void adam_bias_corrections(float b1, float b2, double st, float& bc1, float& bc2_sqrt) {
+  bc1 = (float)(1.0 - pow((double)b1, st));
+  bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, st));
+}
+
 // 2^x by the native v_exp_f32 (the base-2 softmax of the attention kernels)
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 // erf-GELU through libm's erff (gemm_sp.hip has its own erfc-fit gelu_erf)

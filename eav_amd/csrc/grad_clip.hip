@@ -15,39 +15,13 @@
 // the four wave totals are added through LDS as (w0 + w1) + (w2 + w3).  The kernels are bound by their one pass over
 // the ranges; the fp64 arithmetic hides under it.
 #include "eav_common.h"
+#include "job_table.h"
 #include "../../include/eav_hip.h"
 
 namespace {
 
-constexpr int VPT = 8;                        // 16-byte vectors per thread and chunk
-constexpr int CHUNK = 256 * 4 * VPT;          // 8192 elements = 32 KB
-constexpr int MAX_BLOCKS = 2048;              // 256 CUs x 8 workgroups: the grid of a streaming kernel
-
-__device__ __forceinline__ int64_t job_chunks(int64_t n) { return n > 0 ? (n + CHUNK - 1) / CHUNK : 0; }
-
-// The job that holds chunk c.  (j, base) = a job and the number of its first chunk, carried from the workgroup's previous
-// chunk: c only grows.  Wave-uniform: the table is read through the scalar cache.
-__device__ __forceinline__ bool locate(const int64_t* __restrict__ jobs, int njobs, int64_t c, int& j, int64_t& base) {
-  while (j < njobs) {
-    const int64_t nc = job_chunks(jobs[2 * j + 1]);
-    if (c < base + nc) return true;
-    base += nc;
-    ++j;
-  }
-  return false;       // nchunks larger than the table holds: nothing is touched
-}
-
-// How the `len` elements at p are cut: h head elements, nvec 16-byte vectors, r tail elements.
-struct Cut {
-  int h, nvec, r;
-};
-__device__ __forceinline__ Cut cut_chunk(const float* p, int len) {
-  Cut c;
-  c.h = min(len, (int)((4u - (unsigned)(((uintptr_t)p >> 2) & 3u)) & 3u));
-  c.nvec = (len - c.h) >> 2;
-  c.r = (len - c.h) & 3;
-  return c;
-}
+constexpr int VPT = JOB_VPT;                  // 16-byte vectors per thread and chunk (job_table.h, shared with adam_jobs.hip)
+constexpr int CHUNK = JOB_CHUNK;              // 8192 elements = 32 KB
 
 __device__ __forceinline__ double sq(float x) { return (double)x * (double)x; }
 __device__ __forceinline__ double sq4(const float4& a) { return ((sq(a.x) + sq(a.y)) + sq(a.z)) + sq(a.w); }
@@ -63,11 +37,6 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__device__ __forceinline__ float4 ld_g4(const float* p, bool vec) {
-  if (vec) return *reinterpret_cast<const float4*>(p);
-  return make_float4(p[0], p[1], p[2], p[3]);
-}
-
 __global__ __launch_bounds__(256) void sumsq_kernel(const int64_t* __restrict__ jobs, int njobs, int64_t nchunks,
                                                     double* __restrict__ partials) {
   __shared__ double red[4];
@@ -75,11 +44,11 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const int64_t* __restrict__ 
   int j = 0;
   int64_t base = 0;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    if (!locate(jobs, njobs, c, j, base)) return;
+    if (!job_locate<2, 1>(jobs, njobs, c, j, base)) return;
     const int64_t off = (c - base) * CHUNK;
     const float* p = reinterpret_cast<const float*>(jobs[2 * j]) + off;
     const int len = (int)min((int64_t)CHUNK, jobs[2 * j + 1] - off);
-    const Cut k = cut_chunk(p, len);
+    const JobCut k = job_cut_chunk(p, len);
     const float4* pv = reinterpret_cast<const float4*>(p + k.h);
     float4 v[VPT];
 #pragma unroll
@@ -108,12 +77,12 @@ __global__ __launch_bounds__(256) void fold_kernel(const int64_t* __restrict__ j
   int j = 0;
   int64_t base = 0;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    if (!locate(jobs_g, njobs, c, j, base)) return;
+    if (!job_locate<2, 1>(jobs_g, njobs, c, j, base)) return;
     const int64_t off = (c - base) * CHUNK;
     const float* g = reinterpret_cast<const float*>(jobs_g[2 * j]) + off;
     float* a = reinterpret_cast<float*>(jobs_a[2 * j]) + off;
     const int len = (int)min((int64_t)CHUNK, jobs_g[2 * j + 1] - off);
-    const Cut k = cut_chunk(a, len);
+    const JobCut k = job_cut_chunk(a, len);
     const bool gvec = (((uintptr_t)(g + k.h)) & 15) == 0;
     float4* av = reinterpret_cast<float4*>(a + k.h);
     const float* gb = g + k.h;
@@ -121,7 +90,7 @@ __global__ __launch_bounds__(256) void fold_kernel(const int64_t* __restrict__ j
 #pragma unroll
     for (int u = 0; u < VPT; ++u) {
       const int i = t + 256 * u;
-      gv[u] = i < k.nvec ? ld_g4(gb + 4 * (int64_t)i, gvec) : make_float4(0.f, 0.f, 0.f, 0.f);
+      gv[u] = i < k.nvec ? job_ld4(gb + 4 * (int64_t)i, gvec) : make_float4(0.f, 0.f, 0.f, 0.f);
       if (!FIRST) ov[u] = i < k.nvec ? av[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     double acc = 0.0;
@@ -167,11 +136,11 @@ __global__ __launch_bounds__(256) void scale_ranges_kernel(const int64_t* __rest
   int j = 0;
   int64_t base = 0;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    if (!locate(jobs, njobs, c, j, base)) return;
+    if (!job_locate<2, 1>(jobs, njobs, c, j, base)) return;
     const int64_t off = (c - base) * CHUNK;
     float* p = reinterpret_cast<float*>(jobs[2 * j]) + off;
     const int len = (int)min((int64_t)CHUNK, jobs[2 * j + 1] - off);
-    const Cut k = cut_chunk(p, len);
+    const JobCut k = job_cut_chunk(p, len);
     float4* pv = reinterpret_cast<float4*>(p + k.h);
     float4 v[VPT];
 #pragma unroll
@@ -207,8 +176,6 @@ __global__ __launch_bounds__(256) void clip_finish_kernel(const double* __restri
   }
 }
 
-int grid_for(int64_t nchunks) { return (int)(nchunks < MAX_BLOCKS ? nchunks : MAX_BLOCKS); }
-
 }  // namespace
 
 extern "C" int64_t eav_grad_chunk_elems(void) { return CHUNK; }
@@ -218,7 +185,7 @@ extern "C" int64_t eav_grad_nchunks(int64_t n) { return n > 0 ? cdiv64(n, CHUNK)
 
 extern "C" int eav_grad_sumsq(const void* jobs, int njobs, int64_t nchunks, double* partials, void* stream) {
   EAV_REQUIRE(jobs && partials && njobs > 0 && nchunks > 0, "eav_grad_sumsq: bad arguments (table, partials, njobs > 0, nchunks > 0)");
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream, (const int64_t*)jobs, njobs,
+  hipLaunchKernelGGL(sumsq_kernel, dim3(job_grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream, (const int64_t*)jobs, njobs,
                      nchunks, partials);
   EAV_CHECK_LAUNCH("eav_grad_sumsq");
   return EAV_OK;
@@ -229,10 +196,10 @@ extern "C" int eav_grad_fold(const void* jobs_g, const void* jobs_acc, int njobs
   EAV_REQUIRE(jobs_g && jobs_acc && weight && njobs > 0 && nchunks > 0,
               "eav_grad_fold: bad arguments (two tables, weight, njobs > 0, nchunks > 0)");
   if (first)
-    hipLaunchKernelGGL(fold_kernel<true>, dim3(grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(fold_kernel<true>, dim3(job_grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream,
                        (const int64_t*)jobs_g, (const int64_t*)jobs_acc, njobs, nchunks, weight, partials);
   else
-    hipLaunchKernelGGL(fold_kernel<false>, dim3(grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(fold_kernel<false>, dim3(job_grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream,
                        (const int64_t*)jobs_g, (const int64_t*)jobs_acc, njobs, nchunks, weight, partials);
   EAV_CHECK_LAUNCH("eav_grad_fold");
   return EAV_OK;
@@ -248,7 +215,7 @@ extern "C" int eav_grad_clip_finish(const double* partials, int64_t nchunks, flo
 
 extern "C" int eav_scale_ranges(const void* jobs, int njobs, int64_t nchunks, const float* scalar, void* stream) {
   EAV_REQUIRE(jobs && scalar && njobs > 0 && nchunks > 0, "eav_scale_ranges: bad arguments (table, scalar, njobs > 0, nchunks > 0)");
-  hipLaunchKernelGGL(scale_ranges_kernel, dim3(grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream, (const int64_t*)jobs,
+  hipLaunchKernelGGL(scale_ranges_kernel, dim3(job_grid_for(nchunks)), dim3(256), 0, (hipStream_t)stream, (const int64_t*)jobs,
                      njobs, nchunks, scalar);
   EAV_CHECK_LAUNCH("eav_scale_ranges");
   return EAV_OK;

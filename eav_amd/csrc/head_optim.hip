@@ -220,26 +220,15 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   float gs = 1.f;
   if (SCALED) gs = *gscale;
   if (step_dev) {  // capturable: bias corrections from a device-resident step count
-    const double st = (double)*step_dev;
-    bc1 = (float)(1.0 - pow((double)b1, st));
-    bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, st));
+    adam_bias_corrections(b1, b2, (double)*step_dev, bc1, bc2_sqrt);
   }
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    float pv = p[i], gv = g[i];
-    if (SCALED) {
-      gv *= gs;
-      asm volatile("" : "+v"(gv));      // the rounded product is a value of its own: never one half of a later fma
-    }
-    if (wd != 0.f) {
-      if (decoupled) pv *= 1.f - lr * wd; else gv += wd * pv;
-    }
-    const float mv = b1 * m[i] + (1.f - b1) * gv;
-    const float vv = b2 * v[i] + (1.f - b2) * gv * gv;
+    float pv = p[i], mv = m[i], vv = v[i];
+    adam_update<SCALED>(pv, g[i], mv, vv, gs, lr, b1, b2, eps, wd, bc1, bc2_sqrt, decoupled);    // eav_common.h
     m[i] = mv;
     v[i] = vv;
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    p[i] = pv - (lr / bc1) * (mv / denom);
+    p[i] = pv;
   }
 }
 

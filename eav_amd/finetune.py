@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .augment import BatchAugment, EpochPlan
-from .optim import BCEWithLogitsLoss, CrossEntropyLoss, FusedAdam, MSELoss
+from .optim import BCEWithLogitsLoss, CrossEntropyLoss, FusedAdam, LRSchedule, MSELoss
 from .runtime import DeviceLoader
 from .transformer import PROBLEM_TYPES, Encoder
 
@@ -31,6 +31,53 @@ def balanced_class_weights(labels, n_classes):
     w = np.zeros(n_classes, dtype=np.float64)
     w[counts > 0] = len(y) / (n_classes * counts[counts > 0])
     return w
+
+
+def encoder_layer_id(name, layers):
+    """The layer id of an Encoder parameter for layer-wise learning-rate decay (BEiT's get_num_layer_for_vit): 0 for the
+    embeddings (cls / distillation tokens, position table, patch projection), i + 1 for encoder layer i, layers + 1 for
+    the final LayerNorm and the classifier (AST's classifier.layernorm included)."""
+    parts = name.split(".")
+    if "embeddings" in parts:
+        return 0
+    if "layers" in parts:
+        return int(parts[parts.index("layers") + 1]) + 1
+    return layers + 1
+
+
+def encoder_no_decay(name):
+    """Whether HF Trainer's rule keeps weight decay off this Encoder parameter: biases, LayerNorm weights, and the
+    parameters that are no matrices at all - the tokens and the position table."""
+    if name.endswith(".bias") or name.endswith("_token") or name.endswith("position_embeddings"):
+        return True
+    return name.endswith(".weight") and "layernorm" in name.split(".")[-2]
+
+
+def encoder_param_groups(model, lr, weight_decay, layer_decay=1.0, decay_bias_and_norm=True):
+    """torch param-group dicts for an Encoder (a pure function of its parameter names: runs on a CPU model).
+
+    layer_decay: the group of layer id `i` (encoder_layer_id) gets lr * layer_decay ** (layers + 1 - i) - the head is
+    updated at lr, the embeddings at lr * layer_decay ** (layers + 1).  decay_bias_and_norm=False moves every parameter
+    encoder_no_decay names into groups with weight_decay 0.  Every parameter lands in exactly one group; next to
+    "params", "lr" and "weight_decay" a group carries "names" (its parameters' names, in named_parameters() order),
+    "layer_id" (None when layer_decay is 1: ids are not told apart) and "lr_scale".  With both options at their defaults
+    there is one group."""
+    layer_decay = float(layer_decay)
+    if not 0.0 < layer_decay <= 1.0:
+        raise ValueError(f"layer_decay {layer_decay!r} is outside (0, 1]")
+    layers = model.cfg.layers
+    groups = {}
+    for name, p in model.named_parameters():
+        lid = encoder_layer_id(name, layers) if layer_decay != 1.0 else None
+        decays = bool(decay_bias_and_norm) or not encoder_no_decay(name)
+        key = (-1 if lid is None else lid, not decays)
+        if key not in groups:
+            scale = 1.0 if lid is None else layer_decay ** (layers + 1 - lid)
+            groups[key] = {"params": [], "names": [], "lr": float(lr) * scale,
+                           "weight_decay": float(weight_decay) if decays else 0.0, "layer_id": lid, "lr_scale": scale}
+        groups[key]["params"].append(p)
+        groups[key]["names"].append(name)
+    return [groups[k] for k in sorted(groups)]
 
 
 def require_gpu(who):
@@ -81,6 +128,24 @@ class FineTuneBase:
     class_weights = None
     mixup_alpha = 0.0
     augment_seed = 0
+    # Learning-rate options, set the same way; with all of them at their defaults _enter_phase does what it always did
+    # and the optimiser keeps its one-launch-per-run path:
+    #   lr_scheduler_type     "constant", "constant_with_warmup", "linear" or "cosine" (optim.LRSchedule, the lambdas of
+    #                         transformers.get_scheduler): a fresh schedule per train() call over epochs x optimiser steps
+    #                         per epoch (gradient_accumulation_steps counts groups, not micro-batches)
+    #   warmup_ratio          the share of those steps spent warming up (rounded up, HF's rule); warmup_steps, when not
+    #                         None, is the count itself
+    #   layer_decay           < 1: layer-wise learning-rate decay, layer i at lr * layer_decay ** (layers + 1 - id)
+    #   decay_bias_and_norm   False: no weight decay on biases, LayerNorm weights, tokens and the position table
+    # Any of them switches the optimiser to its multi-tensor step (optim.FusedAdam(multi_tensor=True)): two launches per
+    # step whatever the groups look like.  The epoch line gains ", lr x" under a non-constant schedule.
+    lr_scheduler_type = "constant"
+    warmup_ratio = 0.0
+    warmup_steps = None
+    layer_decay = 1.0
+    decay_bias_and_norm = True
+    _lr_options_applied = False         # the optimiser's groups / schedule were rebuilt by _apply_lr_options
+
     _criterion_key = (0.0, None)        # (label_smoothing, class weights) loss_fn was built with
     _augmented_epochs = 0               # epochs planned so far: the `epoch` of BatchAugment.plan_epoch
     _augment = None                     # the phase's BatchAugment (None: batches are plain gathers)
@@ -213,10 +278,61 @@ class FineTuneBase:
             self.loss_fn.accumulate(logits, tb, self._batch_loss, out)
         return tb.numel()
 
-    def _enter_phase(self, lr, freeze):
+    def _lr_options_active(self):
+        return (self.lr_scheduler_type != "constant" or float(self.layer_decay) != 1.0 or not self.decay_bias_and_norm)
+
+    def _schedule_for(self, epochs):
+        """The LRSchedule of a train() call of `epochs` epochs (None: constant)."""
+        if self.lr_scheduler_type == "constant":
+            return None
+        if self.lr_scheduler_type not in LRSchedule.KINDS:
+            raise ValueError(f"lr_scheduler_type {self.lr_scheduler_type!r}: expected one of {LRSchedule.KINDS}")
+        if epochs is None:
+            raise ValueError(f"lr_scheduler_type {self.lr_scheduler_type!r} needs the number of epochs of the phase")
+        k_acc = max(1, int(self.gradient_accumulation_steps))
+        total = int(epochs) * -(-len(self.train_dataloader) // k_acc)
+        if self.warmup_steps is not None:
+            warmup = int(self.warmup_steps)
+        else:
+            if not 0.0 <= float(self.warmup_ratio) <= 1.0:
+                raise ValueError(f"warmup_ratio {self.warmup_ratio!r} is outside [0, 1]")
+            warmup = int(np.ceil(total * float(self.warmup_ratio)))
+        return LRSchedule(self.lr_scheduler_type, warmup, total)
+
+    def _apply_lr_options(self, lr, epochs):
+        """Rebuild the optimiser's param groups from encoder_param_groups and attach the phase's schedule; the state is
+        keyed by parameter and survives.  Back at the defaults after a phase with options: one group, no schedule, the
+        one-launch-per-run step again."""
+        opt = self.optimizer
+        template = {k: v for k, v in opt.param_groups[0].items() if k not in ("params", "names", "layer_id", "lr_scale")}
+        if not self._lr_options_active():
+            if self._lr_options_applied:
+                opt.param_groups = [dict(template, params=list(self.model.parameters()), lr=lr,
+                                         weight_decay=self._weight_decay)]
+                opt.set_schedule(None)
+                opt.multi_tensor = False
+                self._lr_options_applied = False
+            return
+        if not self._lr_options_applied:
+            self._weight_decay = opt.param_groups[0]["weight_decay"]
+        groups = encoder_param_groups(self.model, lr, self._weight_decay, self.layer_decay, self.decay_bias_and_norm)
+        opt.param_groups = [dict(template, **g) for g in groups]
+        opt.multi_tensor = True
+        opt.set_schedule(self._schedule_for(epochs))
+        self._lr_options_applied = True
+
+    def _lr_text(self):
+        """", lr x" for the epoch line under a non-constant schedule (one read-back per epoch), else ""."""
+        if self.lr_scheduler_type == "constant" or self.optimizer.last_lr is None:
+            return ""
+        return f", lr {float(self.optimizer.last_lr.item()):.3e}"
+
+    def _enter_phase(self, lr, freeze, epochs=None):
         lr = self.initial_lr if lr is None else lr
         for group in self.optimizer.param_groups:
             group['lr'] = lr
+        if self._lr_options_active() or self._lr_options_applied:
+            self._apply_lr_options(lr, epochs)
         self.optimizer.max_grad_norm = self.max_grad_norm
         trainable_head = {id(p) for p in self.model.classifier.parameters()}
         for p in self.model.parameters():

@@ -19,6 +19,11 @@ unfrozen fine-tuning phases give the head and the backbone different counts
 Training-loop options (csrc/grad_clip.hip): ``FusedAdam(max_grad_norm=...)`` clips by the global L2 norm inside the
 step, ``FusedAdam.accumulate()`` folds the gradients of several backward passes into an accumulator the next step
 consumes, and ``clip_grad_norm_`` is torch's free function on the same kernels.  Nothing of it reads a value back.
+
+Learning-rate options (csrc/adam_jobs.hip): ``FusedAdam(multi_tensor=True)`` updates every tensor of every param group -
+each with its own ``lr`` / ``weight_decay`` and step count - in two launches over a device job table, and
+``FusedAdam.set_schedule(LRSchedule(...))`` scales the rates by ``transformers.get_scheduler``'s factors, evaluated on the
+device from a device-resident step count.  Off by default: the default step launches what it always did.
 """
 from __future__ import annotations
 
@@ -109,6 +114,87 @@ def _flat_slack(p):
     return 16 + 4 * getattr(p, "_eav_pad", 0) if getattr(p, "_eav_flat", None) is not None else 1
 
 
+class LRSchedule:
+    """The learning-rate multiplier of ``transformers.get_scheduler(kind, ...)`` for ``kind`` in ``KINDS``: warmup from 0
+    over ``num_warmup_steps`` optimiser steps, then constant, linear decay to 0 at ``num_training_steps``, or cosine decay
+    (``num_cycles`` = 0.5: half a wave, down to 0 at ``num_training_steps``).  ``t`` counts the optimiser steps completed
+    since the schedule was attached (``FusedAdam.set_schedule``), so the first step runs at ``factor(0)`` - 0 when there
+    is a warmup, exactly as ``LambdaLR`` behaves.  ``factor`` is the host float64 version, for printing and for tests;
+    the optimiser evaluates the same expressions on the device (csrc/adam_jobs.hip), from a device-resident ``t``."""
+
+    KINDS = ("constant", "constant_with_warmup", "linear", "cosine")
+
+    def __init__(self, kind, num_warmup_steps=0, num_training_steps=None, num_cycles=0.5):
+        if kind not in self.KINDS:
+            raise ValueError(f"LRSchedule: kind {kind!r}: expected one of {self.KINDS}")
+        if int(num_warmup_steps) != num_warmup_steps or num_warmup_steps < 0:
+            raise ValueError(f"LRSchedule: num_warmup_steps {num_warmup_steps!r} must be an integer >= 0")
+        if kind in ("linear", "cosine"):
+            if num_training_steps is None or int(num_training_steps) != num_training_steps or num_training_steps < 0:
+                raise ValueError(f"LRSchedule: kind {kind!r} needs num_training_steps, an integer >= 0, "
+                                 f"got {num_training_steps!r}")
+        self.kind = kind
+        self.num_warmup_steps = int(num_warmup_steps) if kind != "constant" else 0
+        self.num_training_steps = 0 if num_training_steps is None else int(num_training_steps)
+        self.num_cycles = float(num_cycles)
+
+    @property
+    def code(self):
+        """The kind as include/eav_hip.h numbers it (EAV_SCHED_*)."""
+        return self.KINDS.index(self.kind)
+
+    def factor(self, t):
+        import math
+        t, W, T = int(t), self.num_warmup_steps, self.num_training_steps
+        if self.kind == "constant":
+            return 1.0
+        if t < W:
+            return float(t) / float(max(1, W))
+        if self.kind == "constant_with_warmup":
+            return 1.0
+        if self.kind == "linear":
+            return max(0.0, float(T - t) / float(max(1, T - W)))
+        progress = float(t - W) / float(max(1, T - W))
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * self.num_cycles * 2.0 * progress)))
+
+    def __repr__(self):
+        return (f"LRSchedule({self.kind!r}, num_warmup_steps={self.num_warmup_steps}, "
+                f"num_training_steps={self.num_training_steps}, num_cycles={self.num_cycles})")
+
+
+_CONSTANT = LRSchedule("constant")
+
+
+class _AdamJobTable:
+    """One cached table of eav_adam_step_jobs (rows: include/eav_hip.h) with the device step counts its rows read."""
+
+    def __init__(self, device, jobs, shared_step_ptr):
+        words = _lib.JOB_WORDS
+        n = len(jobs)
+        self.njobs = n
+        self.nchunks = sum(int(_lib.plain("eav_adam_jobs_nchunks", r[4])) for r in jobs)
+        self.per_tensor = shared_step_ptr is None
+        # the counts hold the steps COMPLETED: eav_adam_jobs_begin advances them before it reads them
+        self.counts = torch.tensor([r[5] - 1 for r in jobs], dtype=torch.int64).to(device) if self.per_tensor else None
+        self.steps = [r[5] - 1 for r in jobs]           # host mirror: the step each job ran last
+        rows = torch.zeros(n, words, dtype=torch.int64)
+        rows[:, :5] = torch.tensor([r[:5] for r in jobs], dtype=torch.int64)
+        rows[:, 5] = torch.tensor([r[6] for r in jobs], dtype=torch.float64).view(torch.int64)
+        if self.per_tensor:
+            rows[:, 6] = self.counts.data_ptr() + 8 * torch.arange(n, dtype=torch.int64)
+        else:
+            rows[:, 6] = shared_step_ptr
+        rows[:, 7] = torch.tensor([r[7] for r in jobs], dtype=torch.float32).view(torch.int32).to(torch.int64) & 0xffffffff
+        self.rows = rows.to(device)
+
+    def sync_counts(self, steps):
+        """`steps`: the step each job is about to run.  Re-seeds the device counts when they are not one behind (another
+        table advanced these tensors in between, or the state was loaded)."""
+        if self.per_tensor and [s - 1 for s in steps] != self.steps:
+            self.counts.copy_(torch.tensor([s - 1 for s in steps], dtype=torch.int64))
+        self.steps = list(steps)
+
+
 class FusedAdam(torch.optim.Optimizer):
     """Adam (``decoupled=False``) / AdamW (``decoupled=True``) with torch's
     hyper-parameter names; one ``eav_adam_step`` launch per contiguous run.
@@ -125,10 +211,32 @@ class FusedAdam(torch.optim.Optimizer):
 
     ``accumulate(weight)`` folds the current gradients into an accumulator (the models' backward OVERWRITES the flat
     gradient buffer, so torch's idiom of several backward() calls before one step() cannot work here); the next step()
-    consumes the accumulator instead of ``p.grad``."""
+    consumes the accumulator instead of ``p.grad``.
+
+    ``multi_tensor=True`` (keyword-only, like ``max_grad_norm`` now) updates every tensor in TWO launches whatever the
+    param groups look like (csrc/adam_jobs.hip): step() builds one job per parameter tensor that has a gradient -
+    adjacent tensors with equal ``lr``, ``weight_decay`` and step count merged as on the default path, ACROSS groups -
+    and issues ``eav_adam_jobs_begin`` (step counts, schedule factor, each job's lr and bias corrections, all on the
+    device) and ``eav_adam_step_jobs``.  Per-group ``lr`` and ``weight_decay`` are honoured; ``betas``, ``eps`` and
+    ``decoupled`` must be equal across the groups (EavError otherwise).  The per-tensor step counts live in a device
+    int64 array seeded from ``state[p]["step"]`` whenever a table is built - head and backbone keep their own counts
+    through the frozen / unfrozen phases - and the host mirror is still advanced, so ``state_dict()``
+    keeps torch's shape; with ``capturable=True`` every job reads the one device count.  The table is cached by what it
+    describes - pointers, sizes AND each job's ``lr`` and ``weight_decay``: changing ``group["lr"]`` or
+    ``group["weight_decay"]`` between steps is picked up because it is part of the cache key (a new table is built, the
+    old one stays cached for when the values return); a steady-state step allocates and copies nothing.
+    ``max_grad_norm`` and ``accumulate()`` work as on the default path, and the element update is the same function
+    (``adam_update``, csrc/eav_common.h): the same bits as ``eav_adam_step`` with a device step count gives.
+
+    ``set_schedule(LRSchedule(...))`` multiplies every group's ``lr`` by a factor evaluated ON THE DEVICE from a
+    device-resident count of the steps completed since the call; ``group["lr"]`` stays the base rate and nothing mutates
+    it per step, so a captured step() follows the schedule on every replay.  It needs - and turns on - ``multi_tensor``.
+    ``last_lr`` is the 0-dim device tensor holding group 0's rate in the last step, ``(float)(lr * factor)``, never read
+    back by the library.  Tables and the schedule record are created by the first step:
+    run one step eagerly before capturing, and capture again after ``set_schedule``."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
-                 capturable=False, max_grad_norm=None):
+                 capturable=False, *, multi_tensor=False, max_grad_norm=None):
         """capturable=True keeps ONE step count in device memory (incremented by a kernel), so that step()
         can be captured in a hipGraph and replayed; it requires every parameter to receive a gradient on
         every step (true for EEGNet; the two-phase AST/ViT fine-tune uses the default host-side counts)."""
@@ -136,6 +244,11 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._flat_state = {}
         self.capturable = capturable
+        self.multi_tensor = bool(multi_tensor)
+        self.schedule = None
+        self.last_lr = None
+        self._sched = None              # device schedule record (include/eav_hip.h)
+        self._adam_tables = {}          # _AdamJobTable by (device, jobs)
         self._dev_step = None
         # capturable: set by a caller that increments the device step count itself at the start of the step, in a launch
         # it issues anyway (GraphStep: eav_step_begin) - step() then skips its own eav_counter_inc for that one call
@@ -254,6 +367,120 @@ class FusedAdam(torch.optim.Optimizer):
             self._dev_step = torch.zeros((), dtype=torch.int64, device=dev)
         return self._dev_step
 
+    def set_schedule(self, schedule):
+        """Attach an LRSchedule (None: detach - the base rates apply again) and restart its step count at 0.  Turns
+        ``multi_tensor`` on; a captured step() must be captured again afterwards."""
+        if schedule is not None and not isinstance(schedule, LRSchedule):
+            raise TypeError(f"FusedAdam.set_schedule: expected an LRSchedule or None, got {type(schedule).__name__}")
+        self.schedule = schedule
+        if schedule is not None:
+            self.multi_tensor = True
+        if self._sched is not None:
+            self._sched[0].zero_()
+
+    def _step_jobs(self):
+        """step() of ``multi_tensor=True`` (class docstring): eav_adam_jobs_begin + eav_adam_step_jobs over one table."""
+        first = self.param_groups[0]
+        shared = (tuple(float(b) for b in first["betas"]), float(first["eps"]), bool(first["decoupled"]))
+        folded = set(self._acc_key) if self._acc_folds else None      # accumulate() was called: consume the accumulator
+        runs, touched = [], {}
+        for group in self.param_groups:
+            if (tuple(float(b) for b in group["betas"]), float(group["eps"]), bool(group["decoupled"])) != shared:
+                raise _lib.EavError("FusedAdam(multi_tensor=True): betas, eps and decoupled must be equal across the param "
+                                    "groups (lr and weight_decay may differ)")
+        for group in self.param_groups:
+            lr, wd = float(group["lr"]), float(group["weight_decay"])
+            for p in group["params"]:
+                if folded is not None:
+                    if id(p) not in folded:
+                        continue
+                    g = self.accumulated_grad(p)
+                elif p.grad is None:
+                    if self.capturable:
+                        raise _lib.EavError("FusedAdam(capturable=True): every parameter must have a gradient")
+                    continue
+                else:
+                    g = self._checked_grad(p)
+                st = self.state[p]
+                if getattr(p, "_eav_flat", None) is not None:
+                    touched[p._eav_flat[0].data_ptr()] = p._eav_flat[0]
+                if not st:
+                    self._init_state(p, st)
+                st["step"] += 1
+                # [p, g, m, v, numel, step, lr, wd, declared padding in bytes]
+                runs.append([p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                             p.numel(), 0 if self.capturable else st["step"], lr, wd, 4 * getattr(p, "_eav_pad", 0)])
+        if not runs:
+            self._acc_folds, self._acc_partials = 0, False
+            return
+        # merge what is adjacent in all four buffers (up to the 16-byte alignment padding plus declared zero padding,
+        # whose gradient and moments are zero) and shares lr, weight decay and step count - whichever group it is in
+        runs.sort(key=lambda r: r[0])
+        jobs = []
+        for r in runs:
+            if jobs:
+                q = jobs[-1]
+                gap = r[0] - (q[0] + 4 * q[4])
+                if (0 <= gap < 16 + q[8] and r[5:8] == q[5:8] and r[1] - q[1] == r[0] - q[0]
+                        and r[2] - q[2] == r[0] - q[0] and r[3] - q[3] == r[0] - q[0]):
+                    q[4] = (r[0] - q[0]) // 4 + r[4]
+                    q[8] = r[8]
+                    continue
+            jobs.append(r)
+        dev = next(iter(p for group in self.param_groups for p in group["params"])).device
+        if self._sched is None or self._sched.device != dev:
+            self._sched = torch.zeros(_lib.SCHED_WORDS, dtype=torch.int64, device=dev)
+            self.last_lr = self._sched.view(torch.float32)[4]
+        # the step counts change every step: they are seeded into the table's device counts, not part of its key
+        key = (dev, self.capturable, tuple((r[0], r[1], r[2], r[3], r[4], r[6], r[7]) for r in jobs))
+        table = self._adam_tables.get(key)
+        if table is None:
+            if len(self._adam_tables) >= 16:
+                self._adam_tables.clear()
+            table = self._adam_tables[key] = _AdamJobTable(dev, jobs, self._dev_step.data_ptr() if self.capturable else None)
+        table.sync_counts([r[5] for r in jobs])
+        gscale = None
+        if self.max_grad_norm is not None:
+            if folded is not None:      # the accumulator's own table: the partials of a last=True fold belong to it
+                gscale = self._clip(dev, self._acc_tables, self._acc_partials)
+            else:
+                gscale = self._clip(dev, self._tables.get(dev, tuple((r[1], r[1], r[4]) for r in jobs)), False)
+        self._acc_folds, self._acc_partials = 0, False
+        sch = self.schedule if self.schedule is not None else _CONSTANT
+        b1, b2 = shared[0]
+        st = _lib.stream_ptr()
+        _lib.call("eav_adam_jobs_begin", table.rows.data_ptr(), table.njobs, _lib.ptr(table.counts),
+                  table.njobs if table.per_tensor else 0, self._sched.data_ptr(), sch.code, sch.num_warmup_steps,
+                  sch.num_training_steps, sch.num_cycles, float(first["lr"]), b1, b2, st)
+        _lib.call("eav_adam_step_jobs", table.rows.data_ptr(), table.njobs, table.nchunks, b1, b2, shared[1],
+                  int(shared[2]), gscale, st)
+        # the byte ranges that just changed, for whoever caches derived copies of these parameters (step()'s comment)
+        for fl in touched.values():
+            if not getattr(fl, "_eav_track_dirty", False):
+                continue
+            lo = fl.data_ptr()
+            d = getattr(fl, "_eav_dirty", [])
+            d.extend((r[0], r[0] + 4 * r[4]) for r in jobs if lo <= r[0] < lo + 4 * fl.numel())
+            if len(d) > 64:
+                d = [(min(a for a, _ in d), max(b for _, b in d))]
+            fl._eav_dirty = d
+
+    def _init_state(self, p, st):
+        """Step count 0 and zero moments; the moments of a flat model's parameters are views of two flat buffers laid out
+        like the parameters, so that adjacent tensors stay adjacent in all four."""
+        st["step"] = 0
+        flat = getattr(p, "_eav_flat", None)
+        if flat is not None and flat[0].data_ptr() + 4 * flat[2] == p.data_ptr():
+            shared = self._flat_state.setdefault(flat[0].data_ptr(), {})
+            if not shared:
+                shared["m"] = torch.zeros_like(flat[0])
+                shared["v"] = torch.zeros_like(flat[0])
+            st["exp_avg"] = shared["m"][flat[2]:flat[2] + p.numel()].view(p.shape)
+            st["exp_avg_sq"] = shared["v"][flat[2]:flat[2] + p.numel()].view(p.shape)
+        else:
+            st["exp_avg"] = torch.zeros_like(p)
+            st["exp_avg_sq"] = torch.zeros_like(p)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
@@ -265,6 +492,9 @@ class FusedAdam(torch.optim.Optimizer):
                 self.step_counted = False
             else:
                 _lib.call("eav_counter_inc", self._dev_step.data_ptr(), _lib.stream_ptr())
+        if self.multi_tensor:
+            self._step_jobs()
+            return loss
         folded = set(self._acc_key) if self._acc_folds else None      # accumulate() was called: consume the accumulator
         plan = []
         for group in self.param_groups:
@@ -285,18 +515,7 @@ class FusedAdam(torch.optim.Optimizer):
                 if getattr(p, "_eav_flat", None) is not None:
                     touched[p._eav_flat[0].data_ptr()] = p._eav_flat[0]
                 if not st:
-                    st["step"] = 0
-                    flat = getattr(p, "_eav_flat", None)
-                    if flat is not None and flat[0].data_ptr() + 4 * flat[2] == p.data_ptr():
-                        shared = self._flat_state.setdefault(flat[0].data_ptr(), {})
-                        if not shared:
-                            shared["m"] = torch.zeros_like(flat[0])
-                            shared["v"] = torch.zeros_like(flat[0])
-                        st["exp_avg"] = shared["m"][flat[2]:flat[2] + p.numel()].view(p.shape)
-                        st["exp_avg_sq"] = shared["v"][flat[2]:flat[2] + p.numel()].view(p.shape)
-                    else:
-                        st["exp_avg"] = torch.zeros_like(p)
-                        st["exp_avg_sq"] = torch.zeros_like(p)
+                    self._init_state(p, st)
                 st["step"] += 1
                 runs.append([p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                              p.numel(), st["step"], g, 4 * getattr(p, "_eav_pad", 0)])

@@ -105,21 +105,22 @@ class ImageClassifierTrainer(FineTuneBase):
         return torch.stack(frames).to(self.device)
 
     def train(self, epochs=3, lr=None, freeze=True, log=False):
-        lr = self._enter_phase(lr, freeze)
+        lr = self._enter_phase(lr, freeze, epochs)
         print(f"Training with {'frozen' if freeze else 'unfrozen'} feature layers at lr={lr}")
         for epoch in range(epochs):
             self._train_one_epoch(after_batch=lambda k, nb: print(f'batch ({k}/{nb})'))
             rows = self._evaluate()
             self._keep_outputs(rows, epoch == epochs - 1, freeze)
+            lr_text = self._lr_text()
             if not self._classifies():
                 test_metric = self._metric_text(sum(r[1] for r in rows) / sum(r[2] for r in rows))
-                print(f"Epoch {epoch + 1}, Test {test_metric}")
+                print(f"Epoch {epoch + 1}, Test {test_metric}{lr_text}")
                 if log:
                     with open('training_performance.txt', 'a') as f:
                         f.write(f"{self.sub}, Epoch {epoch + 1}, Test {test_metric}\n")
                 continue
             avg_accuracy = sum(r[1] / r[2] for r in rows) / len(rows)          # mean of batch accuracies (Q14)
-            print(f"Epoch {epoch + 1}, Test Accuracy: {avg_accuracy * 100:.2f}%")
+            print(f"Epoch {epoch + 1}, Test Accuracy: {avg_accuracy * 100:.2f}%{lr_text}")
             if log:
                 with open('training_performance.txt', 'a') as f:
                     f.write(f"{self.sub}, Epoch {epoch + 1}, Test Accuracy: {avg_accuracy * 100:.2f}%\n")

@@ -349,6 +349,44 @@ int eav_grad_fold(const void* jobs_g, const void* jobs_acc, int njobs, int64_t n
 int eav_grad_clip_finish(const double* partials, int64_t nchunks, float max_norm, float* out2, void* stream);
 /* g *= *scalar in place over a job table; nothing is written when the scalar is exactly 1. */
 int eav_scale_ranges(const void* jobs, int njobs, int64_t nchunks, const float* scalar, void* stream);
+/* ---- Multi-tensor Adam / AdamW over a job table, learning-rate schedule on the device (csrc/adam_jobs.hip) ----
+ * One optimiser step = eav_adam_jobs_begin + eav_adam_step_jobs however many tensors, learning rates, weight decays and
+ * step counts there are; nothing is read back, every per-step scalar is device memory, so the pair can be captured.
+ * A job row is EAV_ADAM_JOB_WORDS int64 words (80 bytes):
+ *   0 p  1 g  2 m  3 v   fp32 ranges of `numel` elements, 4-byte aligned at least
+ *   4 numel              > 0
+ *   5 base_lr            the bits of a double
+ *   6 step               pointer to the device int64 step count the job reads (its own entry of `counts`, or a count the
+ *                        caller advances itself, e.g. the one a capturable optimiser shares with eav_adam_step)
+ *   7 weight_decay       fp32 bits in the low half, high half 0
+ *   8 lr | bc1 << 32     fp32 bits, written by eav_adam_jobs_begin
+ *   9 bc2s               fp32 bits in the low half, written by eav_adam_jobs_begin
+ * The schedule record is EAV_ADAM_SCHED_WORDS int64 words: 0 t = optimiser steps completed since the schedule was attached
+ * (the caller zeroes it), 1 the factor of the last step (double), 2 (float)(report_lr * factor) of the last step (fp32, low
+ * half: the rate a caller wants to show, e.g. its first group's), 3 unused.
+ * The jobs are cut into chunks like a table of eav_grad_sumsq: eav_adam_jobs_nchunks(numel) chunks per job (the same
+ * number as eav_grad_nchunks), nchunks = their sum. */
+#define EAV_ADAM_JOB_WORDS 10
+#define EAV_ADAM_SCHED_WORDS 4
+#define EAV_SCHED_CONSTANT 0
+#define EAV_SCHED_CONSTANT_WITH_WARMUP 1
+#define EAV_SCHED_LINEAR 2
+#define EAV_SCHED_COSINE 3
+int64_t eav_adam_jobs_nchunks(int64_t n);
+/* One workgroup.  counts[i] += 1 for i < ncounts (ncounts may be 0, counts then NULL); factor = the multiplier of
+ * transformers.get_scheduler's lambda for `kind` at t = sched[0], in fp64 (W = warmup_steps, T = training_steps):
+ *   t < W (every kind but constant): t / max(1, W);  constant, constant_with_warmup: 1;
+ *   linear: max(0, (T - t) / max(1, T - W));  cosine: max(0, 0.5 (1 + cos(pi * num_cycles * 2 * (t - W) / max(1, T - W))));
+ * then sched[0] += 1, and every row gets lr = (float)(base_lr * factor), bc1 = (float)(1 - beta1^step),
+ * bc2s = (float)sqrt(1 - beta2^step) with the powers in fp64 - the expressions of eav_adam_step's step_dev branch - from the
+ * step counts as they stand after the increments.  An unknown kind is refused before anything is launched. */
+int eav_adam_jobs_begin(void* jobs, int njobs, int64_t* counts, int ncounts, void* sched, int kind, int64_t warmup_steps,
+                        int64_t training_steps, double num_cycles, double report_lr, float beta1, float beta2, void* stream);
+/* The update of every job, element by element what eav_adam_step (gscale NULL) / eav_adam_step_scaled (the gradient is
+ * g * *gscale, rounded to fp32 first; g is not written) computes with the row's lr, weight_decay, bc1 and bc2s: the same
+ * bits, whichever way a range is cut into jobs.  No atomics; results do not depend on the grid. */
+int eav_adam_step_jobs(const void* jobs, int njobs, int64_t nchunks, float beta1, float beta2, float eps, int decoupled,
+                       const float* gscale, void* stream);
 /* Batch assembly in HBM: out[i,:] = src[idx[i],:] (rows of row_elems floats) / out[i] = src[idx[i]] (labels).
  * Replaces the per-batch host->device copies of the reference loops (EEGNet_tor.py:100-101). */
 int eav_gather_rows(const float* src, const int64_t* idx, float* out, int nrows, int64_t row_elems, void* stream);

@@ -83,6 +83,15 @@ def main():
                     "inside every optimiser step (trainer.max_grad_norm); default: no clipping, like the reference")
     ap.add_argument("--grad-accum", type=int, default=1, metavar="K", help="one optimiser step per K micro-batches "
                     "(trainer.gradient_accumulation_steps): effective batch K x the launch batch")
+    ap.add_argument("--lr-scheduler", default="constant", choices=("constant", "constant_with_warmup", "linear", "cosine"),
+                    help="learning-rate schedule of every train() call (trainer.lr_scheduler_type, the lambdas of "
+                    "transformers.get_scheduler); default: the reference's constant rate")
+    ap.add_argument("--warmup-ratio", type=float, default=0.0, metavar="R", help="share of a train() call's optimiser steps "
+                    "spent warming up from 0 (trainer.warmup_ratio)")
+    ap.add_argument("--layer-decay", type=float, default=1.0, metavar="D", help="layer-wise learning-rate decay in (0, 1]: the "
+                    "head at lr, layer i at lr * D ** (layers + 1 - i) (trainer.layer_decay)")
+    ap.add_argument("--no-decay-bias-norm", action="store_true", help="no weight decay on biases, LayerNorm weights, tokens "
+                    "and the position table, HF Trainer's rule (trainer.decay_bias_and_norm = False)")
     ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="E", help="cross-entropy label smoothing in [0, 1] "
                     "(trainer.label_smoothing, HF's label_smoothing_factor)")
     ap.add_argument("--class-weights", choices=("balanced",), default=None, help="weight the classes by n / (classes x "
@@ -102,6 +111,8 @@ def main():
         ap.error("--grad-accum takes K >= 1 and --max-grad-norm F > 0")
     if not 0.0 <= args.label_smoothing <= 1.0 or not args.mixup_alpha >= 0.0 or args.time_mask < 0 or args.freq_mask < 0:
         ap.error("--label-smoothing takes E in [0, 1], --mixup-alpha A >= 0, --time-mask / --freq-mask integers >= 0")
+    if not 0.0 <= args.warmup_ratio <= 1.0 or not 0.0 < args.layer_decay <= 1.0:
+        ap.error("--warmup-ratio takes R in [0, 1] and --layer-decay D in (0, 1]")
     audio = args.kind == "audio"
     if audio and args.hflip:
         ap.error("--hflip is a vision option")
@@ -152,6 +163,8 @@ def main():
                     tr = ImageClassifierTrainer(data, model_path=path, sub=f"subject_{sub:02d}", num_labels=5, lr=5e-5,
                                                 batch_size=bsz, image_size=args.image_size)
                 tr.max_grad_norm, tr.gradient_accumulation_steps = args.max_grad_norm, args.grad_accum
+                tr.lr_scheduler_type, tr.warmup_ratio = args.lr_scheduler, args.warmup_ratio
+                tr.layer_decay, tr.decay_bias_and_norm = args.layer_decay, not args.no_decay_bias_norm
                 tr.label_smoothing, tr.class_weights = args.label_smoothing, args.class_weights
                 tr.mixup_alpha, tr.augment_seed = args.mixup_alpha, args.augment_seed
                 if audio:
