@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .optim import CrossEntropyLoss, FusedAdam
+from .criteria import CrossEntropyLoss
+from .optim import FusedAdam
 from .runtime import DeviceLoader, KernelFn, KernelModule, train_step
 
 _PARAM_ORDER = ["features.0.weight", "features.0.bias", "features.2.weight", "features.2.bias", "features.6.weight",

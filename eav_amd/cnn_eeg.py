@@ -18,7 +18,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, eegnet_canon
-from .optim import CrossEntropyLoss, FusedAdam
+from .criteria import CrossEntropyLoss
+from .optim import FusedAdam
 from .runtime import DeviceLoader, KernelFn, KernelModule, train_step
 
 _PARAM_ORDER = [

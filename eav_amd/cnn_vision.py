@@ -22,7 +22,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .optim import CrossEntropyLoss, FusedAdam
+from .criteria import CrossEntropyLoss
+from .optim import FusedAdam
 from .runtime import (BN_M1, BN_M2, BN_SCALE, BN_SHIFT, DeviceLoader, KernelFn, KernelModule, bn_field,
                       eager_step)
 

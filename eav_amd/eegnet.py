@@ -25,8 +25,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .criteria import CrossEntropyLoss
 from .eegnet_paths import _PARAM_ORDER, FastPath, GenericPath, IndexedBatch
-from .optim import CrossEntropyLoss, FusedAdam
+from .optim import FusedAdam
 # re-exported: bench.py, tools/ and the tests import GraphStep, gather_batch and DeviceLoader from this module
 from .runtime import (DeviceLoader, GraphStep, KernelFn, KernelModule, cached_workspace, eager_step,  # noqa: F401
                       gather_batch, train_step)

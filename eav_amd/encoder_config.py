@@ -7,7 +7,7 @@ from types import SimpleNamespace
 
 import torch
 
-# Classes the classification head takes: up to HEAD_NARROW_CLASSES (16, optim.py) on eav_dense_softmax_* (the classes in
+# Classes the classification head takes: up to HEAD_NARROW_CLASSES (16, criteria.py) on eav_dense_softmax_* (the classes in
 # registers), beyond that on eav_dense_wide_* (csrc/head_wide.hip; EAV_HEAD_MAX_CLASSES of include/eav_hip.h) - AudioSet's
 # 527, ImageNet's 1000, ImageNet-21k's 21 843.
 HEAD_MAX_CLASSES = 32768

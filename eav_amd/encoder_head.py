@@ -10,7 +10,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .optim import head_is_wide
+from .criteria import head_is_wide
 
 
 class _HeadFn(torch.autograd.Function):

@@ -17,7 +17,8 @@ import torch
 
 from . import _lib
 from .augment import BatchAugment, EpochPlan
-from .optim import BCEWithLogitsLoss, CrossEntropyLoss, FusedAdam, LRSchedule, MSELoss
+from .criteria import BCEWithLogitsLoss, CrossEntropyLoss, MSELoss
+from .optim import FusedAdam, LRSchedule
 from .runtime import DeviceLoader
 from .transformer import PROBLEM_TYPES, Encoder
 

@@ -1,16 +1,12 @@
-"""Fused Adam / AdamW over flat parameter storage + the criteria (cross-entropy, BCE-with-logits, MSE).
+"""Fused Adam / AdamW over flat parameter storage.  The criteria (cross-entropy, BCE-with-logits, MSE) live in
+``eav_amd/criteria.py``; their public names are re-exported here, where they used to be.
 
 Host-side mirrors of what the reference trainers construct:
   * ``optim.Adam(model.parameters(), lr)``            CNN_torch/EEGNet_tor.py:82
   * ``optim.AdamW(model.parameters(), lr)``           Transformer_Audio.py:30, Transformer_Vision.py:36
     (weight_decay is torch's default 0.01 - the trainer's ctor argument is ignored)
-  * ``nn.CrossEntropyLoss()``                          EEGNet_tor.py:81, Transformer_Audio.py:31
 
-  * ``nn.BCEWithLogitsLoss()`` / ``nn.MSELoss()``      the other two losses HF's classification models pick by
-    ``config.problem_type`` (transformers/loss/loss_utils.py, ForSequenceClassificationLoss)
-
-The arithmetic runs in libeav_hip.so (``eav_adam_step`` / ``eav_ce_fwd_bwd`` / ``eav_bce_logits_fwd_bwd`` / ``eav_mse_fwd_bwd``;
-``eav_ce_general_fwd_bwd`` for ``CrossEntropyLoss(weight=..., label_smoothing=...)`` and class-probability targets).
+The arithmetic runs in libeav_hip.so (``eav_adam_step``).
 Parameters that live in one flat buffer (``flatten_parameters``) are updated
 with one launch per run of tensors that share a step count - the frozen and
 unfrozen fine-tuning phases give the head and the backbone different counts
@@ -27,11 +23,13 @@ device from a device-resident step count.  Off by default: the default step laun
 """
 from __future__ import annotations
 
-import os
+from operator import itemgetter
 
 import torch
 
 from . import _lib
+from .criteria import (BCEWithLogitsLoss, CrossEntropyLoss, HEAD_NARROW_CLASSES, MSELoss,  # noqa: F401 - the old import path
+                       head_is_wide, unit_gradient)
 
 
 def flatten_parameters(module: torch.nn.Module, order=None, pad_after=None):
@@ -71,20 +69,31 @@ def flatten_parameters(module: torch.nn.Module, order=None, pad_after=None):
     return flat, gflat, offsets
 
 
-def _merge_ranges(ranges):
-    """ranges: lists [ptr, other_ptr, numel, slack_bytes] - merged, in address order, where the next range begins less than
-    `slack_bytes` after the end of the previous one at BOTH pointers (flat buffers: the 16-byte alignment padding plus
-    declared zero padding, whose gradient is zero; loose tensors: slack 1, i.e. exactly adjacent)."""
+# A row: a run of fp32 elements that lies at the same place in several buffers, as a list of plain integers
+#   [ptr, rel, numel, slack, key]
+# ptr: its address in the first buffer; rel: tuple of the byte distances from there to the same run in the other buffers
+# ((acc - g,), (0,) or (g - p, m - p, v - p)); slack: bytes - the next row may begin less than this after the end of this
+# one and still join it; key: what joined rows must share (step count, lr, weight decay; None: nothing).
+_PTR, _REL, _NUMEL, _SLACK, _KEY = range(5)
+
+
+def _merge_rows(rows):
+    """The one rule for "merge what is adjacent".  `rows` are taken in address order of `ptr` (a stable sort); a row joins
+    its predecessor where it begins less than the predecessor's `slack` bytes after its end (never before it), lies at
+    the same distances in the other buffers (equal `rel`) and the keys are equal.  The slack covers what lies between two
+    tensors and holds zeros in every buffer - flat buffers: the 16-byte alignment padding plus declared zero padding
+    (`_flat_slack`); loose tensors: slack 1, i.e. exactly adjacent.  The joined row spans both and takes the slack of the
+    row that joined.  Rows are lists and are joined in place - this runs once per tensor in every optimiser step."""
     merged = []
-    for r in sorted(ranges, key=lambda r: r[0]):
+    for r in sorted(rows, key=itemgetter(_PTR)):
         if merged:
             q = merged[-1]
-            gap = r[0] - (q[0] + 4 * q[2])
-            if 0 <= gap < q[3] and r[1] - q[1] == r[0] - q[0]:
-                q[2] = (r[0] - q[0]) // 4 + r[2]
-                q[3] = r[3]
+            gap = r[_PTR] - (q[_PTR] + 4 * q[_NUMEL])
+            if 0 <= gap < q[_SLACK] and r[_KEY] == q[_KEY] and r[_REL] == q[_REL]:
+                q[_NUMEL] = (r[_PTR] - q[_PTR]) // 4 + r[_NUMEL]
+                q[_SLACK] = r[_SLACK]
                 continue
-        merged.append(list(r))
+        merged.append(r)
     return merged
 
 
@@ -169,22 +178,24 @@ class _AdamJobTable:
     """One cached table of eav_adam_step_jobs (rows: include/eav_hip.h) with the device step counts its rows read."""
 
     def __init__(self, device, jobs, shared_step_ptr):
+        """jobs: rows over (p, g, m, v) with key (step, lr, weight decay)."""
         words = _lib.JOB_WORDS
         n = len(jobs)
         self.njobs = n
-        self.nchunks = sum(int(_lib.plain("eav_adam_jobs_nchunks", r[4])) for r in jobs)
+        self.nchunks = sum(int(_lib.plain("eav_adam_jobs_nchunks", r[_NUMEL])) for r in jobs)
         self.per_tensor = shared_step_ptr is None
         # the counts hold the steps COMPLETED: eav_adam_jobs_begin advances them before it reads them
-        self.counts = torch.tensor([r[5] - 1 for r in jobs], dtype=torch.int64).to(device) if self.per_tensor else None
-        self.steps = [r[5] - 1 for r in jobs]           # host mirror: the step each job ran last
+        self.steps = [step - 1 for _, _, _, _, (step, _, _) in jobs]       # host mirror: the step each job ran last
+        self.counts = torch.tensor(self.steps, dtype=torch.int64).to(device) if self.per_tensor else None
         rows = torch.zeros(n, words, dtype=torch.int64)
-        rows[:, :5] = torch.tensor([r[:5] for r in jobs], dtype=torch.int64)
-        rows[:, 5] = torch.tensor([r[6] for r in jobs], dtype=torch.float64).view(torch.int64)
+        rows[:, :5] = torch.tensor([[p, p + g, p + m, p + v, numel] for p, (g, m, v), numel, _, _ in jobs], dtype=torch.int64)
+        rows[:, 5] = torch.tensor([lr for _, _, _, _, (_, lr, _) in jobs], dtype=torch.float64).view(torch.int64)
         if self.per_tensor:
             rows[:, 6] = self.counts.data_ptr() + 8 * torch.arange(n, dtype=torch.int64)
         else:
             rows[:, 6] = shared_step_ptr
-        rows[:, 7] = torch.tensor([r[7] for r in jobs], dtype=torch.float32).view(torch.int32).to(torch.int64) & 0xffffffff
+        rows[:, 7] = (torch.tensor([wd for _, _, _, _, (_, _, wd) in jobs], dtype=torch.float32).view(torch.int32)
+                      .to(torch.int64) & 0xffffffff)
         self.rows = rows.to(device)
 
     def sync_counts(self, steps):
@@ -335,9 +346,10 @@ class FusedAdam(torch.optim.Optimizer):
                     self._acc_flat[fl[1].data_ptr()] = torch.zeros_like(fl[1])
             elif p not in self._acc_loose:
                 self._acc_loose[p] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            ranges.append([g.data_ptr(), self.accumulated_grad(p).data_ptr(), p.numel(), _flat_slack(p)])
+            at = g.data_ptr()
+            ranges.append([at, (self.accumulated_grad(p).data_ptr() - at,), p.numel(), _flat_slack(p), None])
         dev = ps[0].device
-        tables = self._tables.get(dev, tuple((r[0], r[1], r[2]) for r in _merge_ranges(ranges)))
+        tables = self._tables.get(dev, tuple((at, at + acc, numel) for at, (acc,), numel, _, _ in _merge_rows(ranges)))
         jobs_g, jobs_a, njobs, nchunks, partials = tables
         want = bool(last) and self.max_grad_norm is not None
         _lib.call("eav_grad_fold", jobs_g.data_ptr(), jobs_a.data_ptr(), njobs, nchunks,
@@ -378,18 +390,18 @@ class FusedAdam(torch.optim.Optimizer):
         if self._sched is not None:
             self._sched[0].zero_()
 
-    def _step_jobs(self):
-        """step() of ``multi_tensor=True`` (class docstring): eav_adam_jobs_begin + eav_adam_step_jobs over one table."""
-        first = self.param_groups[0]
-        shared = (tuple(float(b) for b in first["betas"]), float(first["eps"]), bool(first["decoupled"]))
+    # ---- what the two step paths share ----------------------------------------------------------------------------
+    def _gather(self):
+        """The walk over the parameters that both paths begin with.  Each tensor is updated from its view of the
+        accumulator when accumulate() was called since the last step, else from ``p.grad`` as _checked_grad passes it;
+        a tensor without a gradient is skipped like torch does (a capturable optimiser refuses it).  State is created on
+        first sight and the host step count advanced.  Returns ([(group, rows)] with one row (_merge_rows) over
+        (p, g, m, v) per tensor, keyed by its host step count; the flat parameter buffers these tensors live in, by
+        address; the device of the gradients - None when there is nothing to update)."""
         folded = set(self._acc_key) if self._acc_folds else None      # accumulate() was called: consume the accumulator
-        runs, touched = [], {}
+        plan, touched, dev, flat = [], {}, None, None
         for group in self.param_groups:
-            if (tuple(float(b) for b in group["betas"]), float(group["eps"]), bool(group["decoupled"])) != shared:
-                raise _lib.EavError("FusedAdam(multi_tensor=True): betas, eps and decoupled must be equal across the param "
-                                    "groups (lr and weight_decay may differ)")
-        for group in self.param_groups:
-            lr, wd = float(group["lr"]), float(group["weight_decay"])
+            rows = []
             for p in group["params"]:
                 if folded is not None:
                     if id(p) not in folded:
@@ -402,50 +414,93 @@ class FusedAdam(torch.optim.Optimizer):
                 else:
                     g = self._checked_grad(p)
                 st = self.state[p]
-                if getattr(p, "_eav_flat", None) is not None:
-                    touched[p._eav_flat[0].data_ptr()] = p._eav_flat[0]
+                fl = getattr(p, "_eav_flat", None)
+                if fl is not None and fl[0] is not flat:        # (neighbours share their buffer: one entry, one look)
+                    flat = fl[0]
+                    touched[flat.data_ptr()] = flat
                 if not st:
                     self._init_state(p, st)
                 st["step"] += 1
-                # [p, g, m, v, numel, step, lr, wd, declared padding in bytes]
-                runs.append([p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                             p.numel(), 0 if self.capturable else st["step"], lr, wd, 4 * getattr(p, "_eav_pad", 0)])
-        if not runs:
-            self._acc_folds, self._acc_partials = 0, False
+                if dev is None:
+                    dev = g.device
+                # adjacent in all four buffers up to the 16-byte alignment padding plus declared zero padding, whose
+                # gradient and moments are zero, so the update leaves it zero
+                at = p.data_ptr()
+                rows.append([at, (g.data_ptr() - at, st["exp_avg"].data_ptr() - at, st["exp_avg_sq"].data_ptr() - at),
+                             p.numel(), 16 + 4 * getattr(p, "_eav_pad", 0), st["step"]])
+            plan.append((group, rows))
+        return plan, touched, dev
+
+    def _acc_reset(self):
+        """The accumulator is consumed (or there was nothing to consume): the next accumulate() starts a new group."""
+        self._acc_folds, self._acc_partials = 0, False
+
+    def _grad_scale(self, dev, runs):
+        """The clipping coefficient's device pointer for a step over `runs` (None: no clipping), from the accumulator's own
+        table when the step consumes it - the partials of a last=True fold belong to that table - else from a table over
+        the gradient ranges of `runs`, in their order.  Empties the accumulator either way."""
+        gscale = None
+        if self.max_grad_norm is not None and runs:
+            if self._acc_folds:
+                gscale = self._clip(dev, self._acc_tables, self._acc_partials)
+            else:
+                ranges = tuple((at + g, at + g, numel) for at, (g, _, _), numel, _, _ in runs)
+                gscale = self._clip(dev, self._tables.get(dev, ranges), False)
+        self._acc_reset()
+        return gscale
+
+    @staticmethod
+    def _record_dirty(touched, runs):
+        """Tell whoever caches derived copies of these parameters (transformer.Encoder's fp16 operand planes) which byte
+        ranges of the flat buffers just changed.  Only flat buffers whose owner registered interest - `_eav_track_dirty` -
+        are tracked, and a list collapses to its hull once it passes 64 entries: an eager loop that nobody drains must
+        not grow it."""
+        tracked = [(fl, fl.data_ptr(), fl.data_ptr() + 4 * fl.numel()) for fl in touched.values()
+                   if getattr(fl, "_eav_track_dirty", False)]
+        for at, _, numel, _, _ in runs if tracked else ():
+            for fl, lo, hi in tracked:
+                if lo <= at < hi:
+                    d = getattr(fl, "_eav_dirty", [])
+                    d.append((at, at + 4 * numel))
+                    if len(d) > 64:
+                        d = [(min(a for a, _ in d), max(b for _, b in d))]
+                    fl._eav_dirty = d
+
+    def _step_jobs(self):
+        """step() of ``multi_tensor=True`` (class docstring): eav_adam_jobs_begin + eav_adam_step_jobs over one table."""
+        # checked across the groups BEFORE any state is touched: a refused step leaves the step counts where they were
+        first = self.param_groups[0]
+        shared = (tuple(float(b) for b in first["betas"]), float(first["eps"]), bool(first["decoupled"]))
+        for group in self.param_groups:
+            if (tuple(float(b) for b in group["betas"]), float(group["eps"]), bool(group["decoupled"])) != shared:
+                raise _lib.EavError("FusedAdam(multi_tensor=True): betas, eps and decoupled must be equal across the param "
+                                    "groups (lr and weight_decay may differ)")
+        plan, touched, dev = self._gather()
+        # a job's tensors share lr, weight decay and step count, whichever group they are in - the count being 0 for a
+        # capturable optimiser, whose jobs all read the one device count (the default path keys on the host count then
+        # too) - and are merged ACROSS the groups, in one address order: a job is a table row, their order costs no launch
+        capturable, runs = self.capturable, []
+        for group, rows in plan:
+            lr, wd = float(group["lr"]), float(group["weight_decay"])
+            for r in rows:
+                r[_KEY] = (0 if capturable else r[_KEY], lr, wd)
+            runs += rows
+        jobs = _merge_rows(runs)
+        if not jobs:        # no gradient anywhere: nothing is launched, the accumulator flags are emptied all the same
+            self._acc_reset()
             return
-        # merge what is adjacent in all four buffers (up to the 16-byte alignment padding plus declared zero padding,
-        # whose gradient and moments are zero) and shares lr, weight decay and step count - whichever group it is in
-        runs.sort(key=lambda r: r[0])
-        jobs = []
-        for r in runs:
-            if jobs:
-                q = jobs[-1]
-                gap = r[0] - (q[0] + 4 * q[4])
-                if (0 <= gap < 16 + q[8] and r[5:8] == q[5:8] and r[1] - q[1] == r[0] - q[0]
-                        and r[2] - q[2] == r[0] - q[0] and r[3] - q[3] == r[0] - q[0]):
-                    q[4] = (r[0] - q[0]) // 4 + r[4]
-                    q[8] = r[8]
-                    continue
-            jobs.append(r)
-        dev = next(iter(p for group in self.param_groups for p in group["params"])).device
         if self._sched is None or self._sched.device != dev:
             self._sched = torch.zeros(_lib.SCHED_WORDS, dtype=torch.int64, device=dev)
             self.last_lr = self._sched.view(torch.float32)[4]
         # the step counts change every step: they are seeded into the table's device counts, not part of its key
-        key = (dev, self.capturable, tuple((r[0], r[1], r[2], r[3], r[4], r[6], r[7]) for r in jobs))
+        key = (dev, capturable, tuple((at, rel, numel, lr, wd) for at, rel, numel, _, (_, lr, wd) in jobs))
         table = self._adam_tables.get(key)
         if table is None:
             if len(self._adam_tables) >= 16:
                 self._adam_tables.clear()
-            table = self._adam_tables[key] = _AdamJobTable(dev, jobs, self._dev_step.data_ptr() if self.capturable else None)
-        table.sync_counts([r[5] for r in jobs])
-        gscale = None
-        if self.max_grad_norm is not None:
-            if folded is not None:      # the accumulator's own table: the partials of a last=True fold belong to it
-                gscale = self._clip(dev, self._acc_tables, self._acc_partials)
-            else:
-                gscale = self._clip(dev, self._tables.get(dev, tuple((r[1], r[1], r[4]) for r in jobs)), False)
-        self._acc_folds, self._acc_partials = 0, False
+            table = self._adam_tables[key] = _AdamJobTable(dev, jobs, self._dev_step.data_ptr() if capturable else None)
+        table.sync_counts([r[_KEY][0] for r in jobs])
+        gscale = self._grad_scale(dev, jobs)
         sch = self.schedule if self.schedule is not None else _CONSTANT
         b1, b2 = shared[0]
         st = _lib.stream_ptr()
@@ -454,16 +509,7 @@ class FusedAdam(torch.optim.Optimizer):
                   sch.num_training_steps, sch.num_cycles, float(first["lr"]), b1, b2, st)
         _lib.call("eav_adam_step_jobs", table.rows.data_ptr(), table.njobs, table.nchunks, b1, b2, shared[1],
                   int(shared[2]), gscale, st)
-        # the byte ranges that just changed, for whoever caches derived copies of these parameters (step()'s comment)
-        for fl in touched.values():
-            if not getattr(fl, "_eav_track_dirty", False):
-                continue
-            lo = fl.data_ptr()
-            d = getattr(fl, "_eav_dirty", [])
-            d.extend((r[0], r[0] + 4 * r[4]) for r in jobs if lo <= r[0] < lo + 4 * fl.numel())
-            if len(d) > 64:
-                d = [(min(a for a, _ in d), max(b for _, b in d))]
-            fl._eav_dirty = d
+        self._record_dirty(touched, jobs)
 
     def _init_state(self, p, st):
         """Step count 0 and zero moments; the moments of a flat model's parameters are views of two flat buffers laid out
@@ -485,79 +531,26 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         if self.capturable:
-            if self._dev_step is None:
-                dev = next(p for g in self.param_groups for p in g["params"]).device
-                self._dev_step = torch.zeros((), dtype=torch.int64, device=dev)
+            count = self.device_step_counter()
             if self.step_counted:
                 self.step_counted = False
             else:
-                _lib.call("eav_counter_inc", self._dev_step.data_ptr(), _lib.stream_ptr())
+                _lib.call("eav_counter_inc", count.data_ptr(), _lib.stream_ptr())
         if self.multi_tensor:
             self._step_jobs()
             return loss
-        folded = set(self._acc_key) if self._acc_folds else None      # accumulate() was called: consume the accumulator
-        plan = []
-        for group in self.param_groups:
-            runs = []  # (p_ptr, g_ptr, m_ptr, v_ptr, numel, step) candidates for merging
-            touched = {}
-            for p in group["params"]:
-                if folded is not None:
-                    if id(p) not in folded:
-                        continue
-                    g = self.accumulated_grad(p)
-                elif p.grad is None:
-                    if self.capturable:
-                        raise _lib.EavError("FusedAdam(capturable=True): every parameter must have a gradient")
-                    continue
-                else:
-                    g = self._checked_grad(p)
-                st = self.state[p]
-                if getattr(p, "_eav_flat", None) is not None:
-                    touched[p._eav_flat[0].data_ptr()] = p._eav_flat[0]
-                if not st:
-                    self._init_state(p, st)
-                st["step"] += 1
-                runs.append([p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                             p.numel(), st["step"], g, 4 * getattr(p, "_eav_pad", 0)])
-            # merge runs that are adjacent (up to 16-B alignment padding, plus declared zero padding - whose
-            # gradient and moments are zero, so the update leaves it zero) in all four buffers
-            runs.sort(key=lambda r: r[0])
-            merged = []
-            for r in runs:
-                if merged:
-                    q = merged[-1]
-                    gap = r[0] - (q[0] + 4 * q[4])
-                    if (0 <= gap < 16 + q[7] and r[5] == q[5] and r[1] - q[1] == r[0] - q[0]
-                            and r[2] - q[2] == r[0] - q[0] and r[3] - q[3] == r[0] - q[0]):
-                        q[4] = (r[0] - q[0]) // 4 + r[4]
-                        q[7] = r[7]
-                        continue
-                merged.append(r)
-            plan.append((group, merged, touched))
-        gscale = None
-        if self.max_grad_norm is not None and any(merged for _, merged, _ in plan):
-            dev = next(r[6].device for _, merged, _ in plan for r in merged)
-            if folded is not None:      # the accumulator's own table: the partials of a last=True fold belong to it
-                gscale = self._clip(dev, self._acc_tables, self._acc_partials)
-            else:
-                ranges = tuple((r[1], r[1], r[4]) for _, merged, _ in plan for r in merged)
-                gscale = self._clip(dev, self._tables.get(dev, ranges), False)
-        self._acc_folds, self._acc_partials = 0, False
-        for group, merged, touched in plan:
-            for r in merged:
-                self._launch(r[0], r[1], r[2], r[3], r[4], group, r[5], gscale)
-                # tell whoever caches derived copies of these parameters (transformer.Encoder's fp16 operand
-                # planes) which byte ranges of the flat buffer just changed
-                # (only flat buffers whose owner registered interest - `_eav_track_dirty` - are tracked, and the list
-                # collapses to its hull beyond a few entries: an eager loop that nobody drains must not grow it)
-                for fl in touched.values():
-                    lo = fl.data_ptr()
-                    if getattr(fl, "_eav_track_dirty", False) and lo <= r[0] < lo + 4 * fl.numel():
-                        d = getattr(fl, "_eav_dirty", [])
-                        d.append((r[0], r[0] + 4 * r[4]))
-                        if len(d) > 64:
-                            d = [(min(a for a, _ in d), max(b for _, b in d))]
-                        fl._eav_dirty = d
+        # one launch per run of adjacent tensors that share a step count - the HOST count, also when capturable (all equal
+        # then).  Merged WITHIN a group only and launched group by group, by address inside a group: the hyper-parameters
+        # are launch arguments.  The grad-norm ranges follow the same order, which is the order the fp64 partials are
+        # added in and so decides the bits of the norm.
+        plan, touched, dev = self._gather()
+        plan = [(group, _merge_rows(rows)) for group, rows in plan]
+        runs = [r for _, rows in plan for r in rows]
+        gscale = self._grad_scale(dev, runs)        # (no gradient anywhere: runs is empty and nothing is launched)
+        for group, rows in plan:
+            for at, (g, m, v), numel, _, step in rows:
+                self._launch(at, at + g, at + m, at + v, numel, group, step, gscale)
+        self._record_dirty(touched, runs)
         return loss
 
 
@@ -586,331 +579,12 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
         if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous() or g.device != ps[0].grad.device:
             raise _lib.EavError("clip_grad_norm_ needs contiguous fp32 gradients on one ROCm device (no CPU fallback)")
         if g.numel():
-            ranges.append([g.data_ptr(), g.data_ptr(), g.numel(), _flat_slack(p)])
+            ranges.append([g.data_ptr(), (0,), g.numel(), _flat_slack(p), None])
     dev = ps[0].grad.device
-    _, jobs, njobs, nchunks, partials = _CLIP_TABLES.get(dev, tuple((r[0], r[1], r[2]) for r in _merge_ranges(ranges)))
+    _, jobs, njobs, nchunks, partials = _CLIP_TABLES.get(dev, tuple((at, at, numel) for at, _, numel, _, _ in _merge_rows(ranges)))
     out = torch.empty(2, dtype=torch.float32, device=dev)
     st = _lib.stream_ptr()
     _lib.call("eav_grad_sumsq", jobs.data_ptr(), njobs, nchunks, partials.data_ptr(), st)
     _lib.call("eav_grad_clip_finish", partials.data_ptr(), nchunks, float(max_norm), out.data_ptr(), st)
     _lib.call("eav_scale_ranges", jobs.data_ptr(), njobs, nchunks, out.data_ptr() + 4, st)
     return out[0]
-
-
-class _CEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores, targets, flag, scratch=None, general=None):
-        B, NC = scores.shape
-        loss = torch.empty((), dtype=torch.float32, device=scores.device)
-        need_grad = ctx.needs_input_grad[0]
-        dsc = torch.empty_like(scores) if need_grad else None      # no gradient buffer under no_grad (validate())
-        _ce_launch(scratch, scores, targets, loss, dsc, None, flag, general)
-        ctx.dsc = dsc
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        return _seeded(ctx.dsc, gout), None, None, None, None
-
-
-def _seeded(dsc, gout):
-    """The gradient a criterion's backward returns.  d loss / d scores (`dsc`) was produced by the forward launch; the
-    incoming gradient (1.0 for loss.backward()) is applied by the library - no torch kernel inside a captured step.
-    `unit_gradient(device)` is a constant 1.0 that callers may pass as the seed (loss.backward(gradient=...)): recognised
-    here, nothing is launched."""
-    if gout.data_ptr() != _UNIT.get(gout.device, (None, 0))[1]:
-        # any other upstream gradient scales a COPY: dsc stays the unit-gradient result, so a second backward
-        # (retain_graph=True) or a re-used graph never scales twice
-        out = dsc.clone()
-        _lib.call("eav_scale_by_scalar", out.data_ptr(), gout.contiguous().data_ptr(), out.numel(), _lib.stream_ptr())
-        return out
-    return dsc
-
-
-# classes the narrow head kernels are meant for (eav_dense_softmax_* keeps them in registers, eav_ce_fwd_bwd walks a row
-# with one thread); Encoder.head_algo and CrossEntropyLoss.head_algo switch to the wide kernels above it
-HEAD_NARROW_CLASSES = 16
-
-
-def head_is_wide(algo, classes, found):
-    """Whether `classes` classes go to the wide kernels under head_algo `algo`; `found` ("the head has") words the refusal."""
-    if algo not in ("auto", "wide", "narrow"):
-        raise ValueError(f"head_algo {algo!r}: expected 'auto', 'wide' or 'narrow'")
-    if algo == "narrow" and classes > HEAD_NARROW_CLASSES:
-        raise NotImplementedError(f"head_algo 'narrow' takes at most {HEAD_NARROW_CLASSES} classes, {found} {classes}")
-    return algo == "wide" or (algo == "auto" and classes > HEAD_NARROW_CLASSES)
-
-
-def _ce_launch(scratch, scores, targets, loss, dsc, ncorrect, flag, general=None):
-    """eav_ce_fwd_bwd (scratch None), or eav_ce_wide_fwd_bwd (one wave per row) with its per-row scratch; with `general` =
-    (class weights or None, label smoothing), eav_ce_general_fwd_bwd on int64 labels or fp32 class probabilities."""
-    B, NC = scores.shape
-    if general is not None:
-        weight, smoothing = general
-        soft = targets.dtype == torch.float32
-        _lib.call("eav_ce_general_fwd_bwd", scores.data_ptr(), None if soft else targets.data_ptr(),
-                  targets.data_ptr() if soft else None, _lib.ptr(weight), float(smoothing), loss.data_ptr(), _lib.ptr(dsc),
-                  _lib.ptr(ncorrect), flag.data_ptr(), scratch.data_ptr(), B, NC, _lib.stream_ptr())
-    elif scratch is not None:
-        _lib.call("eav_ce_wide_fwd_bwd", scores.data_ptr(), targets.data_ptr(), loss.data_ptr(), _lib.ptr(dsc),
-                  _lib.ptr(ncorrect), flag.data_ptr(), scratch.data_ptr(), B, NC, _lib.stream_ptr())
-    else:
-        _lib.call("eav_ce_fwd_bwd", scores.data_ptr(), targets.data_ptr(), loss.data_ptr(), _lib.ptr(dsc),
-                  _lib.ptr(ncorrect), flag.data_ptr(), B, NC, _lib.stream_ptr())
-
-
-_UNIT = {}
-
-
-def unit_gradient(device):
-    """A device-resident constant 1.0 to seed ``loss.backward(gradient=unit_gradient(dev))`` with: autograd then needs no
-    fill kernel for the implicit ones_like(loss), and the CE backward recognises it and skips its scaling launch."""
-    device = torch.device(device)
-    if device not in _UNIT:
-        t = torch.ones((), dtype=torch.float32, device=device)
-        _UNIT[device] = (t, t.data_ptr())
-    return _UNIT[device][0]
-
-
-class CrossEntropyLoss:
-    """``nn.CrossEntropyLoss()`` (mean reduction) as one fused HIP kernel that
-    produces the loss and its input gradient together.
-
-    Like torch, targets equal to -100 (the default ignore_index) are excluded from the mean and get a zero gradient, and
-    any other class index outside [0, classes) is rejected: the kernel never indexes with such a label (the row
-    contributes nothing to the loss and receives a zero gradient) and records it in a device flag; ``check()`` reads the flag (one host synchronisation) and
-    raises.  The trainers call it once per epoch - a per-step check would serialise host and GPU; code that drives the
-    criterion directly calls ``check()`` whenever it synchronises anyway.
-
-    ``head_algo`` routes by the class count like ``Encoder.head_algo``: "auto" (default; EAV_HEAD_ALGO overrides) takes
-    eav_ce_wide_fwd_bwd above 16 classes and eav_ce_fwd_bwd up to there, "wide" forces the former at any width and
-    "narrow" the latter, which raises above 16 classes as the Encoder's does.  The wide kernel's per-row scratch is kept
-    on the criterion, one buffer per (batch, device): nothing is allocated for it in the launch path.
-
-    ``weight`` (per-class weights, anything torch.as_tensor takes) and ``label_smoothing`` (0 <= eps <= 1) are torch's
-    arguments of those names, keyword-only and fixed at construction - read-only attributes: a captured step has the
-    scalar baked in, a later change could silently not apply.  Targets may also be fp32 class probabilities
-    [batch, classes] (mixup's soft targets).  The defaults on class indices launch what they always did; anything else
-    goes to eav_ce_general_fwd_bwd (csrc/head_ce_soft.hip) at every width - ``head_algo`` does not apply there - with
-    its own per-(batch, device) scratch.  The weights are kept as an fp32 tensor and moved to the device of the first
-    scores; a length other than the class count raises.  With class indices the mean is over the weights of the valid
-    labels (torch's rule); labels whose weights add up to 0 give a NaN loss like an all-ignored batch."""
-
-    def __init__(self, *, weight=None, label_smoothing=0.0):
-        smoothing = float(label_smoothing)
-        if not 0.0 <= smoothing <= 1.0:
-            raise ValueError(f"CrossEntropyLoss: label_smoothing {label_smoothing!r} is outside [0, 1]")
-        if weight is not None:
-            weight = torch.as_tensor(weight).detach().to(torch.float32).reshape(-1).contiguous().clone()
-            if weight.numel() < 1:
-                raise ValueError("CrossEntropyLoss: weight is empty")
-        self._weight, self._smoothing = weight, smoothing
-        self._flag = None
-        self._scratch = {}
-        self._general_scratch = {}
-        self.head_algo = os.environ.get("EAV_HEAD_ALGO", "auto")
-
-    weight = property(lambda self: self._weight, doc="per-class weights (fp32 tensor) or None; fixed at construction")
-    label_smoothing = property(lambda self: self._smoothing, doc="the smoothing factor; fixed at construction")
-
-    def _wide(self, classes):
-        return head_is_wide(self.head_algo, classes, "the scores have")
-
-    def _scratch_for(self, scores):
-        """The wide kernel's row terms for this batch size (None: the narrow kernel runs)."""
-        B, NC = scores.shape
-        if not self._wide(NC):
-            return None
-        key = (B, scores.device)
-        if key not in self._scratch:
-            self._scratch[key] = torch.empty(_lib.plain("eav_ce_wide_ws_floats", B), dtype=torch.float32, device=scores.device)
-        return self._scratch[key]
-
-    def _route(self, scores, targets):
-        """(scratch, general) of _ce_launch: the default criterion on class indices keeps its two kernels, everything else
-        takes the general one with the weights on the scores' device."""
-        if targets.dim() == 1 and self._weight is None and self._smoothing == 0.0:
-            return self._scratch_for(scores), None
-        B, NC = scores.shape
-        if self._weight is not None:
-            if self._weight.numel() != NC:
-                raise ValueError(f"CrossEntropyLoss: {self._weight.numel()} class weights for {NC} classes")
-            if self._weight.device != scores.device:
-                self._weight = self._weight.to(scores.device)
-        key = (B, scores.device)
-        if key not in self._general_scratch:
-            self._general_scratch[key] = torch.empty(_lib.plain("eav_ce_general_ws_floats", B), dtype=torch.float32,
-                                                     device=scores.device)
-        return self._general_scratch[key], (self._weight, self._smoothing)
-
-    @staticmethod
-    def _targets(scores, targets, who):
-        """int64 [B] class indices or fp32 [B, NC] class probabilities, contiguous."""
-        if targets.dim() == 2:
-            if tuple(targets.shape) != tuple(scores.shape):
-                raise _lib.EavError(f"{who}: class-probability targets {tuple(targets.shape)} for scores {tuple(scores.shape)}")
-            if targets.dtype != torch.float32:
-                targets = targets.float()
-            return targets.contiguous()
-        if targets.dim() != 1 or targets.numel() != scores.shape[0]:
-            raise _lib.EavError(f"{who}: {targets.numel()} targets for {scores.shape[0]} rows of scores")
-        if targets.dtype != torch.int64:
-            targets = targets.long()
-        return targets.contiguous()
-
-    def check(self):
-        if self._flag is not None:
-            bad = int(self._flag.item())
-            if bad != 0:
-                self._flag.zero_()
-                raise _lib.EavError(f"CrossEntropyLoss: target {bad - 1 if bad > 0 else bad} is outside [0, classes) "
-                                    "(the reference's labels 1,3,5,7,9 must be mapped to 0..4 first)")
-
-    def accumulate(self, scores, targets, loss_out, ncorrect):
-        """Evaluation form (no gradient, nothing read back): writes the mean loss of this batch into the 0-dim device
-        tensor `loss_out` and adds the number of argmax hits to the device int32 `ncorrect` - a validation loop reads
-        both once per epoch instead of synchronising twice per batch (EEGNet_tor.py:126-130 calls .item() per batch)."""
-        if not scores.is_cuda or scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
-            raise _lib.EavError("CrossEntropyLoss.accumulate: scores must be a contiguous fp32 [batch, classes] device tensor")
-        # every operand goes to the kernel as a raw pointer: a host tensor would be dereferenced on the GPU
-        soft = isinstance(targets, torch.Tensor) and targets.dim() == 2
-        if soft and not targets.is_floating_point():
-            raise TypeError(f"CrossEntropyLoss.accumulate: [batch, classes] targets are class probabilities, got {targets.dtype}")
-        if not isinstance(targets, torch.Tensor) or targets.device != scores.device \
-                or (tuple(targets.shape) != tuple(scores.shape) if soft else
-                    targets.dim() != 1 or targets.numel() != scores.shape[0]):
-            raise _lib.EavError(f"CrossEntropyLoss.accumulate: targets must be {scores.shape[0]} labels on {scores.device} "
-                                "(no CPU fallback: move the loader's tensors to the device)")
-        if not isinstance(loss_out, torch.Tensor) or loss_out.device != scores.device or loss_out.dtype != torch.float32 \
-                or loss_out.numel() < 1:
-            raise _lib.EavError(f"CrossEntropyLoss.accumulate: loss_out must be an fp32 tensor on {scores.device}")
-        if not isinstance(ncorrect, torch.Tensor) or ncorrect.device != scores.device or ncorrect.dtype != torch.int32 \
-                or ncorrect.numel() < 1:
-            raise _lib.EavError(f"CrossEntropyLoss.accumulate: ncorrect must be an int32 tensor on {scores.device}")
-        targets = self._targets(scores, targets, "CrossEntropyLoss.accumulate")
-        if self._flag is None or self._flag.device != scores.device:
-            self._flag = torch.zeros((), dtype=torch.int32, device=scores.device)
-        scratch, general = self._route(scores, targets)
-        _ce_launch(scratch, scores, targets, loss_out, None, ncorrect, self._flag, general)
-
-    def __call__(self, scores, targets):
-        if isinstance(targets, torch.Tensor) and targets.dim() == 2 and not targets.is_floating_point():
-            raise TypeError(f"CrossEntropyLoss: [batch, classes] targets are class probabilities, got {targets.dtype}")
-        if not isinstance(scores, torch.Tensor) or not scores.is_cuda or not targets.is_cuda:
-            raise _lib.EavError("CrossEntropyLoss needs device tensors (no CPU fallback)")
-        if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
-            raise _lib.EavError(f"CrossEntropyLoss: scores must be a contiguous fp32 [batch, classes] tensor, got "
-                                f"{tuple(scores.shape)} {scores.dtype}")
-        targets = self._targets(scores, targets, "CrossEntropyLoss")
-        if self._flag is None or self._flag.device != scores.device:
-            self._flag = torch.zeros((), dtype=torch.int32, device=scores.device)
-        scratch, general = self._route(scores, targets)
-        return _CEFn.apply(scores, targets, self._flag, scratch, general)
-
-
-class _ElementLossFn(torch.autograd.Function):
-    """_CEFn's shape for the element-wise criteria: the forward launch produces the loss and d loss / d scores together."""
-
-    @staticmethod
-    def forward(ctx, scores, targets, crit):
-        loss = torch.empty((), dtype=torch.float32, device=scores.device)
-        dsc = torch.empty_like(scores) if ctx.needs_input_grad[0] else None      # no gradient buffer under no_grad
-        crit._launch(scores, targets, loss, dsc, None)
-        ctx.dsc = dsc
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        return _seeded(ctx.dsc, gout), None, None
-
-
-class _ElementLoss:
-    """What BCEWithLogitsLoss and MSELoss share: the mean over all batch x classes elements and its gradient from one
-    launch of csrc/head_loss.hip (one wave per row, row sums added in row order - no atomics, two runs give the same bits).
-
-    Targets are fp32 [batch, classes] on the scores' device ([batch] accepted for one class; integer targets are
-    converted to fp32) and are not validated - torch accepts any float - so `check()` has nothing to report and is a
-    no-op that trainers may call blindly.  The kernels' per-row scratch is kept on the criterion, one buffer per
-    (batch, device): nothing is allocated for it in the launch path, and nothing synchronises with the host."""
-
-    _NAME = _ENTRY = None
-
-    def __init__(self):
-        self._scratch = {}
-
-    def check(self):
-        pass
-
-    def _scratch_for(self, scores):
-        key = (scores.shape[0], scores.device)
-        if key not in self._scratch:
-            self._scratch[key] = torch.empty(_lib.plain("eav_head_loss_ws_floats", scores.shape[0]), dtype=torch.float32,
-                                             device=scores.device)
-        return self._scratch[key]
-
-    def _operands(self, scores, targets, who):
-        if not isinstance(scores, torch.Tensor) or not scores.is_cuda or not isinstance(targets, torch.Tensor) \
-                or not targets.is_cuda:
-            raise _lib.EavError(f"{who} needs device tensors (no CPU fallback)")
-        if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
-            raise _lib.EavError(f"{who}: scores must be a contiguous fp32 [batch, classes] tensor, got "
-                                f"{tuple(scores.shape)} {scores.dtype}")
-        B, NC = scores.shape
-        # every operand goes to the kernel as a raw pointer: a tensor elsewhere would be dereferenced on this GPU
-        if targets.device != scores.device:
-            raise _lib.EavError(f"{who}: targets are on {targets.device}, the scores on {scores.device}")
-        if tuple(targets.shape) != (B, NC) and not (NC == 1 and tuple(targets.shape) == (B,)):
-            raise _lib.EavError(f"{who}: targets {tuple(targets.shape)} for scores {(B, NC)}")
-        if targets.dtype != torch.float32:
-            targets = targets.float()
-        return targets.reshape(B, NC).contiguous()
-
-    def _out_check(self, t, dtype, what, scores, who):
-        if not isinstance(t, torch.Tensor) or t.device != scores.device or t.dtype != dtype or t.numel() < 1:
-            raise _lib.EavError(f"{who}: {what} must be a {str(dtype).replace('torch.', '')} tensor on {scores.device}")
-
-    def __call__(self, scores, targets):
-        targets = self._operands(scores, targets, self._NAME)
-        return _ElementLossFn.apply(scores, targets, self)
-
-
-class BCEWithLogitsLoss(_ElementLoss):
-    """``nn.BCEWithLogitsLoss()`` (mean over batch x classes; no pos_weight): HF's loss for
-    problem_type "multi_label_classification".  Term max(x, 0) - x t + log1p(exp(-|x|)), torch's form, finite for any
-    finite logit; gradient (sigmoid(x) - t) / (batch x classes).  See _ElementLoss for targets, scratch and check()."""
-
-    _NAME = "BCEWithLogitsLoss"
-
-    def _launch(self, scores, targets, loss, dsc, nhits):
-        B, NC = scores.shape
-        _lib.call("eav_bce_logits_fwd_bwd", scores.data_ptr(), targets.data_ptr(), _lib.ptr(loss), _lib.ptr(dsc),
-                  _lib.ptr(nhits), self._scratch_for(scores).data_ptr(), B, NC, _lib.stream_ptr())
-
-    def accumulate(self, scores, targets, loss_out, nhits):
-        """Evaluation form (no gradient, nothing read back): the batch's mean loss into the 0-dim device tensor
-        `loss_out`, and the number of elements with (score > 0) == (target > 0.5) - the multi-label counterpart of
-        CrossEntropyLoss's argmax hits - added to the device int32 `nhits`."""
-        who = "BCEWithLogitsLoss.accumulate"
-        targets = self._operands(scores, targets, who)
-        self._out_check(loss_out, torch.float32, "loss_out", scores, who)
-        self._out_check(nhits, torch.int32, "nhits", scores, who)
-        self._launch(scores, targets, loss_out, None, nhits)
-
-
-class MSELoss(_ElementLoss):
-    """``nn.MSELoss()`` (mean over batch x classes): HF's loss for problem_type "regression".  Term (x - t)^2, gradient
-    2 (x - t) / (batch x classes).  See _ElementLoss for targets, scratch and check()."""
-
-    _NAME = "MSELoss"
-
-    def _launch(self, scores, targets, loss, dsc, nhits):
-        B, NC = scores.shape
-        _lib.call("eav_mse_fwd_bwd", scores.data_ptr(), targets.data_ptr(), _lib.ptr(loss), _lib.ptr(dsc),
-                  self._scratch_for(scores).data_ptr(), B, NC, _lib.stream_ptr())
-
-    def accumulate(self, scores, targets, loss_out):
-        """Evaluation form (no gradient, nothing read back): the batch's mean loss into the 0-dim device tensor `loss_out`."""
-        who = "MSELoss.accumulate"
-        targets = self._operands(scores, targets, who)
-        self._out_check(loss_out, torch.float32, "loss_out", scores, who)
-        self._launch(scores, targets, loss_out, None, None)

@@ -38,6 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, pos_interp, pos_time
+from .criteria import BCEWithLogitsLoss, CrossEntropyLoss, MSELoss
 from .encoder_config import (HEAD_MAX_CLASSES, MAX_TOKENS, PROBLEM_TYPES, _check_single_label,  # noqa: F401 (re-exported)
                              ast_length_geometry, config_from_hf, config_to_hf, interpolated_geometry, make_config,
                              normalise_key, param_shapes, rank_dropout_seed, resolve_problem_type)
@@ -45,7 +46,7 @@ from .encoder_dropout import EncoderDropout
 from .encoder_head import EncoderHead, _HeadFn
 from .encoder_layers import Fp32Layers, SplitLayers
 from .encoder_outputs import EncoderOutputs
-from .optim import BCEWithLogitsLoss, CrossEntropyLoss, MSELoss, flatten_parameters
+from .optim import flatten_parameters
 from .runtime import KernelFn, KernelModule, gather_batch
 
 DEFAULT_PRECISION = "split"
@@ -381,7 +382,7 @@ class Encoder(KernelModule):
 
     def criterion(self, labels=None):
         """The criterion of cfg.problem_type, held on the encoder: CrossEntropyLoss, BCEWithLogitsLoss or MSELoss
-        (optim.py).  While the type is unset, `labels` resolve it as HF does (resolve_problem_type) and it is written into
+        (criteria.py).  While the type is unset, `labels` resolve it as HF does (resolve_problem_type) and it is written into
         cfg.problem_type, where it stays - HF mutates its config in the same way."""
         c = self.cfg
         if c.problem_type is None:

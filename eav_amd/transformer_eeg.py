@@ -29,7 +29,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .optim import CrossEntropyLoss, FusedAdam
+from .criteria import CrossEntropyLoss
+from .optim import FusedAdam
 from .runtime import BN_M1, BN_M2, DeviceLoader, KernelFn, KernelModule, bn_field, train_step
 
 NF, KC, POOL, STRIDE, HD = 40, 13, 35, 7, 64     # filters / conv taps / pool window / pool stride / attention tile

@@ -269,3 +269,36 @@ def test_dirty_ranges_are_recorded_per_job():
     untracked.set_grads(_grads(400))
     uopt.step()
     assert not getattr(untracked.flat, "_eav_dirty", [])
+
+
+def test_default_path_launches_group_by_group_and_records_each_launch(monkeypatch):
+    """The default-path twin of test_dirty_ranges_are_recorded_per_job: one eav_adam_step per run, group 0's tensors by
+    address and then group 1's, each with its group's lr and weight decay, and one dirty range per launch in that order."""
+    net = _Net(track_dirty=True)
+    opt = net.optimizer(multi_tensor=False)
+    net.set_grads(_grads(400))
+    calls, real = [], _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append((name, a)), real(name, *a))[1])
+    opt.step()
+    monkeypatch.setattr(_lib, "call", real)
+    order = [0, 2, 4, 1, 3]
+    assert [name for name, _ in calls] == ["eav_adam_step"] * 5
+    # (p, g, m, v, n, lr, beta1, beta2, eps, weight decay, step, decoupled, device step count, stream)
+    assert [(a[0], a[4], a[5], a[9], a[10]) for _, a in calls] == \
+        [(net.params[i].data_ptr(), SIZES[i], *net.hyper(i), 1) for i in order]
+    want = [(p.data_ptr(), p.data_ptr() + 4 * p.numel()) for p in net.params]
+    assert net.flat._eav_dirty == [want[i] for i in order]
+    one = _Net(track_dirty=True)
+    oopt = one.optimizer(split=False, multi_tensor=False)         # one group: the five tensors merge into one launch
+    one.set_grads(_grads(400))
+    oopt.step()
+    assert one.flat._eav_dirty == [(one.params[0].data_ptr(), one.params[-1].data_ptr() + 4 * SIZES[-1])]
+    for _ in range(70):                                           # nobody drains the list: it collapses to its hull
+        opt.step()
+    assert len(net.flat._eav_dirty) <= 64
+    assert min(a for a, _ in net.flat._eav_dirty) == want[0][0] and max(b for _, b in net.flat._eav_dirty) == want[-1][1]
+    untracked = _Net()
+    uopt = untracked.optimizer(multi_tensor=False)
+    untracked.set_grads(_grads(400))
+    uopt.step()
+    assert not getattr(untracked.flat, "_eav_dirty", [])

@@ -1,5 +1,5 @@
 """csrc/head_loss.hip (eav_bce_logits_fwd_bwd, eav_mse_fwd_bwd) against torch on the CPU in float64, and the two criteria
-of optim.py on top of them.
+of criteria.py on top of them.
 
 Kernel rule, as tests/test_wide_head_gpu.py::_ce_check: GPU error <= 2 x (torch CPU fp32 error against float64) + 1e-5 x
 max|reference|, for the loss and for every element of the gradient.  The reference loss is tests/problem_type_ref.loss,

@@ -8,7 +8,8 @@ the one-launch-per-run path and on the job-table path (csrc/adam_jobs.hip).
 
 Every step is bracketed by HIP events; after 10 warm-up steps the median of 30 is reported (with the fastest and the
 slowest), the variants taken in turn so that drift hits them alike, with the launches per step (counted at _lib.call) and
-GB/s over the 28 bytes per parameter AdamW must move (16 read, 12 written).  The parameters keep changing, the gradient
+GB/s over the 28 bytes per parameter AdamW must move (16 read, 12 written), and the host wall time of the step() call
+itself (nothing synchronises inside it) over the same steps.  The parameters keep changing, the gradient
 is constant.  `--encoder` adds whole training steps of the reduced (2 layers, 64 wide) and the full ViT at B = 128 with
 the trainers' learning-rate options off and on (layer decay 0.75, no-decay split, linear schedule).
 
@@ -18,6 +19,7 @@ import os
 import statistics
 import subprocess
 import sys
+import time
 
 import numpy as np
 import torch
@@ -60,21 +62,24 @@ def ast_sized_module():
 
 
 def timed_steps(variants):
-    """variants: {label: step function}.  Returns {label: [ms] * TIMED}, the variants interleaved step by step."""
+    """variants: {label: step function}.  Returns ({label: [ms] * TIMED}, {label: [host ms] * TIMED}), the variants
+    interleaved step by step; the host time is the wall time of the call itself, which synchronises with nothing."""
     for _ in range(WARMUP):
         for fn in variants.values():
             fn()
     torch.cuda.synchronize()
-    times = {k: [] for k in variants}
+    times, host = {k: [] for k in variants}, {k: [] for k in variants}
     for _ in range(TIMED):
         for k, fn in variants.items():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
+            t0 = time.perf_counter()
             fn()
+            host[k].append(1e3 * (time.perf_counter() - t0))
             b.record()
             b.synchronize()
             times[k].append(a.elapsed_time(b))
-    return times
+    return times, host
 
 
 def launches_of(fn):
@@ -107,14 +112,15 @@ def optimiser_bench():
                        sum(p.numel() for p in params), flat.numel(), len(params))
     n, nflat, ntensors = opts["a"][1:]
     say(f"AST-base layout: {ntensors} tensors, {n} parameters ({nflat} floats in the flat buffer), fp32 p / g / m / v")
-    times = timed_steps({k: v[0].step for k, v in opts.items()})
+    times, host = timed_steps({k: v[0].step for k, v in opts.items()})
     what = {"a": "one group, single eav_adam_step", "b": "no-decay split, one eav_adam_step per run",
             "c": "no-decay split, job table (begin + step_jobs)"}
     for k in ("a", "b", "c"):
         names = launches_of(opts[k][0].step)
         ms = statistics.median(times[k])
         say(f"({k}) {what[k]}: median {ms:.3f} ms per step (min {min(times[k]):.3f}, max {max(times[k]):.3f}, {TIMED} steps), "
-            f"{len(names)} launches per step, {28 * n / ms / 1e6:.0f} GB/s over 28 B/param")
+            f"{len(names)} launches per step, {28 * n / ms / 1e6:.0f} GB/s over 28 B/param; host time of step() median "
+            f"{statistics.median(host[k]):.3f} ms (min {min(host[k]):.3f}, max {max(host[k]):.3f})")
 
 
 def encoder_bench(label, cfg, B):
@@ -136,7 +142,7 @@ def encoder_bench(label, cfg, B):
             crit(model(x).logits, y).backward()
             opt.step()
         runs["options on" if on else "options off"] = step
-    times = timed_steps(runs)
+    times, _ = timed_steps(runs)
     for k, fn in runs.items():
         names = launches_of(fn)
         adam = [n for n in names if n.startswith("eav_adam") or n.startswith("eav_counter")]
