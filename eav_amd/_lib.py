@@ -139,6 +139,11 @@ SIGNATURES = {
     "eav_im2col": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "eav_embed_finish": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_embed_bwd": [_p, _p, _p, _i, _i, _i, _i, _p],
+    "eav_patch_keep_plan": [_p, _p, _i, _i, _i, _u64, _p, _p, _p],
+    "eav_patch_keep_invert": [_p, _p, _i, _i, _i, _p],
+    "eav_im2col_keep": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "eav_embed_finish_keep": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "eav_embed_bwd_keep": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "eav_pos_bicubic_fwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "eav_pos_bicubic_bwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p],
     "eav_pos_time_fwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p],

@@ -123,6 +123,31 @@ def ast_length_geometry(cfg, T):
     return geo
 
 
+def patch_dropout_keep(npatch, p):
+    """The number of patches a sample keeps of `npatch` under patch dropout `p`: timm.layers.PatchDropout's
+    max(1, int(L * (1 - p)))."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"patch_dropout must satisfy 0 <= p < 1, got {p!r}")
+    return max(1, int(int(npatch) * (1.0 - p)))
+
+
+def patch_dropout_geometry(geo, p):
+    """The geometry of a training forward under patch dropout `p` (timm.layers.PatchDropout), derived from the one it would
+    have had - cfg itself, or what interpolated_geometry / ast_length_geometry made of it: a copy whose npatch is the kept
+    count K = patch_dropout_keep(P, p) and whose ntok is nextra + K, which is what everything below the embeddings reads.
+    The full grid stays beside them: H, W, ny, nx, pos_grid / time_grid are untouched (im2col and the position table are
+    those of the full grid) and grid_npatch = P.  Pure: needs no device.  ValueError unless 0 <= p < 1,
+    NotImplementedError for a full grid beyond MAX_TOKENS tokens."""
+    P = int(geo.npatch)
+    K = patch_dropout_keep(P, p)
+    if P + geo.nextra > MAX_TOKENS:
+        raise NotImplementedError(f"at most {MAX_TOKENS} tokens: the full grid gives {P + geo.nextra}")
+    out = SimpleNamespace(**vars(geo))
+    out.grid_npatch, out.npatch, out.ntok = P, K, geo.nextra + K
+    return out
+
+
 def resolve_problem_type(num_labels, labels):
     """The problem_type HF's ForSequenceClassificationLoss settles on when the config leaves it unset: one label is a
     regression, several labels with integer targets (torch.long / torch.int) a single-label classification, anything

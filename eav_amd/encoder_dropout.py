@@ -11,7 +11,10 @@ import torch
 from . import _lib
 
 # kind -> (id at layer 0, id stride per layer, attention rate?), in HF's call order; the name is "emb" / "<kind>.<layer>"
-SITES = {"emb": (0, 0, False), "attn": (1, 3, True), "attn_out": (2, 3, False), "mlp_out": (3, 3, False)}
+# "patch_keep" is no dropout site but the seed stream of the patch-dropout plan (patch_keep.py): an id no layer count
+# reaches (3 * layers < 2^23), still inside the 24 bits site_seed has room for.
+SITES = {"emb": (0, 0, False), "attn": (1, 3, True), "attn_out": (2, 3, False), "mlp_out": (3, 3, False),
+         "patch_keep": (1 << 23, 0, False)}
 
 
 def site_id(kind, layer=0):
@@ -52,7 +55,7 @@ class EncoderDropout:
         # (indexed by SITES' "attention rate?")
         shape = ((B, c.ntok, c.hidden), (B, c.heads, c.ntok, c.ntok))
         rate = (c.hidden_dropout, c.attention_dropout)
-        where = [("emb", 0)] + [(kind, i) for i in range(c.layers) for kind in SITES if kind != "emb"]
+        where = [("emb", 0)] + [(kind, i) for i in range(c.layers) for kind in SITES if SITES[kind][1]]      # (the per-layer kinds)
         return {site_name(kind, i): (site_id(kind, i), shape[SITES[kind][2]], rate[SITES[kind][2]])
                 for kind, i in where if rate[SITES[kind][2]] > 0.0}
 

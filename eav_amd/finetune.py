@@ -125,10 +125,14 @@ class FineTuneBase:
     # phase; the inputs are augmented only in epochs with freeze=False and never in _evaluate - the frozen phase keeps its
     # feature cache.  Training accuracy counts against the primary (first) label of a mixed sample.  With every option
     # at its default nothing of this is entered: the trainers launch what they always did.
+    #   patch_dropout     0 <= p < 1, timm's PatchDropout (Encoder.patch_dropout): every sample of an unfrozen epoch keeps a
+    #                     random max(1, int(P (1 - p))) of its P patch tokens - a regulariser that shortens the step.  Any
+    #                     problem type.  The frozen phase (its feature cache, its launches) and _evaluate see every token.
     label_smoothing = 0.0
     class_weights = None
     mixup_alpha = 0.0
     augment_seed = 0
+    patch_dropout = 0.0
     # Learning-rate options, set the same way; with all of them at their defaults _enter_phase does what it always did
     # and the optimiser keeps its one-launch-per-run path:
     #   lr_scheduler_type     "constant", "constant_with_warmup", "linear" or "cosine" (optim.LRSchedule, the lambdas of
@@ -210,6 +214,10 @@ class FineTuneBase:
                            getattr(self, "hflip", False), self.augment_seed)
         aug.fill = float(getattr(self, "mask_fill", 0.0))
         self._augment = aug if aug.active and not freeze else None
+        pd = float(self.patch_dropout)
+        if not 0.0 <= pd < 1.0:
+            raise ValueError(f"patch_dropout {self.patch_dropout!r} must satisfy 0 <= p < 1")
+        self.model.patch_dropout = 0.0 if freeze else pd
 
     def _epoch_plan(self, batches):
         """The augmentation plan of a training epoch over `batches` (None: plain gathers)."""

@@ -25,7 +25,7 @@ the MLP and the attention outputs / log-sum-exps; the fused attention never mate
 This module is the public model, its loading and saving, the workspace and the two launch sequences.  The rest of the encoder:
 encoder_config (what needs no device), encoder_layers (the two layer schedules), encoder_head (the classification head and
 Encoder.head), encoder_dropout (the dropout sites and generator), encoder_outputs (output_attentions / output_hidden_states /
-attention rollout).
+attention rollout), patch_keep (patch dropout: the plan of who is kept and its tables).
 """
 from __future__ import annotations
 
@@ -41,12 +41,13 @@ from . import _lib, pos_interp, pos_time
 from .criteria import BCEWithLogitsLoss, CrossEntropyLoss, MSELoss
 from .encoder_config import (HEAD_MAX_CLASSES, MAX_TOKENS, PROBLEM_TYPES, _check_single_label,  # noqa: F401 (re-exported)
                              ast_length_geometry, config_from_hf, config_to_hf, interpolated_geometry, make_config,
-                             normalise_key, param_shapes, rank_dropout_seed, resolve_problem_type)
+                             normalise_key, param_shapes, patch_dropout_geometry, rank_dropout_seed, resolve_problem_type)
 from .encoder_dropout import EncoderDropout
 from .encoder_head import EncoderHead, _HeadFn
 from .encoder_layers import Fp32Layers, SplitLayers
 from .encoder_outputs import EncoderOutputs
 from .optim import flatten_parameters
+from .patch_keep import EncoderPatchKeep
 from .runtime import KernelFn, KernelModule, gather_batch
 
 DEFAULT_PRECISION = "split"
@@ -177,6 +178,13 @@ class Encoder(KernelModule):
         # argument, and forward()'s parameter list is HF's.
         self.variable_length = False
         self._active_geo = None       # None: the geometry of cfg
+        # Patch dropout (timm.layers.PatchDropout), 0 <= p < 1: in training mode every sample keeps a random
+        # K = max(1, int(P (1 - p))) of the P patches of the forward's grid, chosen after the position embedding; the readout
+        # tokens always stay, evaluation sees every token.  The forward then runs at patch_dropout_geometry of the geometry
+        # it would have had - the dropped patches leave before the projection (patch_keep.py, csrc/patch_keep.hip).  0 (the
+        # default) and eval mode launch exactly what they always did.
+        self.patch_dropout = 0.0
+        self._patch_keep = EncoderPatchKeep(self)
         # HF's model(..., output_attentions=, output_hidden_states=): these attributes are the defaults of those two keywords
         # of __call__ (HF: config.output_attentions / config.output_hidden_states; from_pretrained copies them from config.json)
         self.output_attentions = False
@@ -357,6 +365,14 @@ class Encoder(KernelModule):
             want = (c.W, c.H) if c.kind == "ast" else (c.C, c.H, c.W)
             if tuple(x.shape[1:]) != want:
                 raise ValueError(f"expected input [B,{','.join(map(str, want))}], got {tuple(x.shape)}")
+        pd = float(self.patch_dropout)
+        if not 0.0 <= pd < 1.0:
+            raise ValueError(f"patch_dropout must satisfy 0 <= p < 1, got {self.patch_dropout!r}")
+        if self.training and pd > 0.0:
+            if self.dropout_active():
+                raise NotImplementedError("dropout together with patch dropout is not implemented (DESIGN.md section 11): the "
+                                          "dropout sites are laid out for cfg.ntok tokens")
+            geo = patch_dropout_geometry(geo if geo is not None else c, pd)
         self._active_geo = geo
         x = x.contiguous().float()
         self._ensure_flat()
@@ -442,6 +458,25 @@ class Encoder(KernelModule):
         forward_counter() returns after that forward), as set_dropout_masks takes them."""
         return self._dropgen.generated_masks(B, counter, seed)
 
+    def set_patch_keep(self, idx):
+        """Testing hook, the twin of set_dropout_masks: explicit kept patches [B, K] (integers, every row ascending and
+        unique, in [0, P) of the forward that uses them; K that forward's kept count) instead of the generated plan; None
+        returns to generated plans.  Validated here, once - it reads the table back, so call it outside a capture."""
+        self._patch_keep.set_table(idx)
+
+    def generated_patch_keep(self, B, counter, seed=None):
+        """The keep table [B, K] (int32) the plan draws in the forward whose counter value is `counter` (the value
+        forward_counter() returns after that forward), at the geometry of the most recent patch-dropped forward - before
+        any: cfg's under patch_dropout."""
+        return self._patch_keep.generated(B, counter, seed)
+
+    def last_patch_keep(self):
+        """The keep table [B, K] (int32, a copy) of the most recent forward, which must have dropped patches."""
+        ws = self._ws
+        if ws is None or getattr(ws, "keep", None) is None:
+            raise _lib.EavError("Encoder.last_patch_keep: the most recent forward dropped no patches")
+        return ws.keep.clone()
+
     def _drop_add(self, y, resid, out, n, kind, layer=0):
         """out = resid + Dropout(y) at the hidden-dropout site (kind, layer); resid None: the gate alone, the site's backward."""
         self._call("eav_tf_dropout_add", y, resid, out, n, *self._ws.drop.site(kind, layer), self._st)
@@ -452,6 +487,12 @@ class Encoder(KernelModule):
         ast_length_geometry); None, None for cfg itself and wherever the stored table serves as it is."""
         return getattr(c, "pos_grid", None), getattr(c, "time_grid", None)
 
+    @staticmethod
+    def _grid(c):
+        """The patch count of the full grid of a patch-dropped geometry (patch_dropout_geometry: c.npatch of them are
+        kept); None for every other geometry."""
+        return getattr(c, "grid_npatch", None)
+
     def _alloc(self, B, dev, full_backward, lay):
         c = self._geo
         D, FF, N, H, Lr = c.hidden, c.ff, c.ntok, c.heads, c.layers
@@ -461,11 +502,16 @@ class Encoder(KernelModule):
         ws = SimpleNamespace(B=B, M=M, ldn=ldn, full=full_backward, layers=lay, fused=self._fused_attention())
         nsave = Lr if full_backward else 1
         ws.col = f(B * c.npatch, c.kp)
+        grid = self._grid(c)
+        ws.keep = None                        # patch dropout: the forward's keep table (its own buffer or an explicit one)
+        if grid is not None:
+            ws.keep_own, ws.inv = self._patch_keep.buffers(c, B, dev)
         if self._fitted(c) != (None, None):
             # the position table resampled (ViT) / fitted along time (AST) to this forward's patch grid
-            ws.pos_i = f(N, D)
+            Np = N if grid is None else c.nextra + grid
+            ws.pos_i = f(Np, D)
             if full_backward:                             # ... and the gradient eav_embed_bwd leaves for that table
-                ws.dpos_i = f(N, D)
+                ws.dpos_i = f(Np, D)
         ws.hs = [f(M, D) for _ in range(Lr + 1)] if full_backward else [f(M, D), f(M, D)]
         keep = lay.fp32_copies(nsave)         # of y1, y2, act (and qkv under the fused attention): split mode keeps planes
         ws.y1 = [f(M, D) for _ in range(keep)]
@@ -588,7 +634,7 @@ class Encoder(KernelModule):
         of the B = 128 one.  One allocated for a full backward also serves the no_grad forwards of its batch size; one
         without the backward's buffers is replaced when a full backward comes."""
         key = (B, str(dev), self._fused_attention(), lay.split, self._head_wide(),
-               (self._geo.H, self._geo.W))
+               (self._geo.H, self._geo.W), self._geo.npatch if self._grid(self._geo) is not None else None)
         old = self._wss.get(key)
         if old is not None and full and not old.full:
             del self._wss[key]
@@ -648,12 +694,20 @@ class Encoder(KernelModule):
         lay.begin_forward(ws, x.device, full)
         pre = c.prefix
         # patch embedding: im2col rows x projection weight -> token rows [nextra:], then cls/dist + positions
-        L("eav_im2col", P(x), P(ws.col), B, c.C, c.H, c.W, c.patch, c.sy, c.sx, c.transposed, st)
+        dropped = self._grid(c) is not None      # patch dropout: the three embedding launches in their _keep forms
+        if dropped:
+            self._patch_keep.begin(ws, B, x.device)
+            L("eav_im2col_keep", P(x), P(ws.col), P(ws.keep), B, c.C, c.H, c.W, c.patch, c.sy, c.sx, c.transposed, c.npatch, st)
+        else:
+            L("eav_im2col", P(x), P(ws.col), B, c.C, c.H, c.W, c.patch, c.sy, c.sx, c.transposed, st)
         h0 = ws.hs[0]
         lay.patch_embed(ws, h0, w(f"{pre}.embeddings.patch_embeddings.projection.bias"))
         pos = self._fit_positions(w(f"{pre}.embeddings.position_embeddings"), ws)
-        L("eav_embed_finish", P(h0), w(f"{pre}.embeddings.cls_token"),
-          w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None, pos, B, N, D, c.nextra, st)
+        tokens = (w(f"{pre}.embeddings.cls_token"), w(f"{pre}.embeddings.distillation_token") if c.kind == "ast" else None)
+        if dropped:
+            L("eav_embed_finish_keep", P(h0), *tokens, pos, P(ws.keep), B, c.npatch, D, c.nextra, st)
+        else:
+            L("eav_embed_finish", P(h0), *tokens, pos, B, N, D, c.nextra, st)
         if drop.ph > 0.0:
             self._drop_add(P(h0), None, P(h0), ws.M * D, "emb")
         outs = self._outs
@@ -733,8 +787,11 @@ class Encoder(KernelModule):
             # the position table's gradient: straight into the stored table's, or - the table fitted to this forward's patch
             # grid - into ws.dpos_i and through the adjoint of the fit
             fitted = self._fitted(c) != (None, None)
-            L("eav_embed_bwd", dh, P(ws.dpos_i) if fitted else gp(f"{pre}.embeddings.position_embeddings"), P(ws.demb), B, N,
-              D, c.nextra, st)
+            dpos = P(ws.dpos_i) if fitted else gp(f"{pre}.embeddings.position_embeddings")
+            if self._grid(c) is not None:      # patch dropout: the full grid's rows, +0.0 where nobody kept
+                L("eav_embed_bwd_keep", dh, dpos, P(ws.demb), P(ws.inv), B, c.grid_npatch, c.npatch, D, c.nextra, st)
+            else:
+                L("eav_embed_bwd", dh, dpos, P(ws.demb), B, N, D, c.nextra, st)
             if fitted:
                 self._fit_positions_backward(ws, gp(f"{pre}.embeddings.position_embeddings"))
             gpos = gflat[offs[f"{pre}.embeddings.position_embeddings"][0]:]

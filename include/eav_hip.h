@@ -694,6 +694,31 @@ int eav_im2col(const float* x, float* col, int B, int C, int H, int W, int P, in
 int eav_embed_finish(float* h, const float* cls, const float* dist, const float* pos, int B, int ntok, int D,
                      int nextra, void* stream);
 int eav_embed_bwd(const float* dh, float* dpos, float* demb, int B, int ntok, int D, int nextra, void* stream);
+/* Patch dropout (timm.layers.PatchDropout; csrc/patch_keep.hip): a training forward keeps K of the P patches of every sample
+ * and the readout tokens.  All five kernels are in gather form - no atomics, the same bits on every run - and read nothing
+ * back, so a captured step may hold them.  keep is int32 [B, K], the kept patch indices of every sample ascending; inv is
+ * int32 [B, P], the slot of patch p in keep[b] or -1.  1 <= K <= P <= EAV_MAX_TOKENS - nextra.
+ * eav_patch_keep_plan draws the tables, one workgroup per sample: the key of patch p of sample b is
+ * eav_hash32(seed + 2 * *counter, b*P + p) (counter NULL: seed itself; the rule of the dropout kernels), the kept set the K
+ * smallest of the total order (key, p) - the 24-bit keys do tie, the patch index decides.  keys (optional, uint32 [B, P])
+ * replaces the hash, as the explicit masks replace it for the dropout kernels.
+ * eav_patch_keep_invert builds inv from a given keep (rows ascending and unique).
+ * eav_im2col_keep: col [B*K, C*P*P], row b*K + s the row eav_im2col forms for patch keep[b][s] (arguments as eav_im2col;
+ * an index outside the grid gives a row of zeros).
+ * eav_embed_finish_keep: h [B, nextra + K, D]; eav_embed_finish with the position row of patch slot s taken from
+ * pos[nextra + keep[b][s]], pos the full [nextra + P, D] table.
+ * eav_embed_bwd_keep: demb[b*K + s] = dh[b, nextra + s]; dpos [nextra + P, D]: rows r < nextra the sum over b of dh[b, r],
+ * row nextra + p the sum in ascending b of dh[b, nextra + inv[b][p]] over the samples that kept p, +0.0 where none did. */
+#define EAV_MAX_TOKENS 2048
+int eav_patch_keep_plan(int* keep, int* inv, int B, int P, int K, uint64_t seed, const uint64_t* counter,
+                        const uint32_t* keys, void* stream);
+int eav_patch_keep_invert(const int* keep, int* inv, int B, int P, int K, void* stream);
+int eav_im2col_keep(const float* x, float* col, const int* keep, int B, int C, int H, int W, int P, int sy, int sx,
+                    int transposed, int K, void* stream);
+int eav_embed_finish_keep(float* h, const float* cls, const float* dist, const float* pos, const int* keep, int B, int K,
+                          int D, int nextra, void* stream);
+int eav_embed_bwd_keep(const float* dh, float* dpos, float* demb, const int* inv, int B, int P, int K, int D, int nextra,
+                       void* stream);
 /* ViT position table at another patch grid (HF ViTEmbeddings.interpolate_pos_encoding: F.interpolate(mode="bicubic",
  * align_corners=False), no antialiasing): pos [nextra + g*g, D] -> out [nextra + ny*nx, D], the first nextra rows copied,
  * the patch rows out = (Wy (x) Wx) pos.  iy / ix [n_out][4] are the source indices of the four taps of every output index

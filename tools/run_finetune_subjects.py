@@ -10,6 +10,8 @@
     python tools/run_finetune_subjects.py audio --audio-root Datasets/EAV      (the dataset folder, Dataload_audio.py:87-93)
     python tools/run_finetune_subjects.py audio --label-smoothing 0.1 --mixup-alpha 0.4 --time-mask 48 --freq-mask 24
                                                      (the regularisers of finetune.FineTuneBase; vision: --hflip)
+    python tools/run_finetune_subjects.py audio --patch-dropout 0.5   (the unfrozen epochs train on half of every clip's patches:
+                                                                       608 tokens instead of 1214)
     python -m torch.distributed.run --nproc-per-node 8 tools/run_finetune_subjects.py audio ...
 
 Every subject is one `AudioModelTrainer` / `ImageClassifierTrainer` run with the reference's hyper-parameters
@@ -105,6 +107,9 @@ def main():
     ap.add_argument("--hflip", action="store_true", help="vision only: mirror every frame left-right with probability 0.5 in "
                     "the unfrozen epochs (trainer.hflip)")
     ap.add_argument("--augment-seed", type=int, default=0, help="seed of the augmentation draws (trainer.augment_seed)")
+    ap.add_argument("--patch-dropout", type=float, default=0.0, metavar="P", help="every sample of an unfrozen epoch keeps a "
+                    "random max(1, int(patches x (1 - P))) of its patch tokens, timm's PatchDropout (trainer.patch_dropout); "
+                    "0 <= P < 1")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     if args.grad_accum < 1 or (args.max_grad_norm is not None and not args.max_grad_norm > 0):
@@ -113,6 +118,8 @@ def main():
         ap.error("--label-smoothing takes E in [0, 1], --mixup-alpha A >= 0, --time-mask / --freq-mask integers >= 0")
     if not 0.0 <= args.warmup_ratio <= 1.0 or not 0.0 < args.layer_decay <= 1.0:
         ap.error("--warmup-ratio takes R in [0, 1] and --layer-decay D in (0, 1]")
+    if not 0.0 <= args.patch_dropout < 1.0:
+        ap.error("--patch-dropout takes P with 0 <= P < 1")
     audio = args.kind == "audio"
     if audio and args.hflip:
         ap.error("--hflip is a vision option")
@@ -167,6 +174,7 @@ def main():
                 tr.layer_decay, tr.decay_bias_and_norm = args.layer_decay, not args.no_decay_bias_norm
                 tr.label_smoothing, tr.class_weights = args.label_smoothing, args.class_weights
                 tr.mixup_alpha, tr.augment_seed = args.mixup_alpha, args.augment_seed
+                tr.patch_dropout = args.patch_dropout
                 if audio:
                     tr.time_mask, tr.freq_mask = args.time_mask, args.freq_mask
                 else:
