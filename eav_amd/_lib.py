@@ -144,6 +144,8 @@ SIGNATURES = {
     "eav_im2col_keep": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "eav_embed_finish_keep": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_embed_bwd_keep": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "eav_drop_path_plan": [_p, _i, _i, _d, _u64, _p, _p, _p],
+    "eav_drop_path_add": [_p, _p, _p, _p, _i, _i64, _p],
     "eav_pos_bicubic_fwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "eav_pos_bicubic_bwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p],
     "eav_pos_time_fwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p],

@@ -71,9 +71,14 @@ class EncoderDropout:
                       _lib.stream_ptr())
         return out
 
+    def generates(self):
+        """Whether the forward about to run draws its masks from the device forward counter."""
+        m, c = self.m, self.m.cfg
+        return m.training and (c.hidden_dropout > 0.0 or c.attention_dropout > 0.0) and m._dropout_masks is None
+
     def begin(self, ws, B, dev):
-        """The DropState of this forward, left on the workspace: explicit masks are validated, else the device counter is
-        advanced (by a launch)."""
+        """The DropState of this forward, left on the workspace: explicit masks are validated, else it reads the device
+        forward counter (which the encoder advances, once per forward, for all its generators)."""
         m, c = self.m, self.m.cfg
         ph, pa = (c.hidden_dropout, c.attention_dropout) if m.training else (0.0, 0.0)
         d = ws.drop = DropState(m.dropout_seed, ph, pa)
@@ -87,5 +92,4 @@ class EncoderDropout:
                         raise _lib.EavError(f"set_dropout_masks: site {name!r} needs a contiguous uint8 mask {shape} on {dev}")
             else:
                 d.cnt = m._counter(dev).data_ptr()
-                m._call("eav_counter_inc", d.cnt, m._st)
         return d

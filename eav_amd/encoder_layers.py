@@ -29,6 +29,12 @@ B_DH2, B_DACT, B_DH1, B_DAO, B_DS, B_DQKV, B_DY2, B_DY1 = BWD_SLOTS = range(8)  
 FS, BS = len(FWD_SLOTS), len(BWD_SLOTS)
 
 
+def path_on(ws, i):
+    """Whether layer i of the forward on this workspace drops paths (encoder_drop_path: p_i > 0 in training mode)."""
+    dp = ws.dpath
+    return dp is not None and 0 <= i < len(dp.p) and dp.on(i)
+
+
 def gemm_f32(m, A, B, C, M, N, K, lda, ldb, ldc, tA=0, tB=0, batch=1, heads=1, sA=(0, 0), sB=(0, 0), sC=(0, 0), alpha=1.0):
     m._call("eav_gemm_f32", A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch, heads, sA[0], sA[1], sB[0], sB[1],
             sC[0], sC[1], float(alpha), None, 0, None, None, 0, 0, m._st)
@@ -150,20 +156,27 @@ class Fp32Layers:
                  sA=(H * N * ldn, N * ldn), sB=(N * 3 * D, hd), sC=(N * D, hd))
         m._outputs.attention(i, j, scale, qkv=qkv)
         # (hidden dropout sits between the bias and the residual add: the product leaves without the residual and one
-        # element-wise pass forms resid + Dropout(product))
+        # element-wise pass forms resid + Dropout(product); drop path - a layer with p_i > 0 - takes the same road with its
+        # per-sample scales)
         hd_on = drop.ph > 0.0
+        dp_on = path_on(ws, i)
+        bare = hd_on or dp_on
         gemm(P(ws.ao[j]), w(f"{Lk}.attention.o_proj.weight"), P(ws.hmid[j]), M, D, D, D, D, D,
-             bias=w(f"{Lk}.attention.o_proj.bias"), resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
+             bias=w(f"{Lk}.attention.o_proj.bias"), resid=None if bare else P(hin), ldr=0 if bare else D)
         if hd_on:
             m._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, "attn_out", i)
+        elif dp_on:
+            m._path_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), i, 0)
         L("eav_layernorm_fwd", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"), w(f"{Lk}.layernorm_after.bias"),
           P(ws.y2[j]), stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
         gemm(P(ws.y2[j]), w(f"{Lk}.mlp.fc1.weight"), P(ws.act[j]), M, FF, D, D, D, FF,
              bias=w(f"{Lk}.mlp.fc1.bias"), gelu=1, pre=P(ws.pre[j]))
         gemm(P(ws.act[j]), w(f"{Lk}.mlp.fc2.weight"), P(hout), M, D, FF, FF, FF, D,
-             bias=w(f"{Lk}.mlp.fc2.bias"), resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
+             bias=w(f"{Lk}.mlp.fc2.bias"), resid=None if bare else P(ws.hmid[j]), ldr=0 if bare else D)
         if hd_on:
             m._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, "mlp_out", i)
+        elif dp_on:
+            m._path_add(P(hout), P(ws.hmid[j]), P(hout), i, 1)
 
     def layer_backward(self, i, Lk, stp, scale):
         """Backward of one layer on the exact-fp32 kernels: ws.dh holds the gradient w.r.t. the layer output on entry, the
@@ -176,11 +189,16 @@ class Fp32Layers:
         hd = D // H
         drop = ws.drop
         dh, dy, dao, dact, dqkv = P(ws.dh), P(ws.dy), P(ws.dao), P(ws.dact), P(ws.dqkv)
-        # fc2: h_out = h_mid + Dropout(act.W2^T + b2): the products see dh o M / (1 - p), the residual branch dh
+        # fc2: h_out = h_mid + Dropout(act.W2^T + b2): the products see dh o M / (1 - p), the residual branch dh (drop path:
+        # dh[b] s[b])
         g_dh = dh
+        dp_on = path_on(ws, i)
         if drop.ph > 0.0:
             g_dh = P(ws.dhd)
             m._drop_add(dh, None, g_dh, M * D, "mlp_out", i)
+        elif dp_on:
+            g_dh = P(ws.dhd)
+            m._path_add(dh, None, g_dh, i, 1)
         wgrad(g_dh, P(ws.act[i]), gp(f"{Lk}.mlp.fc2.weight"), D, FF, M, D, FF)
         bias_grad(g_dh, M, D, D, gp(f"{Lk}.mlp.fc2.bias"))
         gemm(g_dh, w(f"{Lk}.mlp.fc2.weight"), dact, M, FF, D, D, FF, FF, tB=1)
@@ -196,6 +214,8 @@ class Fp32Layers:
         # o_proj
         if drop.ph > 0.0:
             m._drop_add(dh, None, g_dh, M * D, "attn_out", i)
+        elif dp_on:
+            m._path_add(dh, None, g_dh, i, 0)
         wgrad(g_dh, P(ws.ao[i]), gp(f"{Lk}.attention.o_proj.weight"), D, D, M, D, D)
         bias_grad(g_dh, M, D, D, gp(f"{Lk}.attention.o_proj.bias"))
         gemm(g_dh, w(f"{Lk}.attention.o_proj.weight"), dao, M, D, D, D, D, D, tB=1)
@@ -351,10 +371,12 @@ class SplitLayers:
     def begin_forward(self, ws, dev, full):
         self.refresh_weight_planes(dev, full)
         ws.fslots.zero_()
+        if full and ws.dpath is not None and getattr(ws, "dslots", None) is None:      # drop path: as under hidden dropout
+            ws.dslots, ws.dslot = self.slots(2 * self.m._geo.layers, dev)
 
     def begin_backward(self, ws):
         m, c = self.m, self.m._geo
-        if ws.drop.ph > 0.0:
+        if ws.drop.ph > 0.0 or ws.dpath is not None:
             ws.dslots.zero_()
         ws.bslots.zero_()
         # dh of the top layer comes from the head (token-row scatter): one pass for its maximum; every other dh
@@ -573,12 +595,17 @@ class SplitLayers:
         wpl, wsl = wp.get(f"o{i}")
         # (hidden dropout: the product leaves without the residual, one element-wise pass forms resid + Dropout(product) - the
         # split GEMM's epilogue stays as it is)
+        # (drop path, a layer with p_i > 0: the same road with the per-sample scales of the forward's table)
         drop = ws.drop
         hd_on = drop.ph > 0.0
+        dp_on = path_on(ws, i)
+        bare = hd_on or dp_on
         gemm_sp(P(ws.aop[j]), s_ao, wpl, wsl, P(ws.hmid[j]), M, D, D, D, bias=w(f"{Lk}.attention.o_proj.bias"),
-                resid=None if hd_on else P(hin), ldr=0 if hd_on else D)
+                resid=None if bare else P(hin), ldr=0 if bare else D)
         if hd_on:
             m._drop_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), M * D, "attn_out", i)
+        elif dp_on:
+            m._path_add(P(ws.hmid[j]), P(hin), P(ws.hmid[j]), i, 0)
         if fusedp:
             L("eav_layernorm_fwd_planes", P(ws.hmid[j]), w(f"{Lk}.layernorm_after.weight"),
               w(f"{Lk}.layernorm_after.bias"), None, P(ws.y2p[j]), s_y2, stp + 8 * M, stp + 12 * M, M, D, c.eps, st)
@@ -600,9 +627,11 @@ class SplitLayers:
             L("eav_sp_convert_gelu", pre, M, FF, FF, s_act, P(ws.actp[j]), None, st)
         wpl, wsl = wp.get(f"fc2{i}")
         gemm_sp(P(ws.actp[j]), s_act, wpl, wsl, P(hout), M, D, FF, D, bias=w(f"{Lk}.mlp.fc2.bias"),
-                resid=None if hd_on else P(ws.hmid[j]), ldr=0 if hd_on else D)
+                resid=None if bare else P(ws.hmid[j]), ldr=0 if bare else D)
         if hd_on:
             m._drop_add(P(hout), P(ws.hmid[j]), P(hout), M * D, "mlp_out", i)
+        elif dp_on:
+            m._path_add(P(hout), P(ws.hmid[j]), P(hout), i, 1)
 
     def layer_backward(self, i, Lk, stp, scale):
         """Backward of one layer: dh (gradient w.r.t. the layer output, fp32) in ws.dh on entry, gradient w.r.t. the
@@ -627,18 +656,28 @@ class SplitLayers:
         # The gate is a pass of its own into ws.dhd; the gated tensor gets its own MEASURED scale slot (s_dh2 / s_dh1) - the
         # producers' slots hold max|dh| of the ungated tensor, up to 1 / (1 - p) too small.  fused_dh is off on such a step:
         # the LayerNorm backward's planes (and their a-priori bound) are those of the ungated dh.
+        # Drop path gates per sample (dh[b] s[b], s up to 1 / (1 - p_i)) and per layer: the layers with p_i > 0 take this road,
+        # the others keep the fused one - where the LayerNorm backward that would write a layer's planes belongs to a gated
+        # neighbour, that hand-over alone falls back to the conversion pass (fdh_top / fdh_bot).
         drop = ws.drop
         hd_on = drop.ph > 0.0
-        fdh = fdh and not hd_on
+        dp_on = path_on(ws, i)
+        gated = lambda k: hd_on or path_on(ws, k)  # noqa: E731
+        fdh = fdh and not gated(i)
+        fdh_top = fdh and i < c.layers - 1 and not gated(i + 1)       # the layer above wrote the planes of this layer's dh
+        fdh_bot = fdh and i > 0 and not gated(i - 1)                  # this layer writes those of the layer below
         s_dh2, s_dh1, g_dh = b_dh2, b_dh1, dh
-        if hd_on:
+        if hd_on or dp_on:
             s_dh2, s_dh1, g_dh = ws.dslot[2 * i], ws.dslot[2 * i + 1], P(ws.dhd)
-            m._drop_add(dh, None, g_dh, M * D, "mlp_out", i)
+            if hd_on:
+                m._drop_add(dh, None, g_dh, M * D, "mlp_out", i)
+            else:
+                m._path_add(dh, None, g_dh, i, 1)
             L("eav_sp_absmax", g_dh, M, D, D, s_dh2, st)
         # fc2: h_out = h_mid + act.W2^T + b2.  max|dh| is already in b_dh2 (left there by the producer of dh); every
         # conversion pass also yields the bias gradient of its tensor.  (fused_dh: the layer above's LayerNorm backward
         # already wrote these planes and the bias-gradient partials - only the top layer's dh comes from the head)
-        if not (fdh and i < c.layers - 1):
+        if not fdh_top:
             to_planes_bias(g_dh, M, D, s_dh2, ws.dhp, gp(f"{Lk}.mlp.fc2.bias"))
         wgrad_sp(ws.dhp, s_dh2, ws.actp[i], s_act, gp(f"{Lk}.mlp.fc2.weight"), D, FF, M)
         wpl, wsl = wp.get(f"fc2{i}", transposed=True)
@@ -672,8 +711,11 @@ class SplitLayers:
               1, P(part), M, D, b_dh1, st)
             m._reduce_ln(part, ws.np_ln, gp(f"{Lk}.layernorm_after.weight"), gp(f"{Lk}.layernorm_after.bias"), s.reduce)
             # o_proj
-            if hd_on:
-                m._drop_add(dh, None, g_dh, M * D, "attn_out", i)
+            if hd_on or dp_on:
+                if hd_on:
+                    m._drop_add(dh, None, g_dh, M * D, "attn_out", i)
+                else:
+                    m._path_add(dh, None, g_dh, i, 0)
                 L("eav_sp_absmax", g_dh, M, D, D, s_dh1, st)
             to_planes_bias(g_dh, M, D, s_dh1, ws.dhp2, gp(f"{Lk}.attention.o_proj.bias"))
         wgrad_sp(ws.dhp2, s_dh1, ws.aop[i], s_ao, gp(f"{Lk}.attention.o_proj.weight"), D, D, M)
@@ -713,7 +755,7 @@ class SplitLayers:
         wgrad_sp(ws.dqkvp, b_dqkv, ws.y1p[i], s_y1, gp(f"{Lk}.attention.q_proj.weight"), 3 * D, D, M)
         wpl, wsl = wp.get(f"qkv{i}", transposed=True)
         # the gradient w.r.t. this layer's input is the next (lower) layer's dh: leave its max in that layer's slot
-        if fdh and i > 0:
+        if fdh_bot:
             gemm_sp(P(ws.dqkvp), b_dqkv, wpl, wsl, dy, M, D, 3 * D, D, amax=b_dy1, blockmax=False)
             below = Lk.rsplit(".", 1)[0] + f".{i - 1}"
             self.ln_bwd_planes(dy, P(ws.hs[i]), w(f"{Lk}.layernorm_before.weight"), stp, stp + 4 * M, dh,

@@ -128,11 +128,15 @@ class FineTuneBase:
     #   patch_dropout     0 <= p < 1, timm's PatchDropout (Encoder.patch_dropout): every sample of an unfrozen epoch keeps a
     #                     random max(1, int(P (1 - p))) of its P patch tokens - a regulariser that shortens the step.  Any
     #                     problem type.  The frozen phase (its feature cache, its launches) and _evaluate see every token.
+    #   drop_path         0 <= r < 1, stochastic depth, timm's DropPath (Encoder.drop_path_rate): every sample of an unfrozen
+    #                     epoch drops the whole residual branch of layer i with probability r i / (layers - 1).  Any problem
+    #                     type, any geometry, with patch_dropout too.  The frozen phase and _evaluate drop nothing.
     label_smoothing = 0.0
     class_weights = None
     mixup_alpha = 0.0
     augment_seed = 0
     patch_dropout = 0.0
+    drop_path = 0.0
     # Learning-rate options, set the same way; with all of them at their defaults _enter_phase does what it always did
     # and the optimiser keeps its one-launch-per-run path:
     #   lr_scheduler_type     "constant", "constant_with_warmup", "linear" or "cosine" (optim.LRSchedule, the lambdas of
@@ -218,6 +222,10 @@ class FineTuneBase:
         if not 0.0 <= pd < 1.0:
             raise ValueError(f"patch_dropout {self.patch_dropout!r} must satisfy 0 <= p < 1")
         self.model.patch_dropout = 0.0 if freeze else pd
+        dp = float(self.drop_path)
+        if not 0.0 <= dp < 1.0:
+            raise ValueError(f"drop_path {self.drop_path!r} must satisfy 0 <= r < 1")
+        self.model.drop_path_rate = 0.0 if freeze else dp
 
     def _epoch_plan(self, batches):
         """The augmentation plan of a training epoch over `batches` (None: plain gathers)."""

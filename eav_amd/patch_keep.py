@@ -66,7 +66,7 @@ class EncoderPatchKeep:
 
     def begin(self, ws, B, dev):
         """Fill ws.keep / ws.inv for the forward in flight: from the explicit table (one launch: its inverse), else by the
-        plan kernel after advancing the device forward counter (two launches)."""
+        plan kernel from the device forward counter (which the encoder advances, once per forward, for all its generators)."""
         m, c = self.m, self.m._geo
         P, K = c.grid_npatch, c.npatch
         if self.table is not None:
@@ -79,7 +79,6 @@ class EncoderPatchKeep:
             return
         ws.keep = ws.keep_own
         cnt = m._counter(dev)
-        m._call("eav_counter_inc", cnt.data_ptr(), m._st)
         m._call("eav_patch_keep_plan", ws.keep.data_ptr(), ws.inv.data_ptr(), B, P, K, plan_seed(m.dropout_seed),
                 cnt.data_ptr(), None, m._st)
 

@@ -25,7 +25,8 @@ the MLP and the attention outputs / log-sum-exps; the fused attention never mate
 This module is the public model, its loading and saving, the workspace and the two launch sequences.  The rest of the encoder:
 encoder_config (what needs no device), encoder_layers (the two layer schedules), encoder_head (the classification head and
 Encoder.head), encoder_dropout (the dropout sites and generator), encoder_outputs (output_attentions / output_hidden_states /
-attention rollout), patch_keep (patch dropout: the plan of who is kept and its tables).
+attention rollout), patch_keep (patch dropout: the plan of who is kept and its tables), encoder_drop_path (stochastic depth: the
+rates and the per-sample scale table).
 """
 from __future__ import annotations
 
@@ -42,6 +43,7 @@ from .criteria import BCEWithLogitsLoss, CrossEntropyLoss, MSELoss
 from .encoder_config import (HEAD_MAX_CLASSES, MAX_TOKENS, PROBLEM_TYPES, _check_single_label,  # noqa: F401 (re-exported)
                              ast_length_geometry, config_from_hf, config_to_hf, interpolated_geometry, make_config,
                              normalise_key, param_shapes, patch_dropout_geometry, rank_dropout_seed, resolve_problem_type)
+from .encoder_drop_path import EncoderDropPath
 from .encoder_dropout import EncoderDropout
 from .encoder_head import EncoderHead, _HeadFn
 from .encoder_layers import Fp32Layers, SplitLayers
@@ -185,6 +187,13 @@ class Encoder(KernelModule):
         # default) and eval mode launch exactly what they always did.
         self.patch_dropout = 0.0
         self._patch_keep = EncoderPatchKeep(self)
+        # Stochastic depth (timm.layers.DropPath, scale_by_keep), 0 <= r < 1: in training mode sample b drops the whole residual
+        # branch of layer i with probability p_i = r i / (layers - 1), both branches with independent draws, the kept ones
+        # scaled by 1 / (1 - p_i) (encoder_drop_path.py, csrc/drop_path.hip).  A per-sample mask has no token layout: it runs at
+        # every geometry, with patch dropout too.  0 (the default), eval mode and every layer with p_i = 0 (always layer 0)
+        # launch exactly what they always did.
+        self.drop_path_rate = 0.0
+        self._droppath = EncoderDropPath(self)
         # HF's model(..., output_attentions=, output_hidden_states=): these attributes are the defaults of those two keywords
         # of __call__ (HF: config.output_attentions / config.output_hidden_states; from_pretrained copies them from config.json)
         self.output_attentions = False
@@ -373,6 +382,9 @@ class Encoder(KernelModule):
                 raise NotImplementedError("dropout together with patch dropout is not implemented (DESIGN.md section 11): the "
                                           "dropout sites are laid out for cfg.ntok tokens")
             geo = patch_dropout_geometry(geo if geo is not None else c, pd)
+        if self._droppath.active() and self.dropout_active():       # (validates drop_path_rate whatever the mode)
+            raise NotImplementedError("dropout together with drop path is not implemented (DESIGN.md section 11): stock "
+                                      "checkpoints have hidden_dropout_prob = attention_probs_dropout_prob = 0")
         self._active_geo = geo
         x = x.contiguous().float()
         self._ensure_flat()
@@ -477,6 +489,36 @@ class Encoder(KernelModule):
             raise _lib.EavError("Encoder.last_patch_keep: the most recent forward dropped no patches")
         return ws.keep.clone()
 
+    def drop_path_rates(self):
+        """The drop probability of every layer's two residual branches under drop_path_rate: float32 [layers],
+        torch.linspace(0, r, layers) formed in float64 and rounded once."""
+        return self._droppath.rates()
+
+    def set_drop_path_masks(self, mask):
+        """Testing hook, the twin of set_dropout_masks: an explicit keep table uint8 [layers, 2, B] on the model's device
+        ([i, 0] the attention branch of layer i, [i, 1] its MLP branch; rows of layers with p_i = 0 are not read) instead of
+        the generated draws; None returns to them.  Validated here, once - call it outside a capture."""
+        self._droppath.set_masks(mask)
+
+    def generated_drop_path(self, B, counter, seed=None):
+        """The keep table uint8 [layers, 2, B] the generator draws in the forward whose counter value is `counter` (the
+        value forward_counter() returns after that forward); rows of layers with p_i = 0 are all ones."""
+        return self._droppath.generated(B, counter, seed)
+
+    def last_drop_path(self):
+        """The scale table float32 [layers, 2, B] (a copy) of the most recent forward, which must have run with drop path:
+        0 where a branch was dropped, 1 / (1 - p_i) where it was kept, 1 in the rows of layers with p_i = 0."""
+        ws = self._ws
+        if ws is None or getattr(ws, "dpath", None) is None:
+            raise _lib.EavError("Encoder.last_drop_path: the most recent forward ran without drop path")
+        return ws.dpath.table.clone()
+
+    def _path_add(self, y, resid, out, layer, branch):
+        """out = resid + s o y with the per-sample scales of (layer, branch); resid None: the gate alone, the site's backward."""
+        ws = self._ws
+        self._call("eav_drop_path_add", y, resid, out, ws.dpath.row(layer, branch), ws.B, self._geo.ntok * self._geo.hidden,
+                   self._st)
+
     def _drop_add(self, y, resid, out, n, kind, layer=0):
         """out = resid + Dropout(y) at the hidden-dropout site (kind, layer); resid None: the gate alone, the site's backward."""
         self._call("eav_tf_dropout_add", y, resid, out, n, *self._ws.drop.site(kind, layer), self._st)
@@ -537,8 +579,8 @@ class Encoder(KernelModule):
         if full_backward:
             ws.dh, ws.dy, ws.dao = f(M, D), f(M, D), f(M, D)
             ws.dact, ws.dqkv = f(M, FF), f(M, 3 * D)
-            if c.hidden_dropout > 0.0:        # dh o M / (1 - p): what enters the fc2 / o_proj gradient products
-                ws.dhd = f(M, D)
+            # dh o M / (1 - p): what enters the fc2 / o_proj gradient products (drop path allocates its own on first use)
+            ws.dhd = f(M, D) if c.hidden_dropout > 0.0 else None
             if not ws.fused:
                 ws.dP = torch.zeros(B * H, N, ldn, dtype=torch.float32, device=dev)
             ws.demb = f(B * c.npatch, D)
@@ -690,11 +732,16 @@ class Encoder(KernelModule):
         full = self._want_full
         lay = self._split if self.precision == "split" else self._fp32     # (an unknown precision: Fp32Layers.gemm_name raises)
         ws = self._workspace_for(B, x.device, full, lay)
+        dropped = self._grid(c) is not None      # patch dropout: the three embedding launches in their _keep forms
+        # the device forward counter advances once per forward, whichever generators read it (config dropout, the
+        # patch-dropout plan, drop path)
+        if self._dropgen.generates() or (dropped and self._patch_keep.table is None) or self._droppath.generates():
+            L("eav_counter_inc", self._counter(x.device).data_ptr(), st)
         drop = self._dropgen.begin(ws, B, x.device)
+        self._droppath.begin(ws, B, x.device)
         lay.begin_forward(ws, x.device, full)
         pre = c.prefix
         # patch embedding: im2col rows x projection weight -> token rows [nextra:], then cls/dist + positions
-        dropped = self._grid(c) is not None      # patch dropout: the three embedding launches in their _keep forms
         if dropped:
             self._patch_keep.begin(ws, B, x.device)
             L("eav_im2col_keep", P(x), P(ws.col), P(ws.keep), B, c.C, c.H, c.W, c.patch, c.sy, c.sx, c.transposed, c.npatch, st)

@@ -719,6 +719,21 @@ int eav_embed_finish_keep(float* h, const float* cls, const float* dist, const f
                           int D, int nextra, void* stream);
 int eav_embed_bwd_keep(const float* dh, float* dpos, float* demb, const int* inv, int B, int P, int K, int D, int nextra,
                        void* stream);
+/* Stochastic depth (timm.layers.DropPath, scale_by_keep; csrc/drop_path.hip): in training mode sample b drops the whole
+ * residual branch of layer i with probability p_i = rate * i / (L - 1) (formed in double, rounded once to float; 0 for
+ * L = 1), kept branches are scaled by 1 / (1 - p_i).  Both kernels are in gather form - no atomics, the same bits on every
+ * run - and read nothing back, so a captured step may hold them.
+ * eav_drop_path_plan fills scale, float [L, 2, B]: row 2 i the attention branch of layer i, row 2 i + 1 its MLP branch.  Rows
+ * with p_i == 0 hold 1.0.  Elsewhere scale[r][b] is 1 / (1 - p_i) where sample b is kept and 0 where it is dropped: kept means
+ * eav_hash32(seed + (r << 40) + 2 * *counter, b) * 2^-24 >= p_i (counter NULL: no counter term; seed is the site seed of row
+ * 0, consecutive rows have consecutive site ids), or keep[r][b] != 0 where keep (optional, uint8 [L, 2, B]) is given.
+ * eav_drop_path_add: out[b, :] = resid[b, :] + y[b, :] * scale_row[b] over B samples of per_sample floats (per_sample % 4 == 0,
+ * 16-byte aligned pointers; resid NULL: out = y * s, the gate of the backward; out may be y, not resid).  The product is
+ * rounded, then added - float32 resid + y * s bit for bit, signed zeros included; NaN / Inf in a dropped y give NaN. */
+int eav_drop_path_plan(float* scale, int L, int B, double rate, uint64_t seed, const uint64_t* counter, const uint8_t* keep,
+                       void* stream);
+int eav_drop_path_add(const float* y, const float* resid, float* out, const float* scale_row, int B, int64_t per_sample,
+                      void* stream);
 /* ViT position table at another patch grid (HF ViTEmbeddings.interpolate_pos_encoding: F.interpolate(mode="bicubic",
  * align_corners=False), no antialiasing): pos [nextra + g*g, D] -> out [nextra + ny*nx, D], the first nextra rows copied,
  * the patch rows out = (Wy (x) Wx) pos.  iy / ix [n_out][4] are the source indices of the four taps of every output index

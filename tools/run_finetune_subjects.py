@@ -12,6 +12,7 @@
                                                      (the regularisers of finetune.FineTuneBase; vision: --hflip)
     python tools/run_finetune_subjects.py audio --patch-dropout 0.5   (the unfrozen epochs train on half of every clip's patches:
                                                                        608 tokens instead of 1214)
+    python tools/run_finetune_subjects.py vision --drop-path 0.1      (stochastic depth in the unfrozen epochs, timm's DropPath)
     python -m torch.distributed.run --nproc-per-node 8 tools/run_finetune_subjects.py audio ...
 
 Every subject is one `AudioModelTrainer` / `ImageClassifierTrainer` run with the reference's hyper-parameters
@@ -110,6 +111,9 @@ def main():
     ap.add_argument("--patch-dropout", type=float, default=0.0, metavar="P", help="every sample of an unfrozen epoch keeps a "
                     "random max(1, int(patches x (1 - P))) of its patch tokens, timm's PatchDropout (trainer.patch_dropout); "
                     "0 <= P < 1")
+    ap.add_argument("--drop-path", type=float, default=0.0, metavar="R", help="stochastic depth: every sample of an unfrozen "
+                    "epoch drops the residual branches of layer i with probability R i / (layers - 1), timm's DropPath "
+                    "(trainer.drop_path); 0 <= R < 1")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     if args.grad_accum < 1 or (args.max_grad_norm is not None and not args.max_grad_norm > 0):
@@ -120,6 +124,8 @@ def main():
         ap.error("--warmup-ratio takes R in [0, 1] and --layer-decay D in (0, 1]")
     if not 0.0 <= args.patch_dropout < 1.0:
         ap.error("--patch-dropout takes P with 0 <= P < 1")
+    if not 0.0 <= args.drop_path < 1.0:
+        ap.error("--drop-path takes R with 0 <= R < 1")
     audio = args.kind == "audio"
     if audio and args.hflip:
         ap.error("--hflip is a vision option")
@@ -175,6 +181,7 @@ def main():
                 tr.label_smoothing, tr.class_weights = args.label_smoothing, args.class_weights
                 tr.mixup_alpha, tr.augment_seed = args.mixup_alpha, args.augment_seed
                 tr.patch_dropout = args.patch_dropout
+                tr.drop_path = args.drop_path
                 if audio:
                     tr.time_mask, tr.freq_mask = args.time_mask, args.freq_mask
                 else:
