@@ -43,6 +43,7 @@ SIGNATURES = {
     "eav_eegnet_fir_fwd_fft": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_eegnet_fir_wgrad_fft": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_eegnet_fir_wgrad_indexed": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "eav_eegnet_fir_fft_plan": [_i, _i, _i, _i, _p],
     "eav_eegnet_fir_xtab_build": [_p, _i, _i, _i, _i, _p, _p],
     "eav_eegnet_fir_wgrad_fft_xtab": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "eav_eegnet_dw_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
@@ -259,7 +260,7 @@ SCHED_WORDS = 4
 
 # test / tuning overrides (include/eav_hip_tuning.h): process-global, never called by the package
 TUNING = {"eav_gemm_sp_set_tile": [_i], "eav_gemm_sp_set_splitk": [_i], "eav_sp_set_convert_blocks": [_i],
-          "eav_attn_sp_set_nw4_above": [_i]}
+          "eav_attn_sp_set_nw4_above": [_i], "eav_eegnet_fir_fft_set_grid_cap": [_i]}
 
 # Comparison-only kernels (include/eav_hip_extras.h, `make BENCH_EXTRAS=1` -> libeav_extras.so): bench.py's literal-bf16 leg.
 EXTRAS_PATH = os.path.join(_HERE, "libeav_extras.so")

@@ -37,6 +37,7 @@
 
 #include "eav_common.h"
 #include "../../include/eav_hip.h"
+#include "../../include/eav_hip_tuning.h"
 
 namespace {
 
@@ -863,14 +864,19 @@ __global__ __launch_bounds__(1024) void fir_fft_wgrad_finish_tab_kernel(const fl
 // weight gradient: workgroups of 8 waves, at most one per CU, over `items` groups of 8 units: the smallest grid that needs
 // no more rounds than 256 workgroups would (13920 units = 1680 + 60 groups: 249 workgroups x 7 rounds; unpacked, 1800
 // groups took 8 rounds on 225)
+// (the 256 of both grids is one workgroup per CU; eav_eegnet_fir_fft_set_grid_cap - tests and tuning only - lowers it so
+// that the multi-round paths of both kernels are reached at small shapes)
+int g_grid_cap = 0;
+int grid_cap() { return g_grid_cap > 0 ? g_grid_cap : 256; }
 int fft_grid(int items) {
-  if (items <= 256) return std::max(1, items);
-  const int rounds = cdiv(items, 256);
+  const int cap = grid_cap();
+  if (items <= cap) return std::max(1, items);
+  const int rounds = cdiv(items, cap);
   return cdiv(items, rounds);
 }
 int wgrad_groups(const Units& q) { return cdiv(q.nmain, 8) + cdiv(q.npk, 8); }
 // forward: one workgroup of NWF waves per CU while the units last (the kernel deals them round by round, then slot by slot)
-int fwd_grid(const Units& q) { return std::min(256, std::max(1, cdiv(q.total(), NWF))); }
+int fwd_grid(const Units& q) { return std::min(grid_cap(), std::max(1, cdiv(q.total(), NWF))); }
 // The sizing exports do not know klen, hence not whether the tails pack: they take the larger of the two lists (klen = 1
 // packs whenever any filter does, klen = NF never).
 constexpr int K_PACKS = 1, K_NEVER = NF;
@@ -878,6 +884,25 @@ constexpr int K_PACKS = 1, K_NEVER = NF;
 }  // namespace
 
 extern "C" int eav_eegnet_fir_fft_max_taps(void) { return MAXK; }
+
+// test / tuning only (include/eav_hip_tuning.h): the most workgroups either kernel launches; n <= 0 restores 256.  The
+// sizing exports and the plan below follow it, so buffers sized after the call fit the launches after it.
+extern "C" int eav_eegnet_fir_fft_set_grid_cap(int n) {
+  g_grid_cap = n > 0 ? n : 0;
+  return 0;
+}
+
+// The unit list and both grids for a shape, from the very functions the launchers call (host only, no GPU needed):
+// out[0..9) = npair, nmb, nmain, ntail, npk, t0t, forward workgroups, weight-gradient groups, weight-gradient workgroups
+extern "C" int eav_eegnet_fir_fft_plan(int B, int C, int S, int klen, int* out) {
+  EAV_REQUIRE(out && B > 0 && C > 0 && S > 0, "eav_eegnet_fir_fft_plan: bad arguments");
+  EAV_REQUIRE(klen >= 1 && klen <= MAXK, "eav_eegnet_fir_fft_plan: kernLength %d outside [1,%d]", klen, MAXK);
+  const Units q = fft_units(B, C, S, klen);
+  const int groups = wgrad_groups(q);
+  const int v[EAV_FIR_FFT_PLAN_FIELDS] = {q.npair, q.nmb, q.nmain, q.ntail, q.npk, q.t0t, fwd_grid(q), groups, fft_grid(groups)};
+  std::copy(v, v + EAV_FIR_FFT_PLAN_FIELDS, out);
+  return EAV_OK;
+}
 
 // stat_part rows (16 floats each: 8 sums, 8 sums of squares) the forward writes - one per wave, and zeros in those a
 // shorter unit list leaves without a wave

@@ -92,6 +92,12 @@ int eav_eegnet_fir_fwd_fft(const float* x, const int64_t* xidx, const float* w1,
 int64_t eav_eegnet_fir_wgrad_fft_ws_floats(int B, int C, int S);
 int eav_eegnet_fir_wgrad_fft(const float* x, const int64_t* xidx, const float* y1, const float* g1, const float* bn_params,
                              float* ws, float* dW, int B, int C, int S, int klen, void* stream);
+/* The unit list and the grids of the two launchers above for a shape, from the functions they call themselves (host only):
+ * out[EAV_FIR_FFT_PLAN_FIELDS] = npair (electrode pairs), nmb (whole-segment blocks per row), nmain (= B npair nmb units),
+ * ntail (row tails that share transforms, 0: none), npk (= ceil(ntail / 2) packed units), t0t (first output of a packed
+ * tail), the forward's workgroups (12 waves each), the weight gradient's groups of 8 units and its workgroups. */
+#define EAV_FIR_FFT_PLAN_FIELDS 9
+int eav_eegnet_fir_fft_plan(int B, int C, int S, int klen, int* out);
 /* The train-mode weight gradient without its y1 read, for a data set that stays in HBM.  y1 = firstConv(x; w1), so its share
  * of dW is a function of x and w1:  dW[f,k] = scale_f (G[f,k] - (m1_f - mean_f invstd_f m2_f) X1[k] - invstd_f m2_f
  * sum_j w1[f,j] A[j,k]),  G = the eval-mode walk on the raw g1,  A = sum_b A_b,  X1 = sum_b X1_b,

@@ -9,6 +9,7 @@ int eav_gemm_sp_set_tile(int which);   /* 0 heuristic, 1 = 128x128 tiles, 2 = 25
 int eav_gemm_sp_set_splitk(int slices);  /* eav_gemm_sp_splitk: forced slice count (0 = the plan; ws must hold it) */
 int eav_sp_set_convert_blocks(int n);  /* resident-block cap of eav_sp_convert (default 512; 0 = one block per tile) */
 int eav_attn_sp_set_nw4_above(int n);   /* 128-row (4-wave) attention workgroups for N > n (default 128); n < 0: the software-pipelined forward from N >= -n (default 512) */
+int eav_eegnet_fir_fft_set_grid_cap(int n);   /* most workgroups of eav_eegnet_fir_fwd_fft / _wgrad_fft(_xtab) (default 256; n <= 0 restores it); eav_eegnet_fir_fft_plan, eav_eegnet_fir_fwd_fft_nparts and eav_eegnet_fir_wgrad_fft_ws_floats follow it: size buffers after setting it */
 #ifdef __cplusplus
 }
 #endif

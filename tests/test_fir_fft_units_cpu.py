@@ -3,7 +3,8 @@ definition: rows of S samples in blocks of 704, a tail of Lt = S - 704 (nblk - 1
 transform with another tail iff Lt + K - 1 <= 512; main units first, packed tails (2 p, 2 p + 1 of the flattened
 sample x pair index) behind them.  Forward: up to 256 workgroups of 12 waves, nunits // nwaves full rounds, extra e to
 workgroup e % nWG, wave slot e // nWG; wave slot w sits on SIMD w % 4.  Weight gradient: groups of 8 units of one kind,
-the smallest grid that needs no more rounds than 256 workgroups would.  No GPU and no library needed."""
+the smallest grid that needs no more rounds than 256 workgroups would.  No GPU needed; one test compares the restatement
+with eav_eegnet_fir_fft_plan, the rule as the launchers apply it."""
 import numpy as np
 import pytest
 
@@ -72,6 +73,24 @@ def test_every_block_is_covered_once_and_halves_do_not_overlap(B, C, S, K):
     assert (seen == 1).all()
     # whatever the deal of the forward, every unit is run once
     fwd_deal(len(us))
+
+
+@pytest.mark.parametrize("B,C,S,K", SHAPES)
+def test_restatement_is_the_rule_the_launchers_use(B, C, S, K):
+    """eav_eegnet_fir_fft_plan fills its fields from the functions the launchers call: the numpy restatement above must
+    give the same unit list and the same two grids"""
+    import ctypes
+    from eav_amd import _lib
+    out = (ctypes.c_int * 9)()
+    _lib.call("eav_eegnet_fir_fft_plan", B, C, S, K, out)
+    npair, nmb, nmain, ntail, npk, t0t, fwd_wgs, groups, wg_wgs = out
+    us, packs = units(B, C, S, K)
+    nblk = -(-S // LB)
+    assert (npair, nmb) == ((C + 1) // 2, nblk - 1 if packs else nblk) and t0t == nmb * LB
+    assert nmain == sum(1 for u in us if len(u) == 1 and u[0][3] == 0 and u[0][2] < nmb)
+    assert ntail == (B * npair if packs else 0) and npk == len(us) - nmain == (ntail + 1) // 2
+    assert fwd_wgs == fwd_deal(len(us)).shape[0]
+    assert groups == -(-nmain // 8) + -(-npk // 8) and wg_wgs == wgrad_rounds(nmain, npk)[0]
 
 
 def test_packing_condition_at_its_edges():
