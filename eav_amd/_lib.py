@@ -79,6 +79,9 @@ SIGNATURES = {
     "eav_scale_ranges": [_p, _i, _i64, _p, _p],
     "eav_adam_jobs_begin": [_p, _i, _p, _i, _p, _i, _i64, _i64, _d, _d, _f, _f, _p],
     "eav_adam_step_jobs": [_p, _i, _i64, _f, _f, _f, _i, _p, _p],
+    "eav_adam_jobs_begin_avg": [_p, _i, _p, _i, _p, _i, _i64, _i64, _d, _d, _f, _f, _p, _i, _d, _i, _i64, _i64, _p],
+    "eav_adam_step_jobs_avg": [_p, _p, _i, _i64, _f, _f, _f, _i, _p, _p, _p],
+    "eav_swap_jobs": [_p, _p, _i, _i64, _p],
     "eav_counter_inc": [_p, _p],
     "eav_counter_inc4": [_p, _p, _p, _p, _p],
     "eav_step_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
@@ -257,6 +260,10 @@ EXPORTS = sorted(list(SIGNATURES) + list(PLAIN))
 # int64 words of a job row of eav_adam_step_jobs and of its schedule record (EAV_ADAM_JOB_WORDS, EAV_ADAM_SCHED_WORDS)
 JOB_WORDS = 10
 SCHED_WORDS = 4
+# the averaging record (EAV_ADAM_AVG_WORDS), its kinds (EAV_AVG_EMA / SWA) and modes (EAV_AVG_SKIP / COPY / LERP)
+AVG_WORDS = 4
+AVG_KINDS = ("ema", "swa")
+AVG_SKIP, AVG_COPY, AVG_LERP = 0, 1, 2
 
 # test / tuning overrides (include/eav_hip_tuning.h): process-global, never called by the package
 TUNING = {"eav_gemm_sp_set_tile": [_i], "eav_gemm_sp_set_splitk": [_i], "eav_sp_set_convert_blocks": [_i],

@@ -9,6 +9,7 @@ audio.py / vision.py keep the reference's constructors, method signatures and co
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import shutil
 
@@ -18,7 +19,7 @@ import torch
 from . import _lib
 from .augment import BatchAugment, EpochPlan
 from .criteria import BCEWithLogitsLoss, CrossEntropyLoss, MSELoss
-from .optim import FusedAdam, LRSchedule
+from .optim import FusedAdam, LRSchedule, WeightAveraging
 from .runtime import DeviceLoader
 from .transformer import PROBLEM_TYPES, Encoder
 
@@ -154,6 +155,24 @@ class FineTuneBase:
     layer_decay = 1.0
     decay_bias_and_norm = True
     _lr_options_applied = False         # the optimiser's groups / schedule were rebuilt by _apply_lr_options
+    # Weight averaging, set the same way (optim.WeightAveraging, FusedAdam.set_averaging - the averages are updated inside
+    # the optimiser step's own two launches):
+    #   weight_averaging        None, "ema" (timm's ModelEma, AveragedModel with get_ema_multi_avg_fn) or "swa"
+    #   ema_decay, ema_warmup   the EMA's decay; True: min(decay, (1 + n) / (10 + n)) while few steps have been averaged
+    #   averaging_start_epoch   epochs - counted over the train() calls since averaging was attached - trained before the
+    #                           first averaging step (converted to optimiser steps; gradient_accumulation_steps counts groups)
+    #   averaging_every         average every k-th optimiser step from there
+    # When set, _evaluate runs on the averaged weights - the epoch line and `outputs_test` come from them; in the frozen
+    # phase only the head differs, so the feature cache stays valid - and save_pretrained writes them.  Training itself
+    # is not perturbed: the trained parameters are bit-equal to a run without the option (the multi-tensor step it switches
+    # to forms the bias corrections on the device, the default step on the host - the same fp64 expressions, rounded to
+    # fp32 - and the element update is one function).  Attached by the first train()
+    # call that sees the option and kept across the phases.  With None nothing of this is entered.
+    weight_averaging = None
+    ema_decay = 0.999
+    ema_warmup = False
+    averaging_start_epoch = 0
+    averaging_every = 1
 
     _criterion_key = (0.0, None)        # (label_smoothing, class weights) loss_fn was built with
     _augmented_epochs = 0               # epochs planned so far: the `epoch` of BatchAugment.plan_epoch
@@ -260,12 +279,14 @@ class FineTuneBase:
             return DeviceLoader(x, y, self.batch_size, shuffle, self.device)
         return DeviceLoader(x, y, self.batch_size, shuffle, self.device, label_dtype=torch.float32)
 
-    def save_pretrained(self, save_directory):
+    def save_pretrained(self, save_directory, averaged=True):
         """The fine-tuned model as an HF directory (Encoder.save_pretrained), with the preprocessor_config.json of the
         directory it was loaded from, if that had one.  An audio trainer built with max_length saves a model of that
-        length (the position table fitted to it)."""
+        length (the position table fitted to it).  Under `weight_averaging` the averaged weights are written;
+        averaged=False writes the last iterate."""
         length = getattr(self, "max_length", None)
-        self.model.save_pretrained(save_directory, **({} if length is None else {"max_length": length}))
+        with self._averaged() if averaged else contextlib.nullcontext():
+            self.model.save_pretrained(save_directory, **({} if length is None else {"max_length": length}))
         src = os.path.join(self.model.source_dir or "", "preprocessor_config.json")
         if self.model.source_dir and os.path.exists(src):
             dst = os.path.join(save_directory, "preprocessor_config.json")
@@ -338,6 +359,30 @@ class FineTuneBase:
         opt.set_schedule(self._schedule_for(epochs))
         self._lr_options_applied = True
 
+    def _apply_weight_averaging(self):
+        """Attach what the weight-averaging options describe (once: the step count and the averages carry over the
+        phases; again when an option changed), or detach it."""
+        opt = self.optimizer
+        if self.weight_averaging is None:
+            if opt.averaging is not None:
+                opt.set_averaging(None)
+                opt.multi_tensor = self._lr_options_applied
+            return
+        start = int(self.averaging_start_epoch)
+        if start < 0:
+            raise ValueError(f"averaging_start_epoch {self.averaging_start_epoch!r} must be >= 0")
+        k_acc = max(1, int(self.gradient_accumulation_steps))
+        steps_per_epoch = -(-len(self.train_dataloader) // k_acc)
+        want = WeightAveraging(self.weight_averaging, self.ema_decay, self.ema_warmup,
+                               start * steps_per_epoch + 1 if start else 0, self.averaging_every)
+        if opt.averaging != want:
+            opt.set_averaging(want)
+        opt.multi_tensor = True
+
+    def _averaged(self):
+        """The context _evaluate and save_pretrained run in: the averaged weights swapped in, when there are any."""
+        return self.optimizer.averaged_parameters() if self.optimizer.averaging is not None else contextlib.nullcontext()
+
     def _lr_text(self):
         """", lr x" for the epoch line under a non-constant schedule (one read-back per epoch), else ""."""
         if self.lr_scheduler_type == "constant" or self.optimizer.last_lr is None:
@@ -350,6 +395,8 @@ class FineTuneBase:
             group['lr'] = lr
         if self._lr_options_active() or self._lr_options_applied:
             self._apply_lr_options(lr, epochs)
+        if self.weight_averaging is not None or self.optimizer.averaging is not None:
+            self._apply_weight_averaging()
         self.optimizer.max_grad_norm = self.max_grad_norm
         trainable_head = {id(p) for p in self.model.classifier.parameters()}
         for p in self.model.parameters():
@@ -493,7 +540,7 @@ class FineTuneBase:
                            torch.float32 if self.problem_type == "regression" else torch.int32)
         self._batch_loss = torch.zeros((), dtype=torch.float32, device=self.device)
         spans, pos = [], 0
-        with torch.no_grad():
+        with self._averaged(), torch.no_grad():
             for k, idx in enumerate(dl.index_batches()):
                 if fc is not None and fc["have_test"]:
                     tb = dl.gather_labels(idx)

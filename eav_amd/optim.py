@@ -20,9 +20,14 @@ Learning-rate options (csrc/adam_jobs.hip): ``FusedAdam(multi_tensor=True)`` upd
 each with its own ``lr`` / ``weight_decay`` and step count - in two launches over a device job table, and
 ``FusedAdam.set_schedule(LRSchedule(...))`` scales the rates by ``transformers.get_scheduler``'s factors, evaluated on the
 device from a device-resident step count.  Off by default: the default step launches what it always did.
+
+Weight averaging (csrc/adam_jobs.hip): ``FusedAdam.set_averaging(WeightAveraging("ema" | "swa", ...))`` keeps an
+exponential or equal-weight average of every parameter, updated inside the multi-tensor step's own two launches from the
+parameter the step has in registers; ``averaged_parameters()`` swaps the averages in for evaluation.
 """
 from __future__ import annotations
 
+import contextlib
 from operator import itemgetter
 
 import torch
@@ -174,11 +179,69 @@ class LRSchedule:
 _CONSTANT = LRSchedule("constant")
 
 
+class WeightAveraging:
+    """What ``FusedAdam.set_averaging`` attaches: an average of the weights kept beside them, updated by the optimiser
+    step itself.  ``s`` counts the optimiser steps since it was attached, from 1; step ``s`` is an averaging step when
+    ``s >= start_step`` and ``(s - start_step) % every == 0``.  The first averaging step copies the parameters
+    (``torch.optim.swa_utils.AveragedModel.update_parameters``' first call); every later one does
+    ``avg += c * (p - avg)`` with
+
+      kind "ema":  c = 1 - decay (``get_ema_multi_avg_fn(decay)``); ``warmup=True`` uses min(decay, (1 + n) / (10 + n))
+                   in place of decay (timm's ModelEmaV2 / tf.train.ExponentialMovingAverage warm-up),
+      kind "swa":  c = 1 / (n + 1) (``get_swa_multi_avg_fn()``): the equal-weight mean of the averaged iterates,
+
+    n = ``n_averaged``, the averaging steps so far.  ``mode_and_coefficient`` is the host float64 version, for tests and
+    printing; the optimiser evaluates the same expressions on the device from device-resident ``s`` and ``n``.
+    Parameters only: buffers (BatchNorm running statistics) are not averaged."""
+
+    KINDS = _lib.AVG_KINDS
+
+    def __init__(self, kind="ema", decay=0.999, warmup=False, start_step=0, every=1):
+        if kind not in self.KINDS:
+            raise ValueError(f"WeightAveraging: kind {kind!r}: expected one of {self.KINDS}")
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"WeightAveraging: decay {decay!r} is outside [0, 1]")
+        if int(start_step) != start_step or start_step < 0:
+            raise ValueError(f"WeightAveraging: start_step {start_step!r} must be an integer >= 0")
+        if int(every) != every or every < 1:
+            raise ValueError(f"WeightAveraging: every {every!r} must be an integer >= 1")
+        self.kind, self.decay, self.warmup = kind, float(decay), bool(warmup)
+        self.start_step, self.every = int(start_step), int(every)
+
+    @property
+    def code(self):
+        """The kind as include/eav_hip.h numbers it (EAV_AVG_EMA / EAV_AVG_SWA)."""
+        return self.KINDS.index(self.kind)
+
+    def as_dict(self):
+        return dict(kind=self.kind, decay=self.decay, warmup=self.warmup, start_step=self.start_step, every=self.every)
+
+    def mode_and_coefficient(self, s, n):
+        """("skip" | "copy" | "lerp", c as a float64) of step ``s`` (from 1) when ``n`` steps have been averaged."""
+        if s < self.start_step or (s - self.start_step) % self.every:
+            return "skip", 0.0
+        if n == 0:
+            return "copy", 1.0
+        if self.kind == "swa":
+            return "lerp", 1.0 / (float(n) + 1.0)
+        d = min(self.decay, (1.0 + float(n)) / (10.0 + float(n))) if self.warmup else self.decay
+        return "lerp", 1.0 - d
+
+    def __eq__(self, other):
+        return isinstance(other, WeightAveraging) and self.as_dict() == other.as_dict()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return (f"WeightAveraging({self.kind!r}, decay={self.decay}, warmup={self.warmup}, start_step={self.start_step}, "
+                f"every={self.every})")
+
+
 class _AdamJobTable:
     """One cached table of eav_adam_step_jobs (rows: include/eav_hip.h) with the device step counts its rows read."""
 
     def __init__(self, device, jobs, shared_step_ptr):
-        """jobs: rows over (p, g, m, v) with key (step, lr, weight decay)."""
+        """jobs: rows over (p, g, m, v) - and the average, under FusedAdam.set_averaging - with key (step, lr, weight decay)."""
         words = _lib.JOB_WORDS
         n = len(jobs)
         self.njobs = n
@@ -188,7 +251,11 @@ class _AdamJobTable:
         self.steps = [step - 1 for _, _, _, _, (step, _, _) in jobs]       # host mirror: the step each job ran last
         self.counts = torch.tensor(self.steps, dtype=torch.int64).to(device) if self.per_tensor else None
         rows = torch.zeros(n, words, dtype=torch.int64)
-        rows[:, :5] = torch.tensor([[p, p + g, p + m, p + v, numel] for p, (g, m, v), numel, _, _ in jobs], dtype=torch.int64)
+        rows[:, :5] = torch.tensor([[p, p + rel[0], p + rel[1], p + rel[2], numel] for p, rel, numel, _, _ in jobs],
+                                   dtype=torch.int64)
+        # the averages' addresses, a parallel array (eav_adam_step_jobs_avg); None without averaging
+        self.avgs = (torch.tensor([p + rel[3] for p, rel, _, _, _ in jobs], dtype=torch.int64).to(device)
+                     if len(jobs[0][_REL]) == 4 else None)
         rows[:, 5] = torch.tensor([lr for _, _, _, _, (_, lr, _) in jobs], dtype=torch.float64).view(torch.int64)
         if self.per_tensor:
             rows[:, 6] = self.counts.data_ptr() + 8 * torch.arange(n, dtype=torch.int64)
@@ -244,7 +311,25 @@ class FusedAdam(torch.optim.Optimizer):
     it per step, so a captured step() follows the schedule on every replay.  It needs - and turns on - ``multi_tensor``.
     ``last_lr`` is the 0-dim device tensor holding group 0's rate in the last step, ``(float)(lr * factor)``, never read
     back by the library.  Tables and the schedule record are created by the first step:
-    run one step eagerly before capturing, and capture again after ``set_schedule``."""
+    run one step eagerly before capturing, and capture again after ``set_schedule``.
+
+    ``set_averaging(WeightAveraging(...))`` keeps an EMA or SWA average of EVERY parameter of the optimiser
+    (``state[p]["avg"]``, present only while averaging is on; a copy of the parameter when attached; views of one flat
+    buffer laid out like the moments for a flat model, so jobs merge as before).  It needs - and turns on -
+    ``multi_tensor``; the step stays two launches, ``eav_adam_jobs_begin_avg`` and ``eav_adam_step_jobs_avg``: the count
+    of steps, ``n_averaged`` and the coefficient live in a device record, the average is formed from the parameter the
+    step holds in registers, and ``p``, ``exp_avg`` and ``exp_avg_sq`` get the bits they get without averaging.  It works
+    with ``max_grad_norm``, ``accumulate()``, a schedule and ``capturable=True`` - a captured step averages on every
+    replay; as for ``set_schedule``, run one step eagerly before capturing and capture again after ``set_averaging``.  A
+    tensor the step skips (``grad`` None, the frozen phase) keeps its average: it equals the parameter until the tensor
+    first trains, as ``AveragedModel`` over the whole model averages a constant parameter to itself.  (A tensor that
+    trained before ``start_step`` and has no gradient in the first averaging step keeps its copy from attach time.)
+    Buffers are not averaged.  ``n_averaged`` is the 0-dim device int64 tensor of the record, never read back by the
+    library.  ``with optimizer.averaged_parameters():`` swaps the averages into the parameters (one ``eav_swap_jobs``
+    launch each way, the swapped ranges recorded like a step's, so an Encoder refreshes its operand planes); it refuses
+    to nest and refuses a step() inside.  ``state_dict()`` gains an ``"averaging"`` entry (the options, ``s`` and ``n`` -
+    read back there and only there) and ``load_state_dict`` restores it with the averages; with averaging off both have
+    the shape they always had."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
                  capturable=False, *, multi_tensor=False, max_grad_norm=None):
@@ -260,6 +345,11 @@ class FusedAdam(torch.optim.Optimizer):
         self.last_lr = None
         self._sched = None              # device schedule record (include/eav_hip.h)
         self._adam_tables = {}          # _AdamJobTable by (device, jobs)
+        self.averaging = None           # WeightAveraging (set_averaging)
+        self._avg_rec = None            # device averaging record (include/eav_hip.h)
+        self._avg_flat = {}             # flat average buffers by the flat parameter buffer's address
+        self._swap_tables = {}          # (rows, avgs, njobs, nchunks, ranges, flats) of averaged_parameters, by its ranges
+        self._swapped = False           # inside averaged_parameters()
         self._dev_step = None
         # capturable: set by a caller that increments the device step count itself at the start of the step, in a launch
         # it issues anyway (GraphStep: eav_step_begin) - step() then skips its own eav_counter_inc for that one call
@@ -390,6 +480,106 @@ class FusedAdam(torch.optim.Optimizer):
         if self._sched is not None:
             self._sched[0].zero_()
 
+    # ---- weight averaging ------------------------------------------------------------------------------------------
+    def set_averaging(self, averaging):
+        """Attach a WeightAveraging (None: detach and drop the averages): every parameter gets ``state[p]["avg"]``, a copy
+        of it, and the step count ``s`` and ``n_averaged`` restart at 0.  Turns ``multi_tensor`` on; a captured step()
+        must be captured again afterwards."""
+        if averaging is not None and not isinstance(averaging, WeightAveraging):
+            raise TypeError(f"FusedAdam.set_averaging: expected a WeightAveraging or None, got {type(averaging).__name__}")
+        if self._swapped:
+            raise _lib.EavError("FusedAdam.set_averaging() inside averaged_parameters(): leave the block first")
+        params = [p for group in self.param_groups for p in group["params"]]
+        if averaging is not None and not all(p.is_cuda for p in params):
+            raise _lib.EavError("FusedAdam.set_averaging needs parameters on a ROCm device (no CPU fallback)")
+        for p in params:
+            if p in self.state:
+                self.state[p].pop("avg", None)
+        self.averaging, self._avg_rec, self._avg_flat, self._swap_tables = averaging, None, {}, {}
+        if averaging is None:
+            return
+        self.multi_tensor = True
+        self._avg_rec = torch.zeros(_lib.AVG_WORDS, dtype=torch.int64, device=params[0].device)
+        with torch.no_grad():
+            for p in params:
+                fl = getattr(p, "_eav_flat", None)
+                if fl is not None and fl[0].data_ptr() + 4 * fl[2] == p.data_ptr():
+                    buf = self._avg_flat.get(fl[0].data_ptr())
+                    if buf is None:
+                        buf = self._avg_flat[fl[0].data_ptr()] = fl[0].clone()
+                    self.state[p]["avg"] = buf[fl[2]:fl[2] + p.numel()].view(p.shape)
+                else:
+                    self.state[p]["avg"] = p.detach().clone(memory_format=torch.contiguous_format)
+
+    @property
+    def n_averaged(self):
+        """The averaging steps so far: a 0-dim device int64 tensor (None while averaging is off)."""
+        return None if self._avg_rec is None else self._avg_rec[1]
+
+    def _swap(self):
+        """p <-> avg over every parameter in one eav_swap_jobs launch; the ranges are recorded as a step records them."""
+        rows, touched = [], {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                fl = getattr(p, "_eav_flat", None)
+                if fl is not None:
+                    touched[fl[0].data_ptr()] = fl[0]
+                at = p.data_ptr()
+                rows.append([at, (self.state[p]["avg"].data_ptr() - at,), p.numel(), _flat_slack(p), None])
+        jobs = _merge_rows(rows)
+        key = tuple((at, a, numel) for at, (a,), numel, _, _ in jobs)
+        table = self._swap_tables.get(key)
+        if table is None:
+            self._swap_tables.clear()
+            dev = self._avg_rec.device
+            t = torch.zeros(len(jobs), _lib.JOB_WORDS, dtype=torch.int64)
+            t[:, 0] = torch.tensor([at for at, _, _ in key], dtype=torch.int64)
+            t[:, 4] = torch.tensor([numel for _, _, numel in key], dtype=torch.int64)
+            table = self._swap_tables[key] = (
+                t.to(dev), torch.tensor([at + a for at, a, _ in key], dtype=torch.int64).to(dev), len(jobs),
+                sum(int(_lib.plain("eav_adam_jobs_nchunks", numel)) for _, _, numel in key))
+        _lib.call("eav_swap_jobs", table[0].data_ptr(), table[1].data_ptr(), table[2], table[3], _lib.stream_ptr())
+        self._record_dirty(touched, jobs)
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """Inside the block the parameters hold the averages (and ``state[p]["avg"]`` the last iterate); on exit they are
+        swapped back, bit for bit.  For evaluating or saving the averaged model."""
+        if self.averaging is None:
+            raise _lib.EavError("FusedAdam.averaged_parameters(): averaging is off - call set_averaging first")
+        if self._swapped:
+            raise _lib.EavError("FusedAdam.averaged_parameters() does not nest: the parameters already hold the averages")
+        self._swap()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swapped = False
+            self._swap()
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.averaging is not None:
+            rec = self._avg_rec.cpu()
+            sd["averaging"] = dict(self.averaging.as_dict(), s=int(rec[0]), n=int(rec[1]))
+        return sd
+
+    def load_state_dict(self, state_dict):
+        cfg = state_dict.get("averaging")
+        super().load_state_dict({k: v for k, v in state_dict.items() if k != "averaging"})
+        params = [p for group in self.param_groups for p in group["params"]]
+        loaded = {p: self.state[p].pop("avg") for p in params if p in self.state and "avg" in self.state[p]}
+        if cfg is None:
+            self.set_averaging(None)
+            return
+        cfg = dict(cfg)
+        s, n = cfg.pop("s"), cfg.pop("n")
+        self.set_averaging(WeightAveraging(**cfg))
+        with torch.no_grad():
+            for p, avg in loaded.items():
+                self.state[p]["avg"].copy_(avg.view(p.shape))
+            self._avg_rec[:2].copy_(torch.tensor([s, n], dtype=torch.int64))
+
     # ---- what the two step paths share ----------------------------------------------------------------------------
     def _gather(self):
         """The walk over the parameters that both paths begin with.  Each tensor is updated from its view of the
@@ -400,6 +590,7 @@ class FusedAdam(torch.optim.Optimizer):
         address; the device of the gradients - None when there is nothing to update)."""
         folded = set(self._acc_key) if self._acc_folds else None      # accumulate() was called: consume the accumulator
         plan, touched, dev, flat = [], {}, None, None
+        averaging = self.averaging is not None
         for group in self.param_groups:
             rows = []
             for p in group["params"]:
@@ -418,7 +609,7 @@ class FusedAdam(torch.optim.Optimizer):
                 if fl is not None and fl[0] is not flat:        # (neighbours share their buffer: one entry, one look)
                     flat = fl[0]
                     touched[flat.data_ptr()] = flat
-                if not st:
+                if "step" not in st:        # (under set_averaging a fresh state already holds "avg")
                     self._init_state(p, st)
                 st["step"] += 1
                 if dev is None:
@@ -426,8 +617,13 @@ class FusedAdam(torch.optim.Optimizer):
                 # adjacent in all four buffers up to the 16-byte alignment padding plus declared zero padding, whose
                 # gradient and moments are zero, so the update leaves it zero
                 at = p.data_ptr()
-                rows.append([at, (g.data_ptr() - at, st["exp_avg"].data_ptr() - at, st["exp_avg_sq"].data_ptr() - at),
-                             p.numel(), 16 + 4 * getattr(p, "_eav_pad", 0), st["step"]])
+                rel = (g.data_ptr() - at, st["exp_avg"].data_ptr() - at, st["exp_avg_sq"].data_ptr() - at)
+                if averaging:               # a fifth buffer that joined rows must be adjacent in
+                    if "avg" not in st:
+                        raise _lib.EavError("FusedAdam: a parameter without an average (added after set_averaging?) - "
+                                            "call set_averaging again")
+                    rel += (st["avg"].data_ptr() - at,)
+                rows.append([at, rel, p.numel(), 16 + 4 * getattr(p, "_eav_pad", 0), st["step"]])
             plan.append((group, rows))
         return plan, touched, dev
 
@@ -444,7 +640,7 @@ class FusedAdam(torch.optim.Optimizer):
             if self._acc_folds:
                 gscale = self._clip(dev, self._acc_tables, self._acc_partials)
             else:
-                ranges = tuple((at + g, at + g, numel) for at, (g, _, _), numel, _, _ in runs)
+                ranges = tuple((at + rel[0], at + rel[0], numel) for at, rel, numel, _, _ in runs)
                 gscale = self._clip(dev, self._tables.get(dev, ranges), False)
         self._acc_reset()
         return gscale
@@ -504,11 +700,20 @@ class FusedAdam(torch.optim.Optimizer):
         sch = self.schedule if self.schedule is not None else _CONSTANT
         b1, b2 = shared[0]
         st = _lib.stream_ptr()
-        _lib.call("eav_adam_jobs_begin", table.rows.data_ptr(), table.njobs, _lib.ptr(table.counts),
-                  table.njobs if table.per_tensor else 0, self._sched.data_ptr(), sch.code, sch.num_warmup_steps,
-                  sch.num_training_steps, sch.num_cycles, float(first["lr"]), b1, b2, st)
-        _lib.call("eav_adam_step_jobs", table.rows.data_ptr(), table.njobs, table.nchunks, b1, b2, shared[1],
-                  int(shared[2]), gscale, st)
+        begin = (table.rows.data_ptr(), table.njobs, _lib.ptr(table.counts), table.njobs if table.per_tensor else 0,
+                 self._sched.data_ptr(), sch.code, sch.num_warmup_steps, sch.num_training_steps, sch.num_cycles,
+                 float(first["lr"]), b1, b2)
+        avg = self.averaging
+        if avg is None:
+            _lib.call("eav_adam_jobs_begin", *begin, st)
+            _lib.call("eav_adam_step_jobs", table.rows.data_ptr(), table.njobs, table.nchunks, b1, b2, shared[1],
+                      int(shared[2]), gscale, st)
+        else:
+            rec = self._avg_rec.data_ptr()
+            _lib.call("eav_adam_jobs_begin_avg", *begin, rec, avg.code, avg.decay, int(avg.warmup), avg.start_step,
+                      avg.every, st)
+            _lib.call("eav_adam_step_jobs_avg", table.rows.data_ptr(), table.avgs.data_ptr(), table.njobs, table.nchunks,
+                      b1, b2, shared[1], int(shared[2]), gscale, rec, st)
         self._record_dirty(touched, jobs)
 
     def _init_state(self, p, st):
@@ -530,6 +735,11 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self._swapped:
+            raise _lib.EavError("FusedAdam.step() inside averaged_parameters(): the parameters hold the averages")
+        if self.averaging is not None and not self.multi_tensor:
+            raise _lib.EavError("FusedAdam: weight averaging runs inside the multi-tensor step - multi_tensor was turned "
+                                "off after set_averaging")
         if self.capturable:
             count = self.device_step_counter()
             if self.step_counted:

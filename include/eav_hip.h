@@ -393,6 +393,36 @@ int eav_adam_jobs_begin(void* jobs, int njobs, int64_t* counts, int ncounts, voi
  * bits, whichever way a range is cut into jobs.  No atomics; results do not depend on the grid. */
 int eav_adam_step_jobs(const void* jobs, int njobs, int64_t nchunks, float beta1, float beta2, float eps, int decoupled,
                        const float* gscale, void* stream);
+/* ---- Weight averaging (EMA / SWA) inside the multi-tensor step (csrc/adam_jobs.hip) ----
+ * The averaging record is EAV_ADAM_AVG_WORDS int64 words of device memory (an enumerator, not a macro):
+ *   0 s   optimiser steps seen since averaging was attached (the caller zeroes it); the first step is s = 1
+ *   1 n   n_averaged: how many steps have entered the average
+ *   2 c | mode << 32     the fp32 coefficient of the current step (low half) and its EAV_AVG_* mode
+ *   3 unused
+ * eav_adam_jobs_begin_avg does everything eav_adam_jobs_begin does (same outputs, same bits) and, in the same workgroup,
+ * s += 1 and the mode of this step: an averaging step is s >= start_step with (s - start_step) % every == 0;
+ *   not an averaging step: EAV_AVG_SKIP, c = 0 - the averages are neither read nor written;
+ *   averaging step, n == 0: EAV_AVG_COPY, c = 1 - avg = p bit for bit (AveragedModel.update_parameters' first call);
+ *   else EAV_AVG_LERP with c = (float)(1 - d), d = decay or, avg_warmup != 0, min(decay, (1 + n) / (10 + n))  (EAV_AVG_EMA)
+ *                       or c = (float)(1 / (n + 1))                                                            (EAV_AVG_SWA)
+ * in fp64, rounded once; after a copy or lerp step n += 1. */
+enum { EAV_ADAM_AVG_WORDS = 4 };
+#define EAV_AVG_EMA 0
+#define EAV_AVG_SWA 1
+#define EAV_AVG_SKIP 0
+#define EAV_AVG_COPY 1
+#define EAV_AVG_LERP 2
+int eav_adam_jobs_begin_avg(void* jobs, int njobs, int64_t* counts, int ncounts, void* sched, int kind, int64_t warmup_steps,
+                            int64_t training_steps, double num_cycles, double report_lr, float beta1, float beta2,
+                            void* avg_record, int avg_kind, double decay, int avg_warmup, int64_t start_step, int64_t every,
+                            void* stream);
+/* eav_adam_step_jobs over the same table - p, m and v come out with its bits - plus avgs[j], the device address (int64) of
+ * job j's average range (fp32, `numel` elements, 4-byte aligned at least, 16-byte accesses where its own address allows).
+ * Mode of avg_record word 2: skip touches no average; copy stores the new p; lerp stores fmaf(c, p_new - avg, avg). */
+int eav_adam_step_jobs_avg(const void* jobs, const void* avgs, int njobs, int64_t nchunks, float beta1, float beta2, float eps,
+                           int decoupled, const float* gscale, const void* avg_record, void* stream);
+/* Exchanges the contents of the p and avgs[j] ranges of a table (words 0 and 4 of a row are read): a pure swap. */
+int eav_swap_jobs(const void* jobs, const void* avgs, int njobs, int64_t nchunks, void* stream);
 /* Batch assembly in HBM: out[i,:] = src[idx[i],:] (rows of row_elems floats) / out[i] = src[idx[i]] (labels).
  * Replaces the per-batch host->device copies of the reference loops (EEGNet_tor.py:100-101). */
 int eav_gather_rows(const float* src, const int64_t* idx, float* out, int nrows, int64_t row_elems, void* stream);

@@ -13,7 +13,14 @@ itself (nothing synchronises inside it) over the same steps.  The parameters kee
 is constant.  `--encoder` adds whole training steps of the reduced (2 layers, 64 wide) and the full ViT at B = 128 with
 the trainers' learning-rate options off and on (layer decay 0.75, no-decay split, linear schedule).
 
-usage: adam_jobs_bench.py [--encoder] [--out FILE]"""
+`--avg` times weight averaging (FusedAdam.set_averaging) on the same layout, one group, the job-table path:
+  (a) the step without averaging            eav_adam_jobs_begin + eav_adam_step_jobs                 28 B/param
+  (b) the fused averaging step              eav_adam_jobs_begin_avg + eav_adam_step_jobs_avg (EMA)   36 B/param
+  (c) (a), then torch._foreach_lerp_        the average as a separate pass over the same tensors     40 B/param
+All timed steps of (b) are lerp steps (the copy falls into the warm-up).  The spread is reported as min / max and as the
+median absolute deviation.
+
+usage: adam_jobs_bench.py [--encoder | --avg] [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -28,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from eav_amd import _lib, synth, transformer as T  # noqa: E402
 from eav_amd.encoder_config import param_shapes  # noqa: E402
 from eav_amd.finetune import encoder_no_decay, encoder_param_groups  # noqa: E402
-from eav_amd.optim import CrossEntropyLoss, FusedAdam, LRSchedule, flatten_parameters  # noqa: E402
+from eav_amd.optim import CrossEntropyLoss, FusedAdam, LRSchedule, WeightAveraging, flatten_parameters  # noqa: E402
 
 WARMUP, TIMED = 10, 30
 lines = []
@@ -123,6 +130,53 @@ def optimiser_bench():
             f"{statistics.median(host[k]):.3f} ms (min {min(host[k]):.3f}, max {max(host[k]):.3f})")
 
 
+def averaging_bench():
+    decay = 0.999
+    opts = {}
+    for label in ("a", "b", "c"):
+        module, _ = ast_sized_module()
+        flat, gflat, _ = flatten_parameters(module)
+        gflat.copy_(torch.randn(gflat.numel(), device="cuda", generator=torch.Generator(device="cuda").manual_seed(2)) * 1e-3)
+        params = list(module.parameters())
+        for p in params:
+            off = p._eav_flat[2]
+            p.grad = gflat[off:off + p.numel()].view(p.shape)
+        opt = FusedAdam(params, lr=5e-6, weight_decay=0.01, decoupled=True, multi_tensor=True)
+        step = opt.step
+        if label == "b":
+            opt.set_averaging(WeightAveraging("ema", decay))
+        elif label == "c":
+            data = [p.data for p in params]
+            avgs = [d.clone() for d in data]
+
+            def step(opt=opt, data=data, avgs=avgs):
+                opt.step()
+                torch._foreach_lerp_(avgs, data, 1.0 - decay)
+        opts[label] = (step, sum(p.numel() for p in params), len(params))
+    n, ntensors = opts["a"][1:]
+    say(f"AST-base layout: {ntensors} tensors, {n} parameters, one group, FusedAdam(multi_tensor=True), EMA decay {decay}")
+    times, host = timed_steps({k: v[0] for k, v in opts.items()})
+    what = {"a": ("step without averaging", 28), "b": ("fused averaging step", 36),
+            "c": ("step without averaging + torch._foreach_lerp_", 40)}
+    for k in ("a", "b", "c"):
+        torch_launches = []
+        if k == "c":            # the lerp's own kernels are not library calls: count them with the profiler
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                torch._foreach_lerp_(avgs, data, 1.0 - decay)
+                torch.cuda.synchronize()
+            torch_launches = [e for e in prof.events() if e.device_type.name != "CPU"]
+        names = launches_of(opts[k][0])
+        ms = statistics.median(times[k])
+        mad = statistics.median(abs(t - ms) for t in times[k])
+        label, nbytes = what[k]
+        say(f"({k}) {label}: median {ms:.3f} ms per step (min {min(times[k]):.3f}, max {max(times[k]):.3f}, MAD {mad:.4f}, "
+            f"{TIMED} steps), {len(names)} library launches per step"
+            + (f" + {len(torch_launches)} of torch's" if k == "c" else "")
+            + f", {nbytes * n / ms / 1e6:.0f} GB/s over {nbytes} B/param; host time median "
+            f"{statistics.median(host[k]):.3f} ms (min {min(host[k]):.3f}, max {max(host[k]):.3f})")
+
+
 def encoder_bench(label, cfg, B):
     x, y = synth.frame_batch(5, B, cfg.H)
     x, y = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
@@ -153,13 +207,17 @@ def encoder_bench(label, cfg, B):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--encoder", action="store_true")
+    ap.add_argument("--avg", action="store_true", help="time the weight-averaging step instead (module docstring)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     global TIMED
     if not torch.cuda.is_available():
         sys.exit("adam_jobs_bench.py measures on the GPU: no device found")
     say(f"{torch.cuda.get_device_name(0)}; {clock_text()}; HIP events around every step, {WARMUP} warm-up, median of {TIMED}")
-    optimiser_bench()
+    if args.avg:
+        averaging_bench()
+    else:
+        optimiser_bench()
     if args.encoder:
         encoder_bench("reduced ViT (2 layers, 64 wide, 56 x 56)",
                       T.make_config("vit", hidden=64, layers=2, heads=4, ff=128, image=56), 128)

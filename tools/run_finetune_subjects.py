@@ -114,6 +114,15 @@ def main():
     ap.add_argument("--drop-path", type=float, default=0.0, metavar="R", help="stochastic depth: every sample of an unfrozen "
                     "epoch drops the residual branches of layer i with probability R i / (layers - 1), timm's DropPath "
                     "(trainer.drop_path); 0 <= R < 1")
+    ap.add_argument("--weight-averaging", choices=("ema", "swa"), default=None, help="evaluate, report and save an average of "
+                    "the weights kept inside the optimiser step (trainer.weight_averaging): exponential (timm's ModelEma) or "
+                    "equal-weight (SWA); default: the last iterate, like the reference")
+    ap.add_argument("--ema-decay", type=float, default=0.999, metavar="D", help="decay of --weight-averaging ema, in [0, 1] "
+                    "(trainer.ema_decay)")
+    ap.add_argument("--ema-warmup", action="store_true", help="use min(D, (1 + n) / (10 + n)) while few steps have been "
+                    "averaged (trainer.ema_warmup)")
+    ap.add_argument("--averaging-start-epoch", type=int, default=0, metavar="E", help="epochs, counted over both phases, "
+                    "trained before the first averaging step (trainer.averaging_start_epoch)")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     if args.grad_accum < 1 or (args.max_grad_norm is not None and not args.max_grad_norm > 0):
@@ -126,6 +135,8 @@ def main():
         ap.error("--patch-dropout takes P with 0 <= P < 1")
     if not 0.0 <= args.drop_path < 1.0:
         ap.error("--drop-path takes R with 0 <= R < 1")
+    if not 0.0 <= args.ema_decay <= 1.0 or args.averaging_start_epoch < 0:
+        ap.error("--ema-decay takes D in [0, 1] and --averaging-start-epoch E >= 0")
     audio = args.kind == "audio"
     if audio and args.hflip:
         ap.error("--hflip is a vision option")
@@ -182,6 +193,8 @@ def main():
                 tr.mixup_alpha, tr.augment_seed = args.mixup_alpha, args.augment_seed
                 tr.patch_dropout = args.patch_dropout
                 tr.drop_path = args.drop_path
+                tr.weight_averaging, tr.ema_decay, tr.ema_warmup = args.weight_averaging, args.ema_decay, args.ema_warmup
+                tr.averaging_start_epoch = args.averaging_start_epoch
                 if audio:
                     tr.time_mask, tr.freq_mask = args.time_mask, args.freq_mask
                 else:
