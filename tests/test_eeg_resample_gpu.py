@@ -114,10 +114,18 @@ def test_an_impulse_reads_the_taps_back(up, down):
 
 
 def test_unreduced_ratio_and_pure_decimation_give_the_same_bits():
+    """An unreduced ratio is reduced before the design (64/250 gives the bits of 32/125; 3/15 is the 101-tap filter of
+    1/5, not a 301-tap one).  Pure decimation has two kernels: eav_decimate_fir_f64 (`decimate`, where `resample` sends
+    up == 1) walks the taps upwards, i.e. the samples downwards, and eav_resample_poly_f64 (`resample_kernel`) walks the
+    samples upwards.  The orders differ, so the bits do (on the MI355X 10 451 of 12 009 outputs at 1/5, by 1.8e-15 at
+    most): what holds is that both lie within the rounding bound of the long-double sum."""
     x = torch.from_numpy(case(32, 125, 20011)[0]).cuda()
     assert same_bits(ed.resample(x, 64, 250).cpu().numpy(), ed.resample(x, 32, 125).cpu().numpy())
-    assert same_bits(ed.resample(x, 1, 5).cpu().numpy(), ed.decimate(x, 5).cpu().numpy())
-    assert same_bits(ed.resample(x, 3, 15).cpu().numpy(), ed.decimate(x, 5).cpu().numpy())
+    host, _, _, ref, bound = case(1, 5, 20011)
+    x = torch.from_numpy(host).cuda()
+    check(ed.decimate(x, 5).cpu().numpy(), ref, bound, "decimate by 5")
+    check(ed.resample_kernel(x, 1, 5).cpu().numpy(), ref, bound, "resample_kernel 1/5")
+    check(ed.resample(x, 3, 15).cpu().numpy(), ref, bound, "resample 3/15")
     assert ed.resample(x, 7, 7) is x
 
 

@@ -273,6 +273,7 @@ def test_frame_preprocessing_bit_exact(golden_dir):
     exp = np.stack([((po.resize_bilinear_u8(f, 96, 48).transpose(2, 0, 1).astype(np.float64) / 255).astype(np.float32)
                      - np.float32([0.485, 0.456, 0.406])[:, None, None]) / np.float32([0.229, 0.224, 0.225])[:, None, None]
                     for f in odd])
+    # superseded by tests/test_preprocess_kernels_gpu.py, which holds these sizes and more to bit equality
     assert np.allclose(got, exp, atol=1e-6)
 
 
@@ -281,6 +282,8 @@ def test_ast_logmel_frontend(golden_dir):
     import os
     from eav_amd.preprocess import waveforms_to_input_values
     from oracle import preprocess_oracle as po
+    # the 5e-6 below is the wrapper's end-to-end check at the workload's shape; tests/test_preprocess_kernels_gpu.py
+    # holds the kernel to a derived per-element bound (a few float32 ulps) at its edges
     g = np.load(os.path.join(golden_dir, "ast_trainer.npz"))
     wav = synth.normal(90, (10, 80000), 0.0, 0.1)
     got = waveforms_to_input_values(wav).cpu().numpy()
@@ -301,6 +304,8 @@ def test_eeg_decimate_and_sosfilt():
     from eav_amd import eeg_data as ed
     x = synth.normal(71, (5, 20011)).astype(np.float64) + 2.0
     xd = torch.from_numpy(x).cuda()
+    # 1e-11 and 1e-9 below are loose end-to-end checks of the wrappers; tests/test_preprocess_kernels_gpu.py holds both
+    # kernels to bounds made of the float64 references' own error against a long-double truth
     for down in (5, 4):
         got = ed.decimate(xd, down).cpu().numpy()
         assert np.abs(got - signal.resample_poly(x, 1, down, axis=1)).max() < 1e-11
