@@ -1,6 +1,6 @@
 """Checking helpers shared by the kernel-level GPU tests (test_audio_cnn_kernels_gpu.py, test_eegnet_canon_kernels_gpu.py,
 test_shallow_tf_kernels_gpu.py, test_encoder_dropout_kernels_gpu.py, test_eegnet_direct_kernels_gpu.py, test_fir_fft_kernels_gpu.py,
-test_preprocess_kernels_gpu.py, test_preprocess_ref_cpu.py, test_batch_glue_kernels_gpu.py): sentinel-filled output buffers with a guard band,
+test_preprocess_kernels_gpu.py, test_preprocess_ref_cpu.py, test_batch_glue_kernels_gpu.py, test_conv64_fft_kernels_gpu.py): sentinel-filled output buffers with a guard band,
 deterministic data, and the two comparisons - bit equality and an element-wise bound; and the operand preparation of the
 split attention kernels (attn_prep, decode_planes: shared with test_split_kernels_gpu.py).
 
